@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench.py -- PnP-SVRG inner-iterations/s on 256x256 CSMRI (20 % sampling) + DnCNN-17 prox.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--workload dncnn|tv|saga-nlm]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--workload dncnn|tv|saga-nlm|sweep] [--full]
+                    [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one inner iteration of pnp_svrg (reference algorithms/pnp_svrg.py:41-94: minibatch SVRG direction via
@@ -13,10 +14,19 @@ Every rank runs its own B problems (weak scaling; the only collective is the fin
 timed region).
 
 Prints ONE JSON line (rank 0) with the driver's contract fields plus `roofline` (dominant kernel = the 64->64 3x3
-conv on the f32 matrix cores; `frac` = EXECUTED MFMA FLOP/s over the f32 matrix peak), `cpu_baseline` (the oracle,
-i.e. the CPU port of the reference path, timed on this box's host cores on a bounded sample) and -- at N = 1 in the
-default configuration -- `secondary`: BASELINE configs 2 (TV prox, HBM-bound) and 4 (Deblur + NLM prox + pnp_saga)
-timed in the same run with their own `roofline` / `cpu_baseline`.
+conv on the f32 matrix cores, timed in-band during the timed steps; `frac` = EXECUTED MFMA FLOP/s over the f32 matrix
+peak).  A plain run does only that: set up, warm up, time the K steps, print the line.
+
+`--full` adds what the headline figure does not need: `cpu_baseline` (the oracle, i.e. the CPU port of the reference
+path, timed on this box's host cores on a bounded sample), config 4's kernel timings that its `roofline` is made of,
+and -- at N = 1 in the default configuration -- `secondary`: BASELINE configs 2 (TV prox, HBM-bound), 4 (Deblur + NLM
+prox + pnp_saga), 3 with the opt-in bf16x3 conv mode and 5 (the sweep) timed in the same run with their own `roofline`
+(and `cpu_baseline`).
+
+`--dump-outputs DIR` writes, after the timed steps, what the timed path hands its caller after its last step (rank 0's
+problems): `z.npy` (the iterates, float32), `sse.npy` (squared error against the ground truth, float64) and `psnr.npy`
+(rounded PSNR, float64) per problem -- for the sweep `z.npy`, `sse.npy` and `item_id.npy` of the gathered items.  Inputs
+are seeded, so two builds run with the same arguments can be compared output for output.
 
 `--gpus N` without torchrun (WORLD_SIZE unset) launches the N ranks itself (torch.distributed.run as a child process,
 before this process touches the GPU) and exits with its status.
@@ -63,8 +73,13 @@ def parse():
                     help='independent reconstructions per GPU (default: 120 = one Set12 x 10 sampling-ratio sweep for dncnn, '
                          '1024 for tv (SURVEY 8d batch list), 64 for saga-nlm)')
     ap.add_argument('--workload', default='dncnn', choices=['dncnn', 'tv', 'saga-nlm', 'sweep'])
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-secondary', action='store_true', help='skip the config-2 / config-4 secondary measurements')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline figure does not need: the CPU baseline, config 4\'s kernel timings and '
+                         '(default configuration, N = 1) the secondary configurations')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baselines')
+    ap.add_argument('--no-secondary', action='store_true', help='with --full: skip the secondary measurements')
     ap.add_argument('--backend', default='nccl', choices=['nccl', 'gloo'],
                     help='gloo + PNP_BENCH_ONE_DEVICE=1 rehearses the N>1 path with all ranks on GPU 0')
     ap.add_argument('--graph', action='store_true',
@@ -413,6 +428,25 @@ def _weights():
     return random_dncnn_weights(17, seed=0), 'random-init weights'
 
 
+DUMP_Z_BYTES = 48 * 2 ** 20                                # iterates written by --dump-outputs (the per-problem arrays are tiny)
+
+
+def dump_outputs(d, z, **per_problem):
+    """--dump-outputs: the iterates z [B, H, W] and per-problem arrays [B] as d/<name>.npy (float32 / float64).  Iterates
+    beyond DUMP_Z_BYTES are written for a fixed seeded sample of the problems, whose indices go to problems.npy."""
+    os.makedirs(d, exist_ok=True)
+    B = z.shape[0]
+    k = min(B, max(1, DUMP_Z_BYTES // (z[0].numel() * 4)))
+    if k < B:
+        idx = np.sort(np.random.default_rng(0).choice(B, k, replace=False))
+        z = z[torch.as_tensor(idx, device=z.device)]
+        np.save(os.path.join(d, 'problems.npy'), idx.astype(np.float64))
+    np.save(os.path.join(d, 'z.npy'), z.detach().float().cpu().numpy())
+    for name, v in per_problem.items():
+        v = v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
+        np.save(os.path.join(d, f'{name}.npy'), v.astype(np.float64))
+
+
 def main():
     a = parse()
     if a.cpu_baseline_child is not None:                        # (no GPU call on this path)
@@ -468,11 +502,13 @@ def main():
     if a.workload == 'sweep':
         dt, warm, w, got = run_sweep_bench(rank, world, weights, a.steps, a.warmup, sync_all, dist, cdev)
         if rank == 0:
+            if a.dump_outputs is not None:
+                dump_outputs(a.dump_outputs, got[0], sse=got[1][:, 1], item_id=got[1][:, 0])
             f = sweep_fields(dt, a.steps, w, got, world)
             line = {'metric': metric_name('sweep'), 'value': f['value'], 'unit': f['unit'], 'n_gpus': world, 'steps': a.steps, 'warmup': warm,
                     'ms_per_step': f['ms_per_step'], 'higher_is_better': True, 'scaling': 'strong', 'vs_baseline': None, 'dtype': 'f32',
                     'data': 'synthetic', 'config': f['config'], 'roofline': f['roofline'],
-                    'cpu_baseline': None if a.no_cpu_baseline else cpu_baseline('dncnn', weights), 'psnr_db': f['psnr_db']}
+                    'cpu_baseline': cpu_baseline('dncnn', weights) if a.full and not a.no_cpu_baseline else None, 'psnr_db': f['psnr_db']}
             print(json.dumps(line))
         if dist is not None:
             dist.barrier()
@@ -493,12 +529,15 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=cdev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    if a.workload == 'saga-nlm':
-        w.time_nlm_and_update()
-    roofline = None if (a.graph and a.workload == 'dncnn') else w.roofline(dt / a.steps)
+    trace = w.eng.psnr_trace()
+    if rank == 0 and a.dump_outputs is not None:                 # (before anything else launches on the engine's buffers)
+        eng = w.eng
+        dump_outputs(a.dump_outputs, eng.z, sse=eng.sse_log[(eng.n_prox - 1) % eng.n_log], psnr=trace[-1])
+    if a.workload == 'saga-nlm' and a.full:
+        w.time_nlm_and_update()                                 # config 4's roofline: its two kernels timed in runs of their own
+    roofline = None if (a.graph and a.workload == 'dncnn') or (a.workload == 'saga-nlm' and not a.full) else w.roofline(dt / a.steps)
 
     # final gather of the results (the only collective on this path; outside the timed region)
-    trace = w.eng.psnr_trace()
     psnr0 = float(np.mean(w.batch.psnr_init()))
     final_psnr = torch.from_numpy(np.ascontiguousarray(trace[-1])).to(cdev)
     if dist is not None:
@@ -510,7 +549,7 @@ def main():
 
     if rank == 0:
         secondary = None
-        if world == 1 and a.workload == 'dncnn' and not a.no_secondary and not a.graph and a.conv is None and a.batch is None:
+        if a.full and world == 1 and a.workload == 'dncnn' and not a.no_secondary and not a.graph and a.conv is None and a.batch is None:
             # BASELINE configs 2 and 4 in the same run, each with its own roofline (and a short CPU baseline)
             secondary = {}
             del w.eng, w.prox, w.batch
@@ -558,7 +597,7 @@ def main():
             del w5, got5
             torch.cuda.empty_cache()
         cpu = None
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             cpu = cpu_baseline(a.workload, weights)
         value = world * B * a.steps / dt
         line = {

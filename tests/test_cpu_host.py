@@ -386,3 +386,28 @@ def test_legacy_choice_delegates_outside_its_contract():
         legacy_rng.choice(np.zeros((2, 2), int), 1)
     with pytest.raises(ValueError):
         legacy_rng.choice(3, 5)
+
+
+def test_bench_dump_outputs_samples_large_iterates(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: iterates beyond the byte budget are written for a fixed seeded sample of the problems (the
+    same in every run, indices in problems.npy); per-problem arrays stay whole, float64; within the budget nothing is
+    sampled."""
+    import bench
+    B, n = 12, 64
+    z = torch.arange(B * n * n, dtype=torch.float32).reshape(B, n, n)
+    sse = torch.arange(B, dtype=torch.float64) + 0.5
+    monkeypatch.setattr(bench, 'DUMP_Z_BYTES', 5 * n * n * 4)
+    for run in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / run), z, sse=sse, psnr=np.arange(B, dtype=np.float32))
+    idx = np.load(tmp_path / 'a' / 'problems.npy')
+    assert idx.dtype == np.float64 and np.array_equal(idx, np.load(tmp_path / 'b' / 'problems.npy'))
+    assert len(idx) == 5 and np.array_equal(idx, np.unique(idx)) and idx.min() >= 0 and idx.max() < B
+    zd = np.load(tmp_path / 'a' / 'z.npy')
+    assert zd.dtype == np.float32 and np.array_equal(zd, z.numpy()[idx.astype(int)])
+    for name, ref in (('sse', sse.numpy()), ('psnr', np.arange(B))):
+        v = np.load(tmp_path / 'a' / f'{name}.npy')
+        assert v.dtype == np.float64 and np.array_equal(v, ref)
+    monkeypatch.setattr(bench, 'DUMP_Z_BYTES', B * n * n * 4)
+    bench.dump_outputs(str(tmp_path / 'c'), z, sse=sse)
+    assert sorted(os.listdir(tmp_path / 'c')) == ['sse.npy', 'z.npy']
+    assert np.array_equal(np.load(tmp_path / 'c' / 'z.npy'), z.numpy())

@@ -151,14 +151,14 @@ def test_bench_line_smoke():
 
 
 def test_bench_default_line_has_secondary_configs():
-    """The default configuration (B = 120) carries configs 2 and 4 as `secondary` with their own rooflines, and the
-    headline `frac` stays a fraction at the default batch."""
+    """With --full, the default configuration (B = 120) carries configs 2 and 4 as `secondary` with their own rooflines, and
+    the headline `frac` stays a fraction at the default batch."""
     import json
     import subprocess
     import sys
     import os
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '3', '--warmup', '1', '--no-cpu-baseline'],
+    out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--full', '--steps', '3', '--warmup', '1', '--no-cpu-baseline'],
                          capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])
@@ -168,6 +168,35 @@ def test_bench_default_line_has_secondary_configs():
     assert sec['saga-nlm']['roofline']['bound'] == 'valu' and sec['saga-nlm']['value'] > 0
     assert sec['saga-nlm']['roofline']['saga_table_update']['bound'] == 'hbm'
     assert sec['tv']['psnr_db']['after_timed_steps_mean'] > sec['tv']['psnr_db']['initial_mean']
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain run (no --full) times the headline path alone: no `secondary`, no CPU baseline, `steps` timed steps.
+    --dump-outputs writes the last step's iterates and per-problem figures, and two runs with the same arguments write the
+    same arrays bit for bit."""
+    import json
+    import subprocess
+    import sys
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    B, steps, dumps = 2, 3, []
+    for run in range(2):
+        d = tmp_path / f'run{run}'
+        out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', str(steps), '--warmup', '1', '--batch', str(B),
+                              '--dump-outputs', str(d)], capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        line = json.loads(out.stdout.strip().splitlines()[-1])
+        assert 'secondary' not in line and line['cpu_baseline'] is None and line['steps'] == steps
+        assert abs(line['value'] - B * steps / (line['ms_per_step'] * steps / 1e3)) < 1e-2 * line['value']
+        dumps.append({n: np.load(d / f'{n}.npy') for n in ('z', 'sse', 'psnr')})
+        assert sorted(os.listdir(d)) == ['psnr.npy', 'sse.npy', 'z.npy']
+        assert abs(line['psnr_db']['after_timed_steps_mean'] - float(np.mean(dumps[-1]['psnr']))) < 1e-9
+    z, sse, psnr = dumps[0]['z'], dumps[0]['sse'], dumps[0]['psnr']
+    assert z.dtype == np.float32 and z.shape == (B, 256, 256) and np.isfinite(z).all()
+    assert sse.dtype == psnr.dtype == np.float64 and sse.shape == psnr.shape == (B,)
+    assert np.array_equal(psnr, np.around(10 * np.log10(1.0 / (sse / (256 * 256))), 2))
+    for n in dumps[0]:
+        assert np.array_equal(dumps[0][n], dumps[1][n]), n
 
 
 def _mix64(x):

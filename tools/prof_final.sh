@@ -6,5 +6,5 @@ cd $GRAFT_REPO_ROOT
 O=gpurun_out/r02
 rm -rf $O && mkdir -p $O
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/dncnn_stats -- python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-secondary > $O/dncnn_stats.json 2> $O/dncnn_stats.err
-python3 bench.py > $O/bench_default.json 2> $O/bench_default.err
+python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 echo "final done"

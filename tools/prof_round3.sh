@@ -14,5 +14,5 @@ rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/tv_w -- $TV 
 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES --output-format csv -d $O/tv_sq1 -- $TV --steps 30 --warmup 10 > $O/tv_sq1.json 2> $O/tv_sq1.err && echo tv sq1 done
 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SALU SQ_WAIT_INST_LDS SQ_WAVES --output-format csv -d $O/tv_sq2 -- $TV --steps 30 --warmup 10 > $O/tv_sq2.json 2> $O/tv_sq2.err && echo tv sq2 done
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/dncnn_stats -- python3 bench.py --no-cpu-baseline --no-secondary > $O/dncnn_stats.json 2> $O/dncnn_stats.err && echo dncnn stats done
-python3 bench.py > $O/bench_default.json 2> $O/bench_default.err && echo default bench done
+python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err && echo default bench done
 tail -c 600 $O/bench_default.json
