@@ -40,15 +40,17 @@ def db2_detail_cols(img):
 
 
 def sigma_cols(img):
-    """Per-column MAD sigma: median(|d[d != 0]|) / 0.6745 (skimage _sigma_est_dwt)."""
-    d = np.abs(db2_detail_cols(img))
-    d = np.where(d == 0.0, np.nan, d)
+    """Per-column MAD sigma: median(|d[d != 0]|) / 0.6745 (skimage _sigma_est_dwt).  A NaN coefficient is nonzero, so
+    np.median sees it and the column's estimate is NaN."""
     with np.errstate(all='ignore'):
+        d = np.abs(db2_detail_cols(img))
+        has_nan = np.isnan(d).any(axis=0)
+        d = np.where(d == 0.0, np.nan, d)
         import warnings
         with warnings.catch_warnings():
             warnings.simplefilter('ignore')
             med = np.nanmedian(d, axis=0)
-    return med / MAD_DENOM
+    return np.where(has_nan, np.nan, med) / MAD_DENOM
 
 
 def estimate_sigma(img):

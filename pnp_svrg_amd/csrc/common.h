@@ -41,14 +41,15 @@ template <typename T> __device__ __forceinline__ T wave_sum(T v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+// min / max over the wave; NaN if any lane holds NaN (np.min / np.max), else the same selection as `u < v ? u : v`
 template <typename T> __device__ __forceinline__ T wave_min(T v) {
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { T u = __shfl_xor(v, o, 64); v = u < v ? u : v; }
+    for (int o = 32; o > 0; o >>= 1) { T u = __shfl_xor(v, o, 64); v = (u < v || u != u) ? u : v; }
     return v;
 }
 template <typename T> __device__ __forceinline__ T wave_max(T v) {
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { T u = __shfl_xor(v, o, 64); v = u > v ? u : v; }
+    for (int o = 32; o > 0; o >>= 1) { T u = __shfl_xor(v, o, 64); v = (u > v || u != u) ? u : v; }
     return v;
 }
 

@@ -83,10 +83,12 @@ int run_pr(const T* A, const T* w, const T* y, const int32_t* rows, int nsel, in
     const int nchunks = 64;
     T* u = ws;                               // [batch][M] (first nsel of each used)
     T* part = ws + (size_t)batch * M;        // [batch][nchunks][N]
-    const dim3 rg((nsel * 64 + 255) / 256, batch);
-    if (spectral) k_pr_rows<T, true><<<rg, 256, 0, s>>>(A, w, y, rows, nsel, M, N, u);
-    else k_pr_rows<T><<<rg, 256, 0, s>>>(A, w, y, rows, nsel, M, N, u);
-    PNP_CHECK_LAUNCH();
+    if (nsel > 0) {                          // nsel == 0: no row, empty chunks below, out = 0 (a zero-sized grid is an error)
+        const dim3 rg((nsel * 64 + 255) / 256, batch);
+        if (spectral) k_pr_rows<T, true><<<rg, 256, 0, s>>>(A, w, y, rows, nsel, M, N, u);
+        else k_pr_rows<T><<<rg, 256, 0, s>>>(A, w, y, rows, nsel, M, N, u);
+        PNP_CHECK_LAUNCH();
+    }
     const int rpc = (nsel + nchunks - 1) / nchunks;
     k_pr_cols<T><<<dim3((N + 255) / 256, nchunks, batch), 256, 0, s>>>(A, u, rows, nsel, M, N, rpc, nchunks, part);
     PNP_CHECK_LAUNCH();

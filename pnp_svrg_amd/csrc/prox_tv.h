@@ -191,7 +191,7 @@ __device__ __forceinline__ void haar_bayes_shrink(T (&x)[H / 4], T var) {
         ss = col_sum(ss);
         const T dvar = ss / (T)(H >> (lev + 1));
         T den = dvar - var;
-        den = den > (T)2.220446049250313e-16 ? den : (T)2.220446049250313e-16;
+        den = (den > (T)2.220446049250313e-16 || den != den) ? den : (T)2.220446049250313e-16;   // max(NaN, eps) is NaN
         thr[lev] = var / sqrt(den);
     }
 #pragma unroll

@@ -65,6 +65,38 @@ def test_sigma_est_and_haar_bayes(g_denoise, tag):
                                g[f'{tag}_tv_mod'], rtol=0, atol=1e-14)
 
 
+@pytest.mark.parametrize('tag', ['h16w48', 'h128w32', 'h32w256'])
+def test_sigma_est_and_haar_bayes_other_shapes(tag):
+    """The same pins at H = 16 (one Haar level) and on non-square images (tests/golden/make_golden_tv_shapes.py)."""
+    g = golden('tv_shapes.npz')
+    z0 = g[f'{tag}_z0']
+    s = od.estimate_sigma(z0)
+    assert abs(s - float(g[f'{tag}_sigma_est'])) <= 1e-15
+    np.testing.assert_allclose(od.TVDenoiser().denoise(noisy=z0, sigma_est=s), g[f'{tag}_tv'], rtol=0, atol=1e-14)
+    np.testing.assert_allclose(od.TVDenoiser(sigma_modifier=1.7).denoise(noisy=z0, sigma_est=s), g[f'{tag}_tv_mod'],
+                               rtol=0, atol=1e-14)
+    d = od.TVDenoiser(denoise_strength=0.07, decay=0.9)
+    np.testing.assert_allclose(d.denoise(noisy=z0, sigma_est=0), g[f'{tag}_tv_strength'], rtol=0, atol=1e-14)
+
+
+def test_sigma_est_and_haar_bayes_nonfinite():
+    """NaN / +-inf pixels: a NaN detail coefficient is nonzero, so the library's median (and the estimate) is NaN; the
+    prox of the NaN column is NaN throughout (max(NaN, eps) in the BayesShrink threshold is NaN)."""
+    g = golden('tv_shapes.npz')
+    z = g['nonfinite_z0']
+    with np.errstate(all='ignore'):
+        s = np.array([od.estimate_sigma(x) for x in z])
+        out = np.stack([od.TVDenoiser(denoise_strength=0.05).denoise(noisy=x, sigma_est=v) for x, v in zip(z, s)])
+    ref_s, ref = g['nonfinite_sigma_est'], g['nonfinite_tv']
+    assert np.array_equal(np.isnan(s), np.isnan(ref_s)) and np.isnan(ref_s[:2]).all()
+    assert abs(s[2] - ref_s[2]) <= 1e-15
+    assert np.array_equal(np.isnan(out), np.isnan(ref)) and np.array_equal(np.isinf(out), np.isinf(ref))
+    assert np.isnan(ref[0, :, 7]).all()
+    fin = np.isfinite(ref)
+    np.testing.assert_allclose(out[fin], ref[fin], rtol=0, atol=1e-14)
+    np.testing.assert_array_equal(out[np.isinf(ref)], ref[np.isinf(ref)])
+
+
 def test_sigma_est_edges(g_denoise):
     g = g_denoise
     assert od.estimate_sigma(np.full((64, 64), 0.25)) == pytest.approx(float(g['const_sigma_est']), abs=1e-15)
