@@ -279,6 +279,9 @@ size_t pnp_dncnn_debug_w44_floats(void);
 int pnp_dncnn_debug_w44_weights(pnp_dncnn_plan* plan, int layer, float* dst, void* stream);
 int pnp_dncnn_debug_mid_layer(pnp_dncnn_plan* plan, int layer, const float* in, float* out, const float* w44_override,
                               int w44_rows, void* stream);
+// the last middle layer with the 64 -> 1 output conv fused in (conv mode 5, ReLU): in [B][64][H][W] -> the 6 x 6 output patch
+// of every 4 x 4 block, part [B][H/4][W/4][6][6] (pixel (4 by + py - 1, 4 bx + px - 1)); w44_rows as above
+int pnp_dncnn_debug_fused_last(pnp_dncnn_plan* plan, const float* in, float* part, int w44_rows, void* stream);
 
 /* Device-resident step counter and log ring (hipGraph replay of a whole outer iteration: nothing in the graph
  * depends on a host-side step index).  pnp_log_append: log[(*step_dev % n_log)][0..n) = src[0..n).        */

@@ -63,6 +63,7 @@ SIGNATURES = {
     'pnp_dncnn_debug_w44_floats': (_sz, []),
     'pnp_dncnn_debug_w44_weights': (_i, [_vp, _i, _vp, _vp]),
     'pnp_dncnn_debug_mid_layer': (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp]),
+    'pnp_dncnn_debug_fused_last': (_i, [_vp, _vp, _vp, _i, _vp]),
     'pnp_draw_thresholds': (_i, [_i, _i, _i, ctypes.c_uint64, ctypes.c_uint32, _i, _vp, _vp, _vp]),
     'pnp_indicator_from_thresholds': (_i, [_i, _i, _vp, _vp, _vp]),
     'pnp_rows_from_thresholds': (_i, [_i, _i, _i, _vp, _vp, _vp]),

@@ -33,6 +33,7 @@
 #include <vector>
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 namespace pnp {
 
@@ -613,6 +614,54 @@ __global__ __launch_bounds__(256) void k_last(const float* __restrict__ act, con
     }
 }
 
+// the rest of k_last behind the fused last layer (conv mode 5, ReLU net; wino44.h): r = the sum of the up to four 6 x 6
+// patches part[b][by][bx] that cover a pixel (own block, the vertical, the horizontal, the diagonal neighbour: one fixed
+// order), then the same epilogue.  Workgroup = 4 x 64 pixels (16 blocks of one block row), one pixel per thread.
+template <typename T>
+__global__ __launch_bounds__(256) void k_last_patches(const float* __restrict__ part, const T* zin, const T* __restrict__ mm,
+                                                      T* zout, float* __restrict__ r_out, const T* __restrict__ xrec,
+                                                      double* __restrict__ sse_part, int H, int W, double srange, double sshift,
+                                                      float blast) {
+    __shared__ double red[4];
+    const int tid = threadIdx.x, b = blockIdx.z;
+    const int iy = tid >> 6, ix = tid & 3, bx = blockIdx.x * 16 + ((tid >> 2) & 15), by = blockIdx.y;
+    const int y = 4 * by + iy, x = 4 * bx + ix;
+    const int NBX = W / 4, NBY = H / 4;
+    const float* pb = part + (size_t)b * NBY * NBX * 36;
+    auto at = [&](int qy, int qx, int py, int px) { return pb[((size_t)qy * NBX + qx) * 36 + py * 6 + px]; };
+    const int vy = iy == 0 ? -1 : iy == 3 ? 1 : 0, vx = ix == 0 ? -1 : ix == 3 ? 1 : 0;     // neighbour whose spill-over reaches here
+    const bool hv = vy != 0 && by + vy >= 0 && by + vy < NBY, hh = vx != 0 && bx + vx >= 0 && bx + vx < NBX;
+    const int py = iy + 1, px = ix + 1, pyn = py - 4 * vy, pxn = px - 4 * vx;              // position in own / neighbour patch
+    float r = at(by, bx, py, px);
+    if (hv) r += at(by + vy, bx, pyn, px);
+    if (hh) r += at(by, bx + vx, py, pxn);
+    if (hv && hh) r += at(by + vy, bx + vx, pyn, pxn);
+    r += blast;                                                 // 0 for the DnCNN family (bias-free last layer)
+    const size_t p = (size_t)b * H * W + (size_t)y * W + x;
+    if (r_out != nullptr) r_out[p] = r;
+    double err = 0.0;
+    if (zout != nullptr) {
+        const T lo = mm ? mm[2 * b] : (T)0, hi = mm ? mm[2 * b + 1] : (T)1;
+        T v = (zin[p] - lo) / (hi - lo);
+        v = v * (T)srange + (T)sshift;
+        v = v - (T)r;
+        v = (v - (T)sshift) / (T)srange;
+        v = v * (hi - lo) + lo;
+        zout[p] = v;
+        if (xrec != nullptr) {
+            const double d = (double)xrec[p] - (double)v;
+            err = d * d;
+        }
+    }
+    if (sse_part != nullptr) {
+        err = wave_sum(err);
+        if ((tid & 63) == 0) red[tid >> 6] = err;
+        __syncthreads();
+        if (tid == 0)
+            sse_part[((size_t)b * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+    }
+}
+
 __global__ void k_sum_parts(const double* __restrict__ part, int nparts, double* __restrict__ out) {
     double s = 0;
     for (int i = threadIdx.x; i < nparts; i += 64) s += part[(size_t)blockIdx.x * nparts + i];
@@ -632,6 +681,8 @@ struct pnp_dncnn_plan {
     float* b_first;                              // [64] device, zeros unless pnp_dncnn_set_affine
     float b_last, slope;                         // last-layer bias, LeakyReLU slope (0 = ReLU)
     int use_wino;
+    bool edge_fusion;                            // conv mode 5, ReLU, float: the last layer inside the last middle layer
+    float* part;                                 // its output patches [B][H/4][W/4][36] (wino44.h); null without F(4x4,3x3)
     float *act0, *act1, *zeros;                  // [B][64][H][W] x2; a zero word for halo padding
     double* mm;                                  // [B][2] (as double or float depending on call)
     double* sse_part;                            // [B][H*W/256]
@@ -688,6 +739,9 @@ extern "C" int pnp_dncnn_plan_create(pnp_dncnn_plan** out, int n_mid, const floa
         p->use_wino = ev ? atoi(ev) : 5;
         if (p->use_wino != 6 && p->use_wino != 5 && p->use_wino != 1 && p->use_wino != 0) p->use_wino = 5;      // (unknown value: the default)
         if (p->use_wino >= 5 && !wino44_supports(H, W)) p->use_wino = 1;
+        // PNP_DNCNN_EDGE_FUSION=0: the separate last-layer kernel everywhere (A/B runs and tests; read once per plan)
+        const char* ef = getenv("PNP_DNCNN_EDGE_FUSION");
+        p->edge_fusion = !(ef && atoi(ef) == 0);
     }
     const size_t act_bytes = (size_t)batch * C * H * W * sizeof(float);
     hipError_t e = hipMalloc(&p->wpack, pack.size() * sizeof(float));
@@ -720,11 +774,12 @@ extern "C" int pnp_dncnn_plan_create(pnp_dncnn_plan** out, int n_mid, const floa
     if (e == hipSuccess) e = hipMemset(p->zeros, 0, 256);
     if (e == hipSuccess) e = hipMalloc(&p->mm, (size_t)batch * 2 * sizeof(double));
     if (e == hipSuccess) e = hipMalloc(&p->sse_part, (size_t)batch * (H * W / 256) * sizeof(double));
+    if (e == hipSuccess && wino44_supports(H, W)) e = hipMalloc(&p->part, wino44_part_floats(H, W, batch) * sizeof(float));
     if (e != hipSuccess) {
         set_error(std::string("pnp_dncnn_plan_create: ") + hipGetErrorString(e));
         for (void* q : {(void*)p->wpack, (void*)p->upack, (void*)p->bias, (void*)p->w_first, (void*)p->w_last, (void*)p->act0,
                         (void*)p->act1, (void*)p->zeros, (void*)p->mm, (void*)p->sse_part, (void*)p->b_first, (void*)p->upack44,
-                        (void*)p->upack44b})
+                        (void*)p->upack44b, (void*)p->part})
             if (q) (void)hipFree(q);
         delete p;
         return PNP_ERR_HIP;
@@ -736,7 +791,8 @@ extern "C" int pnp_dncnn_plan_create(pnp_dncnn_plan** out, int n_mid, const floa
 extern "C" int pnp_dncnn_plan_destroy(pnp_dncnn_plan* p) {
     if (!p) return PNP_OK;
     for (void* q : {(void*)p->wpack, (void*)p->upack, (void*)p->bias, (void*)p->w_first, (void*)p->w_last, (void*)p->act0, (void*)p->act1,
-                    (void*)p->zeros, (void*)p->mm, (void*)p->sse_part, (void*)p->b_first, (void*)p->upack44, (void*)p->upack44b})
+                    (void*)p->zeros, (void*)p->mm, (void*)p->sse_part, (void*)p->b_first, (void*)p->upack44, (void*)p->upack44b,
+                    (void*)p->part})
         (void)hipFree(q);
     for (hipEvent_t e : p->ev) (void)hipEventDestroy(e);
     delete p;
@@ -762,6 +818,9 @@ int run_dncnn(pnp_dncnn_plan* p, const T* z_in, bool normalise, double sigma_net
     const int ntiles = B * (H / TR) * (W / TC);
     const int grid = ntiles < p->num_cu ? ntiles : p->num_cu;
     float *src = p->act0, *dst = p->act1;
+    // the DnCNN family on the F(4x4,3x3) kernel: the 64 -> 1 output conv runs in the last middle layer's epilogue
+    const bool fuse_last = p->edge_fusion && p->use_wino == 5 && p->slope == 0.f && !mmo && std::is_same<T, float>::value &&
+                           p->part != nullptr;
     const bool prof = p->profile && p->ev_used + 2 <= p->ev.size();
     if (prof) PNP_CHECK_HIP(hipEventRecord(p->ev[p->ev_used], s));
     for (int l = 0; l < p->n_mid; ++l) {
@@ -770,8 +829,9 @@ int run_dncnn(pnp_dncnn_plan* p, const T* z_in, bool normalise, double sigma_net
                                          H, W, B, p->num_cu, p->slope, s);
             if (rc != PNP_OK) return rc;
         } else if (p->use_wino == 5) {
+            const bool fl = fuse_last && l == p->n_mid - 1;
             const int rc = wino44_layer(src, dst, p->upack44 + (size_t)l * wino44_weight_floats(1), p->bias + (size_t)l * C, p->zeros,
-                                        H, W, B, p->num_cu, p->slope, s);
+                                        H, W, B, p->num_cu, p->slope, s, 0, fl ? p->w_last : nullptr, fl ? p->part : nullptr);
             if (rc != PNP_OK) return rc;
         } else if (p->slope != 0.f) {                             // LeakyReLU builds exist for the two production kernels
             if (p->use_wino)
@@ -790,6 +850,17 @@ int run_dncnn(pnp_dncnn_plan* p, const T* z_in, bool normalise, double sigma_net
         float* t = src; src = dst; dst = t;
     }
     if (prof) { PNP_CHECK_HIP(hipEventRecord(p->ev[p->ev_used + 1], s)); p->ev_used += 2; }
+    if (fuse_last) {
+        const dim3 fg(W / 64, H / 4, B);
+        k_last_patches<T><<<fg, 256, 0, s>>>(p->part, z_in, mm, z_out, r_out, xrec, sse_out ? p->sse_part : nullptr, H, W, srange,
+                                             sshift, p->b_last);
+        PNP_CHECK_LAUNCH();
+        if (sse_out) {
+            k_sum_parts<<<B, 64, 0, s>>>(p->sse_part, (int)(fg.x * fg.y), sse_out);
+            PNP_CHECK_LAUNCH();
+        }
+        return PNP_OK;
+    }
     dim3 lg((W + LT_C - 1) / LT_C, (H + LT_R - 1) / LT_R, B);
     k_last<T><<<lg, 256, 0, s>>>(src, p->w_last, z_in, mm, z_out, r_out, xrec, sse_out ? p->sse_part : nullptr, H, W,
                                  srange, sshift, mmo ? 1 : 0, p->b_last);
@@ -833,6 +904,15 @@ extern "C" int pnp_dncnn_debug_mid_layer(pnp_dncnn_plan* p, int layer, const flo
         k_mid<true><<<grid, 256, 0, s>>>(in, out, p->wpack + (size_t)l * 4 * 2 * KSTEPS_HALF * 64, p->bias + (size_t)l * C, p->zeros, H, W, ntiles);
     PNP_CHECK_LAUNCH();
     return PNP_OK;
+}
+
+extern "C" int pnp_dncnn_debug_fused_last(pnp_dncnn_plan* p, const float* in, float* part, int w44_rows, void* stream) {
+    PNP_CHECK_ARG(p && in && part && w44_rows >= 0 && w44_rows <= 2, "bad argument");
+    PNP_CHECK_ARG(p->use_wino == 5 && p->slope == 0.f && p->part != nullptr,
+                  "the fused last layer needs the F(4x4,3x3) kernel (mode 5) and ReLU");
+    const int l = p->n_mid - 1;
+    return wino44_layer(in, nullptr, p->upack44 + (size_t)l * wino44_weight_floats(1), p->bias + (size_t)l * C, p->zeros, p->H, p->W,
+                        p->batch, p->num_cu, 0.f, (hipStream_t)stream, w44_rows, p->w_last, part);
 }
 
 extern "C" int pnp_dncnn_set_affine(pnp_dncnn_plan* p, const float* b_first, float b_last, float negative_slope) {

@@ -318,16 +318,29 @@ template <int VPL> __device__ __forceinline__ void transform0(const float* dsrc,
     }
 }
 
+// Last-layer fusion (FL): the DnCNN's 64 -> 1 output conv folded into the epilogue of the last middle layer.  Instead of its
+// 64 channels, a 4 x 4 block leaves the 6 x 6 patch of output partials it feeds,
+//     part[b][by][bx][py][px] = sum_c sum_(dy,dx) w_last[c][dy][dx] a[c][4 by + py + dy - 2][4 bx + px + dx - 2]
+// restricted to the block's own activations (patch row / column 0 and 5 are the one-pixel spill-over into the neighbouring
+// blocks); finish_last_layer (dncnn.hip) adds the up to four patches that cover a pixel.  36 floats per 16 pixels instead
+// of 64 x 16.  The sums: within a lane (its 4 channels) in registers, across its wave's four channel groups by a
+// reduce-scatter over lanes, across the four waves through LDS -- one fixed order per block, whatever the region form.
+constexpr int FL_PATCH = 36;
+constexpr int FL_BLK = 16 * FL_PATCH;                 // one block row of a region: 16 blocks x 36
+template <int NG, bool FL> constexpr int fl_lds_floats() { return FL ? C * 9 + NG * 4 * FL_BLK : 0; }   // w_last + [NG][wave][576]
+
 // STAMP: diagnostic build only (wino44_debug_clock): s_memtime / s_memrealtime around the tile loop, the chunk-end waits and
 // the epilogue; the stamps go to their own buffer
-template <bool LEAKY, int NG = 2, bool STAMP = false, int VAR = 0>
+template <bool LEAKY, int NG = 2, bool STAMP = false, int VAR = 0, bool FL = false>
 __global__ __launch_bounds__(256, 1) void k_mid_wino44(const float* __restrict__ in, float* __restrict__ out,
                                                        const float4* __restrict__ upack, const float* __restrict__ bias,
                                                        int H, int W, int ntiles, float slope,
-                                                       unsigned long long* __restrict__ stamps = nullptr, int tile0 = 0) {
+                                                       unsigned long long* __restrict__ stamps = nullptr, int tile0 = 0,
+                                                       const float* __restrict__ wlast = nullptr, float* __restrict__ part = nullptr) {
     using G = Geo<NG>;
     constexpr int TR = G::TR, PR = G::PR, PLANE = G::PLANE, DBUF = G::DBUF, PPW = G::PPW, VPL = G::VPL, VBUF = G::VBUF;
-    __shared__ __attribute__((aligned(16))) float lds[G::LDS_FLOATS];
+    static_assert(!(FL && LEAKY), "the fused last layer is built for the ReLU net");
+    __shared__ __attribute__((aligned(16))) float lds[G::LDS_FLOATS + fl_lds_floats<NG, FL>()];
     const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     // Regions are numbered in units of 8 x 64 pixels (`tile0` + ...) whatever the form: a 4 x 64 region u is sub-row u & 1 of
     // unit tile0 + (u >> 1), so that a launch of the one-row form can take over the units a two-row launch left (the last,
@@ -410,6 +423,10 @@ __global__ __launch_bounds__(256, 1) void k_mid_wino44(const float* __restrict__
     const TileWalk tw_ = tile_walk(ntiles);
     int tile = tw_.first;
     const int limit = tw_.limit < ntiles ? tw_.limit : ntiles;
+    float* const flw = lds + G::LDS_FLOATS;                // FL: w_last [64][9], then the cross-wave exchange [NG][4][576]
+    float* const flx = flw + C * 9;
+    if constexpr (FL)
+        for (int i = tid; i < C * 9; i += 256) flw[i] = wlast[i];
     {
         const TileDma td0 = tile_dma(tile < limit ? tile : ntiles);
 #pragma unroll
@@ -462,10 +479,20 @@ __global__ __launch_bounds__(256, 1) void k_mid_wino44(const float* __restrict__
         unsigned so = st_off;                 // (re-defined inside the loop: its zero-extension must sit next to the stores for
         asm volatile("" : "+v"(so));          //  instruction selection to fold it into the scalar-base addressing mode)
         __attribute__((address_space(1))) char* const ob = (__attribute__((address_space(1))) char*)out + 4 * ((((size_t)b * C + 16 * wv) * H + ty0) * (size_t)W + tx0);
+        float q[FL_PATCH];                                      // FL: this lane's output patch of the current block, its 4 channels
 #pragma unroll
         for (int blk = 0; blk < 2 * NG; ++blk) {
             {
                 const int g2 = NG == 2 ? 1 - (blk >> 1) : 0, pi = blk & 1;   // block row 1 first: it frees the eight VGPR accumulator quads
+                float wr[2][9];                                 // FL: w_last of channels 2 pi, 2 pi + 1 of the lane's four
+                if constexpr (FL) {
+                    if (pi == 0)
+#pragma unroll
+                        for (int i = 0; i < FL_PATCH; ++i) q[i] = 0.f;
+                    const float* wc = flw + (16 * wv + 4 * (lane >> 4) + 2 * pi) * 9;
+#pragma unroll
+                    for (int t = 0; t < 9; ++t) { wr[0][t] = wc[t]; wr[1][t] = wc[9 + t]; }
+                }
                 // no weight load is in flight across the epilogue (a spilled in-flight load costs its whole latency); the
                 // ring's first entries of the next tile go out before the last block
                 if (blk == 2 * NG - 1) {
@@ -506,14 +533,60 @@ __global__ __launch_bounds__(256, 1) void k_mid_wino44(const float* __restrict__
                         v0.x = fmaxf(y[0].x, 0.f); v0.y = fmaxf(y[1].x, 0.f); v0.z = fmaxf(y[2].x, 0.f); v0.w = fmaxf(y[3].x, 0.f);
                         v1.x = fmaxf(y[0].y, 0.f); v1.y = fmaxf(y[1].y, 0.f); v1.z = fmaxf(y[2].y, 0.f); v1.w = fmaxf(y[3].y, 0.f);
                     }
-                    *(__attribute__((address_space(1))) f32x4*)(oc + so) = v0;          // channel 2 pi, row 4 g2 + r
-                    oc += hw4;
-                    asm volatile("" : "+s"(oc));
-                    *(__attribute__((address_space(1))) f32x4*)(oc + so) = v1;          // channel 2 pi + 1
-                    oc += w4 - hw4;
-                    asm volatile("" : "+s"(oc));
+                    if constexpr (FL) {
+                        // activation (r, k) of the block feeds patch position (r + 2 - dy, k + 2 - dx) through tap (dy, dx)
+                        const float a0[4] = {v0.x, v0.y, v0.z, v0.w}, a1[4] = {v1.x, v1.y, v1.z, v1.w};
+#pragma unroll
+                        for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+                            for (int dx = 0; dx < 3; ++dx)
+#pragma unroll
+                                for (int k = 0; k < 4; ++k) {
+                                    float& d = q[(r + 2 - dy) * 6 + k + 2 - dx];
+                                    d = __builtin_fmaf(wr[0][dy * 3 + dx], a0[k], d);
+                                    d = __builtin_fmaf(wr[1][dy * 3 + dx], a1[k], d);
+                                }
+                    } else {
+                        *(__attribute__((address_space(1))) f32x4*)(oc + so) = v0;          // channel 2 pi, row 4 g2 + r
+                        oc += hw4;
+                        asm volatile("" : "+s"(oc));
+                        *(__attribute__((address_space(1))) f32x4*)(oc + so) = v1;          // channel 2 pi + 1
+                        oc += w4 - hw4;
+                        asm volatile("" : "+s"(oc));
+                    }
                     if (r & 1) __builtin_amdgcn_sched_barrier(0);
                 }
+                if constexpr (FL) {
+                    if (pi == 1) {
+                        // reduce-scatter over the four channel groups (lanes tc + 16 cg): lane keeps patch entries 9 cg .. 9 cg + 8
+                        const bool h32 = (lane & 32) != 0, h16 = (lane & 16) != 0;
+                        float k1[18], k2[9];
+#pragma unroll
+                        for (int i = 0; i < 18; ++i) {
+                            const float mine = h32 ? q[18 + i] : q[i], give = h32 ? q[i] : q[18 + i];
+                            k1[i] = mine + __shfl_xor(give, 32);
+                        }
+#pragma unroll
+                        for (int i = 0; i < 9; ++i) {
+                            const float mine = h16 ? k1[9 + i] : k1[i], give = h16 ? k1[i] : k1[9 + i];
+                            k2[i] = mine + __shfl_xor(give, 16);
+                        }
+                        float* const xd = flx + (g2 * 4 + wv) * FL_BLK + tc * FL_PATCH + 9 * (lane >> 4);
+#pragma unroll
+                        for (int i = 0; i < 9; ++i) xd[i] = k2[i];
+                    }
+                }
+            }
+        }
+        if constexpr (FL) {
+            // the four waves' patches of every block, summed in wave order; one region's NG x 16 patches are contiguous
+            // per block row of `part` ([B][H/4][W/4][36])
+            __syncthreads();
+            float* const pb = part + (((size_t)b * (H / 4) + ty0 / 4) * (size_t)(W / 4) + tx0 / 4) * FL_PATCH;
+            for (int e = tid; e < NG * FL_BLK; e += 256) {
+                const int g2 = e >= FL_BLK ? 1 : 0, rem = e - g2 * FL_BLK;
+                const float* xs = flx + g2 * 4 * FL_BLK + rem;
+                pb[(size_t)g2 * (W / 4) * FL_PATCH + rem] = ((xs[0] + xs[FL_BLK]) + xs[2 * FL_BLK]) + xs[3 * FL_BLK];
             }
         }
         asm volatile("; W44_EPILOGUE_END" ::: "memory");
@@ -557,24 +630,28 @@ void wino44_pack_weights(const float* w_mid, int n_mid, float* out) {
 }
 
 int wino44_layer(const float* in, float* out, const float* upack_layer, const float* bias, const float* zeros, int H, int W,
-                 int batch, int num_cu, float slope, hipStream_t s, int force) {
+                 int batch, int num_cu, float slope, hipStream_t s, int force, const float* wlast, float* part) {
     // 8 x 64 regions (72 accumulator quads per wave) in full waves of one region per CU; what is left -- a launch smaller than
     // the chip, or the last, partly filled wave -- goes through the 4 x 64 form, twice as many regions of half the work (one
     // 256 x 256 image: 256 regions instead of 128; three images: 256 + 256 instead of 384 in two waves).  Same bits either way.
     // force = 1 / 2 (test hook pnp_dncnn_debug_mid_layer only) takes one form for the whole layer.
+    // part != nullptr: the fused last layer (ReLU only): `out` is not written, the output patches go to `part` (wino44.h).
+    PNP_CHECK_ARG(part == nullptr || (slope == 0.f && wlast != nullptr), "the fused last layer needs ReLU and w_last");
     const int units = batch * (H / 8) * (W / w44::TC);
     int full = force == 1 ? 0 : force == 2 ? units : (units / num_cu) * num_cu;              // units done as 8 x 64 regions
     if (force == 0 && 2 * (units - full) > num_cu) full = units;      // (more than half a wave left: one more 8 x 64 wave is cheaper than two 4 x 64 waves)
     const float4* up = (const float4*)upack_layer;
     if (full > 0) {
         const int grid = full < num_cu ? full : num_cu;
-        if (slope != 0.f) w44::k_mid_wino44<true, 2><<<grid, 256, 0, s>>>(in, out, up, bias, H, W, full, slope, nullptr, 0);
+        if (part) w44::k_mid_wino44<false, 2, false, 0, true><<<grid, 256, 0, s>>>(in, out, up, bias, H, W, full, 0.f, nullptr, 0, wlast, part);
+        else if (slope != 0.f) w44::k_mid_wino44<true, 2><<<grid, 256, 0, s>>>(in, out, up, bias, H, W, full, slope, nullptr, 0);
         else w44::k_mid_wino44<false, 2><<<grid, 256, 0, s>>>(in, out, up, bias, H, W, full, 0.f, nullptr, 0);
         PNP_CHECK_LAUNCH();
     }
     if (full < units) {
         const int n1 = 2 * (units - full), grid = n1 < num_cu ? n1 : num_cu;
-        if (slope != 0.f) w44::k_mid_wino44<true, 1><<<grid, 256, 0, s>>>(in, out, up, bias, H, W, n1, slope, nullptr, full);
+        if (part) w44::k_mid_wino44<false, 1, false, 0, true><<<grid, 256, 0, s>>>(in, out, up, bias, H, W, n1, 0.f, nullptr, full, wlast, part);
+        else if (slope != 0.f) w44::k_mid_wino44<true, 1><<<grid, 256, 0, s>>>(in, out, up, bias, H, W, n1, slope, nullptr, full);
         else w44::k_mid_wino44<false, 1><<<grid, 256, 0, s>>>(in, out, up, bias, H, W, n1, 0.f, nullptr, full);
         PNP_CHECK_LAUNCH();
     }

@@ -243,6 +243,14 @@ class DncnnPlan:
         N.call('pnp_dncnn_debug_mid_layer', self._h, int(layer), _p(x), _p(out), _p(w44), int(rows), _stream())
         return out
 
+    def debug_fused_last(self, x, part, rows=0):
+        """the last middle layer with the output conv fused in, on caller-provided buffers (test hook): x [B,64,H,W] ->
+        part [B,H/4,W/4,6,6], the output partials of every 4 x 4 block (pixel (4 by + py - 1, 4 bx + px - 1))"""
+        assert x.dtype == torch.float32 and tuple(x.shape) == (self.B, 64, self.H, self.W)
+        assert part.dtype == torch.float32 and part.numel() == self.B * (self.H // 4) * (self.W // 4) * 36
+        N.call('pnp_dncnn_debug_fused_last', self._h, _p(x), _p(part), int(rows), _stream())
+        return part
+
     def forward(self, x, out=None):
         """raw network residual; x: float32 [B,H,W]."""
         assert x.dtype == torch.float32 and tuple(x.shape) == (self.B, self.H, self.W)

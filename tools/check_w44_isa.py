@@ -26,13 +26,16 @@ def check(asm_text):
     """Per kernel instantiation (also (c): m0 is used by the LDS-DMA statements only): (a) exactly 72 (36 for the one-block-row form) accumulator quads, each the destination of exactly 16 MFMAs (an accumulator
     that was moved shows up as extra quads with fewer); (b) outside the epilogue no instruction other than an MFMA names an
     accumulator AGPR (the 8 VGPR quads of the two-row form are legitimately reused between tiles, (a) covers them)."""
-    problems, kernels = [], 0
+    problems, kernels, checked = [], 0, []
     blocks = re.split(r'\n(?=_ZN3pnp3w4412k_mid_wino44[^\n]*:\s)', asm_text)
     for blk in blocks[1:]:
         name = blk.split(':', 1)[0]
-        m = re.search(r'ILb[01]ELi([12])ELb0ELi0EEEv', name)       # <LEAKY, NG, STAMP = false, VAR = 0>: stamped / ablation builds are not checked
+        # <LEAKY, NG, STAMP = false, VAR = 0, FL>: the production builds, the fused-last-layer ones included; stamped / ablation
+        # builds are not checked
+        m = re.search(r'ILb[01]ELi([12])ELb0ELi0ELb[01]EEEv', name)
         if not m:
             continue
+        checked.append(name)
         nq = 36 * int(m.group(1))
         lines = blk.split('\n')
         end = next((i for i, l in enumerate(lines) if l.startswith('.Lfunc_end')), len(lines))
@@ -69,7 +72,7 @@ def check(asm_text):
         dma = [l for l in lines if 'buffer_load_dwordx4' in l and ' lds' in l]
         if len(m0) != len(dma) or any('s_mov_b32 m0' not in l for l in m0):
             problems.append(f'{name}: {len(m0)} uses of m0 for {len(dma)} LDS-DMA instructions (the compiler touches m0?)')
-    return kernels, problems
+    return kernels, problems, checked
 
 
 def main():
@@ -82,8 +85,10 @@ def main():
                             '-pragma-unroll-threshold=200000', '-fno-slp-vectorize', '-x', 'hip', '--cuda-device-only', '-S', SRC, '-o', out],
                            check=True, stderr=subprocess.DEVNULL)
             text = open(out).read()
-    kernels, problems = check(text)
+    kernels, problems, checked = check(text)
     print(f'{kernels} kernel instantiation(s) checked, {len(problems)} problem(s)')
+    for name in checked:
+        print('  checked: ' + name)
     for p in problems[:40]:
         print('  ' + p)
     return 1 if problems or kernels == 0 else 0
