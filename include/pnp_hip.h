@@ -246,7 +246,8 @@ int pnp_dncnn_set_affine(pnp_dncnn_plan* plan, const float* b_first, float b_las
  *       not the reference's arithmetic operation for operation, and at present SLOWER than 5; H % 8 == 0,
  *       W % 64 == 0.
  * The default comes from the environment variable PNP_DNCNN_WINOGRAD at plan creation (6 as above; unset or any other value = 5,
- * falling back to 1 where the image size does not allow it).                                                          */
+ * falling back to 1 where the image size does not allow it).  This call rejects any other mode, and 5 / 6 where the image
+ * size does not allow them, with PNP_ERR_ARG.                                                                          */
 int pnp_dncnn_set_winograd(pnp_dncnn_plan* plan, int enable);
 /* raw network: r = net(x), x and r [batch][H][W] fp32 (the predicted noise residual)          */
 int pnp_dncnn_forward(pnp_dncnn_plan* plan, const float* x, float* r, void* stream);
@@ -274,7 +275,8 @@ int pnp_dncnn_debug_clock(pnp_dncnn_plan* plan, int reps, double* cycles, double
  * CALLER-provided activation buffers in/out [batch][64][H][W] fp32 -- so that a test can put guard bands around them
  * (tests/test_gpu_dncnn.py::test_wino44_guard_bands).  w44_override (may be NULL; mode 5 only): packed F(4x4,3x3) weights of
  * the layer in the caller's memory, pnp_dncnn_debug_w44_floats() floats as pnp_dncnn_debug_w44_weights copies them out.
- * w44_rows: 0 = the production choice of region form, 1 / 2 = 4 x 64 / 8 x 64 regions for the whole layer (mode 5 only).        */
+ * w44_rows: 0 = the production choice of region form, 1 / 2 = 4 x 64 / 8 x 64 regions for the whole layer (mode 5 only).
+ * pnp_dncnn_debug_w44_weights fails with PNP_ERR_ARG on a plan whose image size rules mode 5 out (no such weights).           */
 size_t pnp_dncnn_debug_w44_floats(void);
 int pnp_dncnn_debug_w44_weights(pnp_dncnn_plan* plan, int layer, float* dst, void* stream);
 int pnp_dncnn_debug_mid_layer(pnp_dncnn_plan* plan, int layer, const float* in, float* out, const float* w44_override,

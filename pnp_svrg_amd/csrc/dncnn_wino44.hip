@@ -604,13 +604,14 @@ __global__ __launch_bounds__(256, 1) void k_mid_wino44(const float* __restrict__
 
 bool wino44_supports(int H, int W) { return H % 8 == 0 && W % w44::TC == 0; }
 
-size_t wino44_weight_floats(int n_mid) { return (size_t)n_mid * 4 * w44::NCH * 18 * 64 * 4; }
+size_t wino44_layer_bytes() { return (size_t)4 * w44::NCH * 18 * 64 * 4 * sizeof(float); }
 
 // w_mid [n_mid][64][64][3][3] (BN folded) -> upack[l][wv][chunk k][xi pair p][lane][e]:  xi = 2 p + (e >> 1), k-step j = e & 1,
 // U_xi[cout = 16 wv + (lane & 15)][cin = 8 k + 2 (lane >> 4) + j],  U = G g G^T,  xi = 6 xi_y + xi_x
-void wino44_pack_weights(const float* w_mid, int n_mid, float* out) {
+void wino44_pack(const float* w_mid, int n_mid, void* out_) {
     static const double G[6][3] = {{1.0 / 4, 0, 0}, {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
                                    {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6}, {0, 0, 1}};
+    float* out = (float*)out_;
     for (int l = 0; l < n_mid; ++l)
         for (int wv = 0; wv < 4; ++wv)
             for (int k = 0; k < w44::NCH; ++k)
@@ -629,18 +630,22 @@ void wino44_pack_weights(const float* w_mid, int n_mid, float* out) {
                     }
 }
 
-int wino44_layer(const float* in, float* out, const float* upack_layer, const float* bias, const float* zeros, int H, int W,
-                 int batch, int num_cu, float slope, hipStream_t s, int force, const float* wlast, float* part) {
+int wino44_layer(const ConvLayerArgs& a) {
     // 8 x 64 regions (72 accumulator quads per wave) in full waves of one region per CU; what is left -- a launch smaller than
     // the chip, or the last, partly filled wave -- goes through the 4 x 64 form, twice as many regions of half the work (one
     // 256 x 256 image: 256 regions instead of 128; three images: 256 + 256 instead of 384 in two waves).  Same bits either way.
     // force = 1 / 2 (test hook pnp_dncnn_debug_mid_layer only) takes one form for the whole layer.
     // part != nullptr: the fused last layer (ReLU only): `out` is not written, the output patches go to `part` (wino44.h).
-    PNP_CHECK_ARG(part == nullptr || (slope == 0.f && wlast != nullptr), "the fused last layer needs ReLU and w_last");
+    PNP_CHECK_ARG(a.part == nullptr || (a.slope == 0.f && a.wlast != nullptr), "the fused last layer needs ReLU and w_last");
+    const float *in = a.in, *bias = a.bias, *wlast = a.wlast;
+    float *out = a.out, *part = a.part;
+    const int H = a.H, W = a.W, num_cu = a.num_cu, force = a.force_rows, batch = a.batch;
+    const float slope = a.slope;
+    const hipStream_t s = a.s;
     const int units = batch * (H / 8) * (W / w44::TC);
     int full = force == 1 ? 0 : force == 2 ? units : (units / num_cu) * num_cu;              // units done as 8 x 64 regions
     if (force == 0 && 2 * (units - full) > num_cu) full = units;      // (more than half a wave left: one more 8 x 64 wave is cheaper than two 4 x 64 waves)
-    const float4* up = (const float4*)upack_layer;
+    const float4* up = (const float4*)(a.w44_override ? a.w44_override : (const float*)a.w + a.layer * wino44_layer_bytes() / sizeof(float));
     if (full > 0) {
         const int grid = full < num_cu ? full : num_cu;
         if (part) w44::k_mid_wino44<false, 2, false, 0, true><<<grid, 256, 0, s>>>(in, out, up, bias, H, W, full, 0.f, nullptr, 0, wlast, part);
@@ -658,24 +663,38 @@ int wino44_layer(const float* in, float* out, const float* upack_layer, const fl
     return PNP_OK;
 }
 
-// diagnostic: `reps` back-to-back launches, the last one stamped; per workgroup {shader cycles, 100 MHz ticks, cycles in the
-// chunk-end waits + barriers, cycles in the epilogue} of the tile loop
-int wino44_debug_clock(const float* in, float* out, const float* upack_layer, const float* bias, int H, int W, int batch,
-                       int num_cu, int reps, unsigned long long* stamps_dev, hipStream_t s) {
-    const int ntiles = batch * (H / 8) * (W / w44::TC);
-    const int grid = ntiles < num_cu ? ntiles : num_cu;
-    for (int i = 0; i < reps - 1; ++i)
-        w44::k_mid_wino44<false, 2><<<grid, 256, 0, s>>>(in, out, (const float4*)upack_layer, bias, H, W, ntiles, 0.f);
-    const int var = getenv("PNP_W44_VAR") ? atoi(getenv("PNP_W44_VAR")) : 0;
-    if (var == 0) w44::k_mid_wino44<false, 2, true><<<grid, 256, 0, s>>>(in, out, (const float4*)upack_layer, bias, H, W, ntiles, 0.f, stamps_dev);
+// per workgroup {shader cycles, 100 MHz ticks, cycles in the chunk-end waits + barriers, cycles in the epilogue} of the tile loop
+int wino44_debug_clock(const ConvLayerArgs& a, int reps, std::vector<double>& cycles, std::vector<double>& ticks) {
+    const int ntiles = a.batch * (a.H / 8) * (a.W / w44::TC);
+    const int grid = ntiles < a.num_cu ? ntiles : a.num_cu;
+    const float *in = a.in, *bias = a.bias;
+    float* out = a.out;
+    const int H = a.H, W = a.W;
+    const hipStream_t s = a.s;
+    const float* upack_layer = (const float*)a.w + a.layer * wino44_layer_bytes() / sizeof(float);
+    std::vector<unsigned long long> h;
+    const int rc = read_stamps(s, grid, 4, [&](unsigned long long* stamps_dev) {
+        for (int i = 0; i < reps - 1; ++i)
+            w44::k_mid_wino44<false, 2><<<grid, 256, 0, s>>>(in, out, (const float4*)upack_layer, bias, H, W, ntiles, 0.f);
+        const int var = getenv("PNP_W44_VAR") ? atoi(getenv("PNP_W44_VAR")) : 0;
+        if (var == 0) w44::k_mid_wino44<false, 2, true><<<grid, 256, 0, s>>>(in, out, (const float4*)upack_layer, bias, H, W, ntiles, 0.f, stamps_dev);
 #ifdef PNP_W44_ABLATIONS   // timing-only builds (wrong results): 10 = no transform
                            // arithmetic, 11 = no DMA, 12 = no weight reloads, 13 = no B reads, 14 = no transform LDS traffic, 15 = bare MFMAs
 #define PNP_W44_ABL(V) else if (var == V) w44::k_mid_wino44<false, 2, true, V><<<grid, 256, 0, s>>>(in, out, (const float4*)upack_layer, bias, H, W, ntiles, 0.f, stamps_dev);
-    PNP_W44_ABL(10) PNP_W44_ABL(11) PNP_W44_ABL(12) PNP_W44_ABL(13) PNP_W44_ABL(14) PNP_W44_ABL(15)
+        PNP_W44_ABL(10) PNP_W44_ABL(11) PNP_W44_ABL(12) PNP_W44_ABL(13) PNP_W44_ABL(14) PNP_W44_ABL(15)
 #undef PNP_W44_ABL
 #endif
-    else PNP_CHECK_ARG(false, "PNP_W44_VAR: this library was built without -DPNP_W44_ABLATIONS");
-    PNP_CHECK_LAUNCH();
+        else PNP_CHECK_ARG(false, "PNP_W44_VAR: this library was built without -DPNP_W44_ABLATIONS");
+        PNP_CHECK_LAUNCH();
+        return PNP_OK;
+    }, h, cycles, ticks);
+    if (rc != PNP_OK) return rc;
+    if (getenv("PNP_DEBUG_STAMPS")) {
+        double wsum = 0, esum = 0, rsum = 0;
+        for (int i = 0; i < grid; ++i) { wsum += (double)(h[4 * i + 2] & 0xFFFFFFFFull); rsum += (double)(h[4 * i + 2] >> 32); esum += h[4 * i + 3]; }
+        fprintf(stderr, "[k_mid_wino44 stamps] mean cycles per WG: chunk-end wait + barrier %.0f  epilogue %.0f  (mode 6: steps 0..5 of the chunks %.0f)\n",
+                wsum / grid, esum / grid, rsum / grid);
+    }
     return PNP_OK;
 }
 

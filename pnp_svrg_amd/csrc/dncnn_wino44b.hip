@@ -156,7 +156,7 @@ __device__ __forceinline__ void bt6_pk(f32x2 q0, f32x2 q1, f32x2 q2, f32x2 q3, f
 // 16 further (the same block, the next channel): the even row ends up with both channels of point XI, the odd row with both
 // channels of point XI + 18, and every term is ONE 4-byte store per lane.  `vdst` carries the row's part of the address: the odd
 // row's 18 points further and two dwords rotated inside the 16-byte item -- points 18..35 hold their channels in the order
-// 4..7, 0..3 (wino44b_pack_weights packs the weights of the waves that own those points the same way), which puts the two rows of
+// 4..7, 0..3 (wino44b_pack packs the weights of the waves that own those points the same way), which puts the two rows of
 // a store on different banks.
 typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
 template <int XI> __device__ __forceinline__ void put_pair(lds_c* vdst, float P, float Q) {
@@ -563,12 +563,13 @@ __global__ __launch_bounds__(256, 1) void k_mid_wino44b(const float* __restrict_
 
 bool wino44b_supports(int H, int W) { return H % 8 == 0 && W % w44b::TC == 0; }
 
-size_t wino44b_weight_halfwords(int n_mid) { return (size_t)n_mid * 4 * w44b::NLOADS * 64 * 8; }
+size_t wino44b_layer_bytes() { return (size_t)4 * w44b::NLOADS * 64 * 8 * sizeof(uint16_t); }
 
 // w_mid [n_mid][64][64][3][3] (BN folded) -> upack[l][wave][chunk k][point t][operand ab][lane][8 channels] (bf16 bit patterns):
 // wave = 2 xh + ch, point xi = 18 xh + t, cout = 32 ch + (lane & 31), cin = 8 k + ((e + 4 xh) & 7); operand 0 = (a1 | a2), 1 = (a3 | a1) by
 // half-wave (lane >> 5), with U = G g G^T evaluated in float64, rounded to fp32 (the fp32 kernel's value) and split by truncation
-void wino44b_pack_weights(const float* w_mid, int n_mid, uint16_t* out) {
+void wino44b_pack(const float* w_mid, int n_mid, void* out_) {
+    uint16_t* out = (uint16_t*)out_;
     static const double G[6][3] = {{1.0 / 4, 0, 0}, {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
                                    {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6}, {0, 0, 1}};
     auto bits = [](float f) { uint32_t u; memcpy(&u, &f, 4); return u; };
@@ -600,34 +601,53 @@ void wino44b_pack_weights(const float* w_mid, int n_mid, uint16_t* out) {
             }
 }
 
-int wino44b_layer(const float* in, float* out, const uint16_t* upack_layer, const float* bias, int H, int W, int batch, int num_cu,
-                  float slope, hipStream_t s) {
-    const int units = batch * (H / 8) * (W / w44b::TC);
-    const int grid = units < num_cu ? units : num_cu;
-    const uint4* up = (const uint4*)upack_layer;
-    if (slope != 0.f) w44b::k_mid_wino44b<true><<<grid, 256, 0, s>>>(in, out, up, bias, H, W, units, slope, nullptr);
-    else w44b::k_mid_wino44b<false><<<grid, 256, 0, s>>>(in, out, up, bias, H, W, units, 0.f, nullptr);
+static const uint4* layer_weights(const ConvLayerArgs& a) {
+    return (const uint4*)((const char*)a.w + a.layer * wino44b_layer_bytes());
+}
+
+int wino44b_layer(const ConvLayerArgs& a) {
+    if (const int rc = check_plain_conv(a)) return rc;
+    const int units = a.batch * (a.H / 8) * (a.W / w44b::TC);
+    const int grid = units < a.num_cu ? units : a.num_cu;
+    const uint4* up = layer_weights(a);
+    if (a.slope != 0.f) w44b::k_mid_wino44b<true><<<grid, 256, 0, a.s>>>(a.in, a.out, up, a.bias, a.H, a.W, units, a.slope, nullptr);
+    else w44b::k_mid_wino44b<false><<<grid, 256, 0, a.s>>>(a.in, a.out, up, a.bias, a.H, a.W, units, 0.f, nullptr);
     PNP_CHECK_LAUNCH();
     return PNP_OK;
 }
 
-// diagnostic: `reps` back-to-back launches, the last one stamped; per workgroup {shader cycles, 100 MHz ticks, cycles in the
-// chunk-end waits + barriers, cycles in the epilogue}
-int wino44b_debug_clock(const float* in, float* out, const uint16_t* upack_layer, const float* bias, int H, int W, int batch,
-                        int num_cu, int reps, unsigned long long* stamps_dev, hipStream_t s) {
-    const int ntiles = batch * (H / 8) * (W / w44b::TC);
-    const int grid = ntiles < num_cu ? ntiles : num_cu;
-    for (int i = 0; i < reps - 1; ++i)
-        w44b::k_mid_wino44b<false><<<grid, 256, 0, s>>>(in, out, (const uint4*)upack_layer, bias, H, W, ntiles, 0.f, nullptr);
-    const int var = getenv("PNP_W44_VAR") ? atoi(getenv("PNP_W44_VAR")) : 0;
-    if (var == 0) w44b::k_mid_wino44b<false, true><<<grid, 256, 0, s>>>(in, out, (const uint4*)upack_layer, bias, H, W, ntiles, 0.f, stamps_dev);
+// per workgroup {shader cycles, 100 MHz ticks, cycles in the chunk-end waits + barriers (+ those of steps 0..5 of the chunks
+// << 32), cycles in the epilogue}
+int wino44b_debug_clock(const ConvLayerArgs& a, int reps, std::vector<double>& cycles, std::vector<double>& ticks) {
+    const int ntiles = a.batch * (a.H / 8) * (a.W / w44b::TC);
+    const int grid = ntiles < a.num_cu ? ntiles : a.num_cu;
+    const float *in = a.in, *bias = a.bias;
+    float* out = a.out;
+    const int H = a.H, W = a.W;
+    const hipStream_t s = a.s;
+    const uint4* up = layer_weights(a);
+    std::vector<unsigned long long> h;
+    const int rc = read_stamps(s, grid, 4, [&](unsigned long long* stamps_dev) {
+        for (int i = 0; i < reps - 1; ++i)
+            w44b::k_mid_wino44b<false><<<grid, 256, 0, s>>>(in, out, up, bias, H, W, ntiles, 0.f, nullptr);
+        const int var = getenv("PNP_W44_VAR") ? atoi(getenv("PNP_W44_VAR")) : 0;
+        if (var == 0) w44b::k_mid_wino44b<false, true><<<grid, 256, 0, s>>>(in, out, up, bias, H, W, ntiles, 0.f, stamps_dev);
 #ifdef PNP_W44_ABLATIONS   // timing-only builds (wrong results)
-#define PNP_W44_ABL(V) else if (var == V) w44b::k_mid_wino44b<false, true, V><<<grid, 256, 0, s>>>(in, out, (const uint4*)upack_layer, bias, H, W, ntiles, 0.f, stamps_dev);
-    PNP_W44_ABL(10) PNP_W44_ABL(11) PNP_W44_ABL(12) PNP_W44_ABL(13) PNP_W44_ABL(14) PNP_W44_ABL(15) PNP_W44_ABL(16)
+#define PNP_W44_ABL(V) else if (var == V) w44b::k_mid_wino44b<false, true, V><<<grid, 256, 0, s>>>(in, out, up, bias, H, W, ntiles, 0.f, stamps_dev);
+        PNP_W44_ABL(10) PNP_W44_ABL(11) PNP_W44_ABL(12) PNP_W44_ABL(13) PNP_W44_ABL(14) PNP_W44_ABL(15) PNP_W44_ABL(16)
 #undef PNP_W44_ABL
 #endif
-    else PNP_CHECK_ARG(false, "PNP_W44_VAR: this library was built without -DPNP_W44_ABLATIONS");
-    PNP_CHECK_LAUNCH();
+        else PNP_CHECK_ARG(false, "PNP_W44_VAR: this library was built without -DPNP_W44_ABLATIONS");
+        PNP_CHECK_LAUNCH();
+        return PNP_OK;
+    }, h, cycles, ticks);
+    if (rc != PNP_OK) return rc;
+    if (getenv("PNP_DEBUG_STAMPS")) {
+        double wsum = 0, esum = 0, rsum = 0;
+        for (int i = 0; i < grid; ++i) { wsum += (double)(h[4 * i + 2] & 0xFFFFFFFFull); rsum += (double)(h[4 * i + 2] >> 32); esum += h[4 * i + 3]; }
+        fprintf(stderr, "[k_mid_wino44 stamps] mean cycles per WG: chunk-end wait + barrier %.0f  epilogue %.0f  (mode 6: steps 0..5 of the chunks %.0f)\n",
+                wsum / grid, esum / grid, rsum / grid);
+    }
     return PNP_OK;
 }
 

@@ -120,6 +120,8 @@ def test_wino44_shapes_and_edges():
     assert np.array_equal(rd, ops.DncnnPlan(w, 40, 96, 1, winograd=1).forward(dev(x96)).cpu().numpy())
     with pytest.raises(Exception):
         ops.DncnnPlan(w, 40, 96, 1, winograd=5)
+    with pytest.raises(Exception):                                      # no F(4x4,3x3) weights are packed for such a plan
+        ops.DncnnPlan(w, 40, 96, 1).debug_w44_weights(0)
 
 
 def test_wino44_run_to_run_identical(W15):
