@@ -231,6 +231,49 @@ def dncnn_forward(weights, x):
     return t[0, 0].numpy()
 
 
+def conv_layer64(x, w, b=None, slope=None):
+    """One 3x3 'same' conv (zero padding) in float64 on torch CPU: x [B, cin, H, W] or [cin, H, W], w [cout, cin, 3, 3],
+    optional bias b [cout]; slope None = no activation, 0 = ReLU, > 0 = LeakyReLU(slope).  Returns a float64 tensor."""
+    import torch
+    import torch.nn.functional as F
+    t = torch.as_tensor(np.asarray(x, dtype=np.float64)) if not torch.is_tensor(x) else x.double()
+    squeeze = t.dim() == 3
+    if squeeze:
+        t = t[None]
+    wt = torch.as_tensor(np.asarray(w, dtype=np.float64))
+    bt = None if b is None else torch.as_tensor(np.asarray(b, dtype=np.float64).reshape(-1))
+    with torch.no_grad():
+        t = F.conv2d(t, wt, bt, padding=1)
+        if slope is not None:
+            t = F.leaky_relu(t, float(slope)) if slope else F.relu(t)
+    return t[0] if squeeze else t
+
+
+def dncnn_forward64(weights, x):
+    """The conv / BN(eval) / activation stack of `dncnn_forward` and `mmo_forward` (without the skip) in float64, from
+    the weight dict as it is: BatchNorm applied unfolded after its conv, optional conv{i}.bias, `negative_slope`
+    (LeakyReLU instead of ReLU) and `transpose_taps` (every 3x3 kernel transposed), read the way ops.DncnnPlan reads
+    them.  x: (H, W) or (B, H, W).  Returns the network output (the residual) in float64, same leading shape."""
+    import torch
+    n_layers = int(weights['n_layers'])
+    slope = float(weights.get('negative_slope', 0.0))
+    tr = bool(weights.get('transpose_taps', False))
+    x = np.asarray(x, dtype=np.float64)
+    t = torch.from_numpy(x.reshape((-1, 1) + x.shape[-2:]))
+    for i in range(n_layers):
+        w = np.asarray(weights[f'conv{i}.weight'], dtype=np.float64)
+        if tr:
+            w = w.swapaxes(-1, -2)
+        t = conv_layer64(t, w, weights.get(f'conv{i}.bias'))
+        if f'bn{i}.weight' in weights:
+            g, beta, mu, var = (torch.from_numpy(np.asarray(weights[f'bn{i}.{k}'], np.float64))[None, :, None, None]
+                                for k in ('weight', 'bias', 'mean', 'var'))
+            t = (t - mu) / torch.sqrt(var + 1e-5) * g + beta
+        if i < n_layers - 1:
+            t = torch.nn.functional.leaky_relu(t, slope) if slope else torch.relu(t)
+    return t[:, 0].numpy().reshape(x.shape)
+
+
 class DnCNNDenoiser:
     """reference denoisers/RealSN_DnCNN.py:16-42 around `dncnn_forward`."""
 

@@ -89,8 +89,10 @@ def test_winograd_vs_direct(W15, io):
     assert np.abs(r5 - io['net256_out']).max() <= 2e-5
     print('max |conv kernel - reference net|: F(4x4,3x3) %.2e  F(2,3) %.2e  direct %.2e' % (
         np.abs(r5 - io['net256_out']).max(), np.abs(rw - io['net256_out']).max(), np.abs(rd - io['net256_out']).max()))
-    # several tiles per persistent workgroup in the XCD-aware order (tilewalk.h), and a count that does not divide
-    # (plain walk): every image of a batch must equal its single-image result, for all conv kernels
+    # several tiles per persistent workgroup in the XCD-aware order (tilewalk.h): every image of a batch must equal its
+    # single-image result, for all conv kernels.  On a 256-CU part both batches take the XCD walk in every form (mode 5 at
+    # B = 5: two 8 x 64 waves, then the last 128 units as one wave of 4 x 64 regions); the plain walk and partial waves are
+    # in test_gpu_dncnn_geometry.py
     rng = np.random.default_rng(5)
     for B in (6, 5):
         xb = rng.random((B, 256, 256)).astype(np.float32)
@@ -127,7 +129,8 @@ def test_wino44_shapes_and_edges():
 def test_wino44_run_to_run_identical(W15):
     """Repeated forward passes through the F(4x4,3x3) layers are bit-identical, with HBM traffic from a second stream under
     half of them (a stale accumulator copy, a missed DMA wait or an LDS race would differ from run to run); both region
-    forms (1 image: 4 x 64 regions, 7 images: 8 x 64) and region counts that do not fill the last wave of workgroups."""
+    forms (1 image: 4 x 64 regions; 7 images on a 256-CU part: three full waves of 8 x 64 regions, then the last 128 units as
+    exactly one wave of 4 x 64 regions)."""
     from pnp_svrg_amd import ops
     side = torch.cuda.Stream()
     junk = torch.empty(32 * 1024 * 1024, device='cuda')

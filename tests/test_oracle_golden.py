@@ -295,6 +295,35 @@ def test_mmo_oracle():
     assert den.t == 2
 
 
+def test_dncnn_forward64():
+    """oracle.dncnn_forward64 (float64, BatchNorm unfolded; the float64 yardstick of the GPU conv geometry tests) against
+    the reference network's float32 output on its sigma = 15 weights, and against `mmo_forward` (biases, LeakyReLU) plus
+    its skip.  Measured here: 1.1e-7 (64^2) / 1.8e-7 (256^2) against `net*_out` (|out| <= 0.21), 2.1e-7 / 2.8e-7 against
+    `mmo_forward` (|out| <= 1.01) -- the float32 rounding of the reference's own runs.  `transpose_taps` on an image is
+    the plain net on its transpose (to float64 rounding)."""
+    w = dict(golden('dncnn_noise15.npz'))
+    io = golden('dncnn_io.npz')
+    for n in (64, 256):
+        np.testing.assert_allclose(od.dncnn_forward64(w, io[f'net{n}_in']), io[f'net{n}_out'], rtol=0, atol=1e-6)
+    xb = np.stack([io['net64_in'], io['net64_in'].T])                  # a batch is the images one by one
+    rb = od.dncnn_forward64(w, xb)
+    assert rb.shape == xb.shape and rb.dtype == np.float64
+    np.testing.assert_allclose(rb[1], od.dncnn_forward64(w, xb[1]), rtol=0, atol=1e-15)
+    g = golden('mmo_seeded.npz')
+    wm = {k: g[k] for k in g.files if k.startswith('conv') or k in ('n_layers', 'negative_slope')}
+    for name in ('sq', 'rect'):
+        x = np.clip(g[f'{name}_in'].T.astype(np.float32), 0.0, 1.0)
+        r64 = od.dncnn_forward64(wm, x)
+        np.testing.assert_allclose(r64 + x, od.mmo_forward(wm, x), rtol=0, atol=1e-6)
+        rt = od.dncnn_forward64(dict(wm, transpose_taps=True), x.T.copy())
+        np.testing.assert_allclose(rt.T, r64, rtol=0, atol=1e-12)
+        # one layer: conv_layer64 with LeakyReLU keeps the negative part scaled by the slope
+        c0 = od.conv_layer64(x[None], wm['conv0.weight'], wm['conv0.bias'], float(wm['negative_slope'])).numpy()
+        lin = od.conv_layer64(x[None], wm['conv0.weight'], wm['conv0.bias']).numpy()
+        assert c0.shape == (64,) + x.shape and (lin < 0).any()
+        np.testing.assert_array_equal(c0, np.where(lin > 0, lin, float(wm['negative_slope']) * lin))
+
+
 # ---------------------------------------------------------------------------------- round-2 fixtures (make_golden_r2.py)
 def _png(tmp_path, name, pixels):
     from PIL import Image
