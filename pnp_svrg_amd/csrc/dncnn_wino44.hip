@@ -11,8 +11,8 @@
 //     channels [16 wv, 16 wv + 16) and keeps ALL 36 x 2 accumulator quads (288 registers) for the region's 2 x 16 blocks;
 //   * input channels go by in chunks of 8: the chunk's (8+2) x 72 halo planes arrive by LDS-DMA, every thread transforms
 //     ONE (channel, block) patch -- the transform is shared by the four waves, i.e. by all 64 output channels -- and
-//     writes its 36 values to the V image [xi][row of blocks][k-row][block][k-step], from which a wave's B operands of
-//     one xi are a single conflict-free ds_read_b64 per block row;
+//     writes its 36 values to the V image [xi][k-row][block][row of blocks][k-step], from which a wave's B operands of
+//     one xi (both block rows) are a single conflict-free ds_read_b128 (one block row: ds_read_b64);
 //   * transformed weights do not fit registers (36 x 64 x 64): they stream from L2 in MFMA operand order, one 16-byte
 //     load per lane and xi pair and chunk through a ring of 18 loads in flight, each value used by two MFMAs (the two
 //     block rows);
@@ -44,7 +44,7 @@ template <int NG_> struct Geo {
     static constexpr int PLANE = NG == 2 ? 768 : 512;              // PR x 72 payload + pad: 0 mod 64 dwords (ds_read_b128 lane groups mix two planes)
     static constexpr int DBUF = KC * PLANE;                        // 24 / 16 DMA pieces of 1 KiB
     static constexpr int PPW = DBUF / 256 / 4;                     // 6 / 4 pieces per wave
-    static constexpr int VPL = 128 * NG;                           // floats per xi plane of V: [NG block rows][4 k-rows][16 blocks][2 k-steps]
+    static constexpr int VPL = 128 * NG;                           // floats per xi plane of V: [4 k-rows][16 blocks][NG block rows][2 k-steps]
     static constexpr int VBUF = 36 * VPL;
     static constexpr int LDS_FLOATS = 2 * DBUF + 2 * VBUF;         // 120 KiB / 68 KiB
     static constexpr int NQ_AGPR = NG == 2 ? 64 : 36;              // accumulator quads kept in AGPRs (of 72: block row 0 and xi < 28 of row 1; of 36: all)
@@ -122,8 +122,7 @@ template <int NG_> struct Ctx {
     f32x2 b[2][NG_];                                           // B operands of the current / next xi: [parity][block row]
     const lds_f* dsrc[2];                                      // this lane's patch in the two d buffers
     lds_f* vdst[2];                                            // its V item in the two V buffers
-    const lds_f* vsrc0[2];                                     // its B operands (block row 0 / 1) in the two V buffers;
-    const lds_f* vsrc1[2];                                     //   separate, laundered bases: no ds_read2st64_b64 merging
+    const lds_f* vsrc0[2];                                     // its B operands (both block rows: 16 bytes) in the two V buffers
     // weight stream of this wave: a scalar cursor (1 KiB per load; advanced on the scalar ALU, re-defined through an empty asm so
     // that it stays ONE register pair instead of 144 hoisted addresses) + the lane's 16 bytes as a 32-bit vector offset
     const __attribute__((address_space(1))) char* ucur;
@@ -135,10 +134,19 @@ template <int NG_> struct Ctx {
         return u;
     }
 };
-// One LDS read beside an f32 MFMA is free, two in the same gap cost about an MFMA (tools/microbench/mfma_f32_fillers.hip),
-// and vector-ALU work is cheapest in blocks; so a step (two xi = 8 MFMAs) has fixed slots, pinned by sched_barriers:
-//     M1 | B(xi1)[0] | M2 | B(xi1)[1] | M3 | VALU block of transform slice p | M4 | slice LDS op 1 |
-//     M5 | B(xi0')[0] | M6 | B(xi0')[1] | M7 | DMA piece p, slice LDS op 2 | M8 | slice LDS op 3, ring reload
+// One memory instruction beside an f32 MFMA is free, two per gap kept up cost up to an MFMA (tools/microbench/
+// mfma_f32_fillers.hip; an isolated pair costs far less: DESIGN 3.1), and vector-ALU work is cheapest in blocks; so a step (two xi = 8 MFMAs) has fixed slots, pinned by
+// sched_barriers.  Two block rows (step2): every memory instruction of a chunk has a gap of its own and the vector-ALU
+// blocks stand alone (tools/check_w44_gaps.py, tests/test_cpu_w44_gaps.py hold the generated code to it) --
+//     M1 | B(xi1) | M2 | a | M3 | VALU block | M4 | b | M5 | B(xi0') | M6 | c | M7 | d | M8 | ring reload
+//     step 0:          a, b = reads of patch row 0   (no VALU: reload of step 17)  d = DMA piece 0
+//     step p = 1..6:   a = DMA piece p (p < 6)   VALU = row transform p - 1        b, c = reads of patch row p (p < 6)
+//     step 7 / 9 / 11: VALU = column transform 0 / 1 / 2                           b, c, d = its V writes 0..2
+//     step 8 / 10 / 12: a, b, c = its V writes 3..5                                steps 13..17: B reads and reloads only
+// (the gap behind M8 of step 17 belongs to the B read of the next chunk's first xi, behind the barrier: that step's ring
+//  reload waits for the free VALU gap of the next chunk's step 0.)
+// One block row (step; half the gaps for nearly the same memory instructions: they share) --
+//     M1 | B(xi1) | M3 | VALU block of transform slice p, slice LDS op 1 | M5 | B(xi0') | M7 | DMA piece p, slice LDS ops 2, 3, ring reload
 #define PNP_SLOT() __builtin_amdgcn_sched_barrier(0)
 
 // patch row R of d buffer DPAR, in two halves; all ten floats are "used" (slice_valu) so that the reads stay one
@@ -200,24 +208,29 @@ template <int SL, typename CT> __device__ __forceinline__ void slice_valu(CT& c)
         bt6_pk(P.t[0][cp], P.t[1][cp], P.t[2][cp], P.t[3][cp], P.t[4][cp], P.t[5][cp], P.v);
     }
 }
+// pair Y (0..5) of the V writes of column slice SL: one ds_write2st64_b32
+template <int DPAR, int SL, int Y, typename CT> __device__ __forceinline__ void v_write(CT& c) {
+    constexpr int VPL = CT::G::VPL;
+    constexpr int cp = col_pair(SL), xa = cp == 0 ? 0 : cp == 1 ? 1 : 3, xb = cp == 0 ? 5 : cp == 1 ? 2 : 4;
+    c.vdst[DPAR][(Y * 6 + xa) * VPL] = c.P.v[Y].x;
+    c.vdst[DPAR][(Y * 6 + xb) * VPL] = c.P.v[Y].y;
+}
 // LDS operation N (0..2) of slice SL: the next patch row's reads (SL < 5) or two of the six pairs of V writes (column slices)
 template <int DPAR, int SL, int N, typename CT> __device__ __forceinline__ void slice_lds(CT& c) {
-    constexpr int VPL = CT::G::VPL;
     if constexpr (SL < 5) {
         if constexpr (N < 2) patch_load<DPAR, SL + 1, N>(c);
     } else if constexpr (is_col_slice(SL)) {
-        constexpr int cp = col_pair(SL), xa = cp == 0 ? 0 : cp == 1 ? 1 : 3, xb = cp == 0 ? 5 : cp == 1 ? 2 : 4;
-#pragma unroll
-        for (int y = 2 * N; y < 2 * N + 2; ++y) {
-            c.vdst[DPAR][(y * 6 + xa) * VPL] = c.P.v[y].x;
-            c.vdst[DPAR][(y * 6 + xb) * VPL] = c.P.v[y].y;
-        }
+        v_write<DPAR, SL, 2 * N>(c);
+        v_write<DPAR, SL, 2 * N + 1>(c);
     }
 }
-template <int VPAR, int XI, int GR, typename CT> __device__ __forceinline__ void b_load(CT& c) {
-    if constexpr (GR < CT::NG) {
-        if (GR == 0) c.b[XI & 1][0] = *(const lds_f2*)(c.vsrc0[VPAR] + XI * CT::G::VPL);
-        else c.b[XI & 1][GR] = *(const lds_f2*)(c.vsrc1[VPAR] + XI * CT::G::VPL);
+// B operands of xi: one ds_read_b64 (one block row) / one ds_read_b128 (both block rows)
+template <int VPAR, int XI, typename CT> __device__ __forceinline__ void b_load(CT& c) {
+    if constexpr (CT::NG == 1) c.b[XI & 1][0] = *(const lds_f2*)(c.vsrc0[VPAR] + XI * CT::G::VPL);
+    else {
+        const f32x4 q = *(const lds_f4*)(c.vsrc0[VPAR] + XI * CT::G::VPL);
+        c.b[XI & 1][0] = f32x2{q.x, q.y};
+        c.b[XI & 1][CT::NG - 1] = f32x2{q.z, q.w};
     }
 }
 // MFMA of block row GR (nothing for a block row the region does not have): first k-step of a xi (constant-zero SrcC in
@@ -232,68 +245,114 @@ template <int XI, int GR, typename CT> __device__ __forceinline__ void mfma_j1(C
     if constexpr (GR < CT::NG) mfma<CT::G::in_agpr(GR, XI)>(c.acc[GR][XI], u, b[GR].y);
 }
 
-// step (K, P) of the main loop: xi = 2P, 2P + 1; dma(piece) issues DMA piece `piece` of chunk K + 2.  With one block row
-// (NG = 1) the slots of M2, M4, M6, M8 and of their B reads are empty.
+// step (K, P) of the main loop, one block row: xi = 2P, 2P + 1; dma(piece) issues DMA piece `piece` of chunk K + 2.
 // VAR (ablation builds, timing only): 10 = no transform arithmetic, 11 = no DMA, 12 = no weight reloads, 13 = no B reads,
 // 14 = no transform LDS traffic, 15 = bare MFMAs
 template <int K, int P, int VAR, typename CT, typename DMA> __device__ __forceinline__ void step(CT& c, DMA&& dma) {
+    static_assert(CT::NG == 1, "two block rows: step2");
     constexpr int X0 = 2 * P, X1 = 2 * P + 1, SQ = K * 18 + P;
-    constexpr int VPAR = K & 1, DPAR = (K + 1) & 1, NG = CT::NG;
+    constexpr int VPAR = K & 1, DPAR = (K + 1) & 1;
     const f32x4 u = c.ur[SQ % URING];
-    f32x2 b0[NG], b1[NG];
-#pragma unroll
-    for (int g = 0; g < NG; ++g) b0[g] = c.b[0][g];
+    f32x2 b0[1] = {c.b[0][0]}, b1[1];
     mfma_j0<K, X0, 0>(c, u.x, b0);                   PNP_SLOT();          // M1
-    if constexpr (VAR != 13 && VAR != 15) b_load<VPAR, X1, 0>(c);
-    PNP_SLOT();
-    mfma_j0<K, X0, 1>(c, u.x, b0);                   PNP_SLOT();          // M2
-    if constexpr (VAR != 13 && VAR != 15) b_load<VPAR, X1, 1>(c);
+    if constexpr (VAR != 13 && VAR != 15) b_load<VPAR, X1>(c);
     PNP_SLOT();
     mfma_j1<X0, 0>(c, u.y, b0);                      PNP_SLOT();          // M3
     if constexpr (VAR != 10 && VAR != 15) slice_valu<P>(c);
     PNP_SLOT();
-    mfma_j1<X0, 1>(c, u.y, b0);                      PNP_SLOT();          // M4
     if constexpr (VAR != 14 && VAR != 15) slice_lds<DPAR, P, 0>(c);
     PNP_SLOT();
-#pragma unroll
-    for (int g = 0; g < NG; ++g) b1[g] = c.b[1][g];
+    b1[0] = c.b[1][0];
     mfma_j0<K, X1, 0>(c, u.z, b1);                   PNP_SLOT();          // M5
-    if constexpr (X1 + 1 < 36 && VAR != 13 && VAR != 15) b_load<VPAR, X1 + 1, 0>(c);
-    PNP_SLOT();
-    mfma_j0<K, X1, 1>(c, u.z, b1);                   PNP_SLOT();          // M6
-    if constexpr (X1 + 1 < 36 && VAR != 13 && VAR != 15) b_load<VPAR, X1 + 1, 1>(c);
+    if constexpr (X1 + 1 < 36 && VAR != 13 && VAR != 15) b_load<VPAR, X1 + 1>(c);
     PNP_SLOT();
     mfma_j1<X1, 0>(c, u.w, b1);                      PNP_SLOT();          // M7
     if constexpr (P < CT::G::PPW && VAR != 11 && VAR != 15) dma(P);
     if constexpr (VAR != 14 && VAR != 15) slice_lds<DPAR, P, 1>(c);
     PNP_SLOT();
-    mfma_j1<X1, 1>(c, u.w, b1);                      PNP_SLOT();          // M8
     if constexpr (VAR != 14 && VAR != 15) slice_lds<DPAR, P, 2>(c);
     if constexpr (VAR != 12 && VAR != 15 && SQ + URING < NCH * 18) c.ur[SQ % URING] = c.uload_next();
     PNP_SLOT();
 }
-template <int K, int VAR, typename CT, typename DMA, int... P> __device__ __forceinline__ void chunk_steps(CT& c, DMA&& dma, std::integer_sequence<int, P...>) {
-    (step<K, P, VAR>(c, dma), ...);
+// two block rows: what stands in slot S (0..3 = a..d of the table above PNP_SLOT) of step P, and the step's VALU block
+template <int DPAR, int P, int S, int VAR, typename CT, typename DMA> __device__ __forceinline__ void slot2(CT& c, DMA&& dma) {
+    constexpr bool LDS = VAR != 14 && VAR != 15, DM = VAR != 11 && VAR != 15;
+    if constexpr (P == 0) {
+        if constexpr (S < 2 && LDS) patch_load<DPAR, 0, S>(c);
+        if constexpr (S == 3 && DM) dma(0);
+    } else if constexpr (P < 6) {
+        if constexpr (S == 0 && DM) dma(P);
+        if constexpr ((S == 1 || S == 2) && LDS) patch_load<DPAR, P, S - 1>(c);
+    } else if constexpr (P >= 7 && P <= 12 && LDS) {
+        constexpr int SL = 6 + 2 * ((P - 7) / 2), Y = (P & 1) ? S - 1 : S + 3;       // odd step: b, c, d = 0..2; even step: a, b, c = 3..5
+        if constexpr (Y >= 0 && Y < 6) v_write<DPAR, SL, Y>(c);
+    }
 }
-// weight reloads issued in steps p0 .. 17 of chunk K
-template <int K> constexpr int reloads_from(int p0) {
+template <int P, typename CT> __device__ __forceinline__ void valu2(CT& c) {
+    if constexpr (P >= 1 && P <= 6) slice_valu<P - 1>(c);
+    else if constexpr (P == 7 || P == 9 || P == 11) slice_valu<P - 1>(c);              // column slices 6, 8, 10
+}
+template <int K, int P, int VAR, typename CT, typename DMA> __device__ __forceinline__ void step2(CT& c, DMA&& dma) {
+    static_assert(CT::NG == 2 && CT::G::PPW == 6, "one DMA piece in each of the steps 0..5");
+    constexpr int X0 = 2 * P, X1 = 2 * P + 1, SQ = K * 18 + P;
+    constexpr int VPAR = K & 1, DPAR = (K + 1) & 1;
+    const f32x4 u = c.ur[SQ % URING];
+    f32x2 b0[2] = {c.b[0][0], c.b[0][1]}, b1[2];
+    mfma_j0<K, X0, 0>(c, u.x, b0);                   PNP_SLOT();          // M1
+    if constexpr (VAR != 13 && VAR != 15) b_load<VPAR, X1>(c);
+    PNP_SLOT();
+    mfma_j0<K, X0, 1>(c, u.x, b0);                   PNP_SLOT();          // M2
+    slot2<DPAR, P, 0, VAR>(c, dma);
+    PNP_SLOT();
+    mfma_j1<X0, 0>(c, u.y, b0);                      PNP_SLOT();          // M3
+    if constexpr (VAR != 10 && VAR != 15) valu2<P>(c);
+    if constexpr (P == 0 && K > 0 && VAR != 12 && VAR != 15 && SQ - 1 + URING < NCH * 18) c.ur[(SQ - 1) % URING] = c.uload_next();
+    PNP_SLOT();
+    mfma_j1<X0, 1>(c, u.y, b0);                      PNP_SLOT();          // M4
+    slot2<DPAR, P, 1, VAR>(c, dma);
+    PNP_SLOT();
+    b1[0] = c.b[1][0]; b1[1] = c.b[1][1];
+    mfma_j0<K, X1, 0>(c, u.z, b1);                   PNP_SLOT();          // M5
+    if constexpr (X1 + 1 < 36 && VAR != 13 && VAR != 15) b_load<VPAR, X1 + 1>(c);
+    PNP_SLOT();
+    mfma_j0<K, X1, 1>(c, u.z, b1);                   PNP_SLOT();          // M6
+    slot2<DPAR, P, 2, VAR>(c, dma);
+    PNP_SLOT();
+    mfma_j1<X1, 0>(c, u.w, b1);                      PNP_SLOT();          // M7
+    slot2<DPAR, P, 3, VAR>(c, dma);
+    PNP_SLOT();
+    mfma_j1<X1, 1>(c, u.w, b1);                      PNP_SLOT();          // M8
+    if constexpr (P < 17 && VAR != 12 && VAR != 15 && SQ + URING < NCH * 18) c.ur[SQ % URING] = c.uload_next();
+    PNP_SLOT();
+}
+template <int K, int VAR, typename CT, typename DMA, int... P> __device__ __forceinline__ void chunk_steps(CT& c, DMA&& dma, std::integer_sequence<int, P...>) {
+    if constexpr (CT::NG == 2) (step2<K, P, VAR>(c, dma), ...);
+    else (step<K, P, VAR>(c, dma), ...);
+}
+// weight reloads of steps p0 .. p1 of chunk K
+template <int K> constexpr int reloads_of(int p0, int p1) {
     int n = 0;
-    for (int p = p0; p < 18; ++p) n += (K * 18 + p + URING < NCH * 18) ? 1 : 0;
+    for (int p = p0; p <= p1; ++p) n += (K * 18 + p + URING < NCH * 18) ? 1 : 0;
     return n;
 }
 // chunk K of a tile: MFMAs on V buffer K & 1, transform of chunk K + 1, DMA of chunk K + 2
 template <int K, bool STAMP, int VAR, typename CT, typename DMA> __device__ __forceinline__ void chunk(CT& c, DMA&& dma, unsigned long long& t_wait) {
-    patch_load<(K + 1) & 1, 0, 0>(c);
-    patch_load<(K + 1) & 1, 0, 1>(c);
-    b_load<K & 1, 0, 0>(c);
-    b_load<K & 1, 0, 1>(c);
+    if constexpr (CT::NG == 1) {                             // (two block rows: patch row 0 is read in step 0)
+        patch_load<(K + 1) & 1, 0, 0>(c);
+        patch_load<(K + 1) & 1, 0, 1>(c);
+    }
+    b_load<K & 1, 0>(c);
     PNP_SLOT();
     chunk_steps<K, VAR>(c, dma, std::make_integer_sequence<int, 18>{});
     unsigned long long ta = 0;
     if (STAMP) ta = __builtin_amdgcn_s_memtime();
-    // this chunk's DMA pieces have landed: they were issued in steps 0 .. PPW - 1, each before its step's weight reload, so
-    // at most the reloads of steps PPW .. 17 may still be in flight (the last chunks of a tile reload nothing: see step())
-    asm volatile("s_waitcnt vmcnt(%0)" :: "n"(reloads_from<K>(CT::G::PPW)) : "memory");
+    // this chunk's DMA pieces have landed: vector-memory operations leave the queue in issue order, and piece p was issued
+    // in step p < PPW before that step's weight reload and behind every older reload, so only reloads are younger than
+    // the last piece.  Two block rows: those of steps PPW - 1 .. 16 (step 17's is issued behind this wait).  One block
+    // row: those of steps PPW - 1 .. 17; the count leaves out step PPW - 1 (one stricter than needed, never weaker).
+    // The last chunk of a tile reloads nothing: see step()
+    constexpr int PPW = CT::G::PPW, younger = CT::NG == 2 ? reloads_of<K>(PPW - 1, 16) : reloads_of<K>(PPW, 17);
+    asm volatile("s_waitcnt vmcnt(%0)" :: "n"(younger) : "memory");
     __syncthreads();
     if (STAMP) t_wait += __builtin_amdgcn_s_memtime() - ta;
 }
@@ -364,7 +423,8 @@ __global__ __launch_bounds__(256, 1) void k_mid_wino44(const float* __restrict__
     const int d_off = 4 * ((2 * wv + j) * (PLANE / 4) + g * PC + tc);               // 16-byte aligned
     const ptrdiff_t hw4 = (ptrdiff_t)4 * H * W, w4 = (ptrdiff_t)4 * W;
     const unsigned st_off = 4u * (unsigned)(4 * (lane >> 4) * H * W + 4 * tc);      // output: channel 4 (lane >> 4) of the wave's 16, column 4 tc
-    const int v_off = g * 128 + wv * 32 + tc * 2 + j;
+    // V item: [k-row wv][block tc][block row g][k-step j] -- the 64 lanes of a wave write 64 consecutive dwords per point
+    const int v_off = NG == 2 ? wv * 64 + tc * 4 + g * 2 + j : wv * 32 + tc * 2 + j;
 
     // DMA piece descriptors: bits 0..26 = element offset of the lane's 16-byte chunk inside the chunk's 8 channel planes,
     // bit 27 = padding, bits 28..31 = which image edge would put the chunk outside
@@ -412,9 +472,10 @@ __global__ __launch_bounds__(256, 1) void k_mid_wino44(const float* __restrict__
     lds_f* const ldsp = (lds_f*)lds;
     c.dsrc[0] = ldsp + d_off;                     c.dsrc[1] = ldsp + DBUF + d_off;
     c.vdst[0] = ldsp + 2 * DBUF + v_off;          c.vdst[1] = ldsp + 2 * DBUF + VBUF + v_off;
-    c.vsrc0[0] = ldsp + 2 * DBUF + 2 * lane;      c.vsrc0[1] = ldsp + 2 * DBUF + VBUF + 2 * lane;
-    c.vsrc1[0] = c.vsrc0[0] + 128;                c.vsrc1[1] = c.vsrc0[1] + 128;             // (block row 1; unused when NG = 1)
-    asm volatile("" : "+v"(c.vsrc1[0]), "+v"(c.vsrc1[1]));
+    // (laundered: folded into the instructions' offsets, the buffers' constant bases push some pairs of a ds_write2st64_b32
+    //  beyond its 8-bit offsets and the pair becomes two ds_write_b32)
+    asm volatile("" : "+v"(c.vdst[0]), "+v"(c.vdst[1]));
+    c.vsrc0[0] = ldsp + 2 * DBUF + 2 * NG * lane; c.vsrc0[1] = ldsp + 2 * DBUF + VBUF + 2 * NG * lane;
     // transformed weights: the same stream of NCH x 18 16-byte loads per lane for every tile, kept URING loads ahead
     const __attribute__((address_space(1))) char* const ubase = (const __attribute__((address_space(1))) char*)upack + (size_t)(wv * NCH * 18) * 1024;
     c.ucur = ubase;
