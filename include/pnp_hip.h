@@ -198,6 +198,17 @@ int pnp_prox_tv(const void* z_in, void* z_out, int H, int W, int batch, int dtyp
                 const void* sigma_in, double sigma_modifier, double fallback_sigma,
                 const void* xrec, double* sse_out, void* sigma_out, void* stream);
 
+/* TVDenoiser(multi=False).denoise (denoisers/TV.py:21-26 with multichannel=False): ONE two-dimensional multi-level
+ * Haar decomposition of the image (pywt.wavedecn, L = max(min(log2 H, log2 W) - 3, 1) levels), one BayesShrink
+ * threshold per detail sub-band (ad, da, dd of every level, each over the whole image), soft shrinkage,
+ * reconstruction -- fused, like pnp_prox_tv, with the noise estimate and the squared-error sum.
+ * Argument for argument pnp_prox_tv, same shapes (H in {16, 32, 64, 128, 256}, W a multiple of 16 in [16, 256]),
+ * same meaning: the estimate made when sigma_in == NULL is pnp_sigma_est's (per-COLUMN db2 MAD, what the loops pass
+ * to every denoiser) bit for bit.  z_out may alias z_in.  An image's result does not depend on the batch.        */
+int pnp_prox_wavelet2d(const void* z_in, void* z_out, int H, int W, int batch, int dtype,
+                       const void* sigma_in, double sigma_modifier, double fallback_sigma,
+                       const void* xrec, double* sse_out, void* sigma_out, void* stream);
+
 /* NLMDenoiser.denoise (denoisers/NLM.py:22-27 -> skimage 0.18 _nl_means_denoising_2d, slow mode,
  * Schraudolph fast_exp).  patch_size as the caller passes it (even sizes are bumped to the
  * next odd one like skimage: 4 -> 5; supported sides 3/5/7), patch_distance in [1, 8].

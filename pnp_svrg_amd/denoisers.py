@@ -30,14 +30,17 @@ class Denoise():
 
 
 class TVDenoiser(Denoise):
-    """reference denoisers/TV.py:9-26: despite the name, skimage's wavelet BayesShrink applied
-    to every column of the 2-D image.  Runs as pnp_prox_tv on the MI355X."""
+    """reference denoisers/TV.py:9-26: despite the name, skimage's wavelet BayesShrink.
+    multi=True (the reference's default): skimage takes the last axis for channels, so every column of the 2-D image
+    is denoised on its own with a 1-D Haar transform; runs as pnp_prox_tv on the MI355X.
+    multi=False: one two-dimensional multi-level Haar decomposition of the image, one threshold per detail sub-band
+    (ad, da, dd of every level); runs as pnp_prox_wavelet2d.  `rescale_sigma` is accepted and without effect
+    (float images), as in skimage."""
 
     def __init__(self, multi=True, rescale_sigma=True, decay=1, denoise_strength=0, sigma_modifier=1, dtype=None):
         super().__init__()
-        if not multi:
-            raise NotImplementedError('multi=False (a true 2-D wavelet transform) is not on the reference hot path')
         self.multi = multi
+        self._prox = ops.prox_tv if multi else ops.prox_wavelet2d
         self.rescale_sigma = rescale_sigma
         self.denoise_strength = denoise_strength
         self.sigma_modifier = sigma_modifier
@@ -49,7 +52,7 @@ class TVDenoiser(Denoise):
         """z: [B,H,W] device tensor.  Returns (denoised, sse or None, sigma_est [B])."""
         self.t += 1
         fallback = self.denoise_strength * self.decay ** self.t
-        return ops.prox_tv(z, sigma_in=sigma_est, sigma_modifier=self.sigma_modifier, fallback_sigma=fallback, xrec=xrec)
+        return self._prox(z, sigma_in=sigma_est, sigma_modifier=self.sigma_modifier, fallback_sigma=fallback, xrec=xrec)
 
     def denoise(self, noisy, sigma_est=0):
         z = _as_dev(noisy, self.dtype)
@@ -66,7 +69,7 @@ class TVDenoiser(Denoise):
         if probe:
             return self.denoise_strength == 0
         self.t += 1
-        ops.prox_tv(z, sigma_modifier=self.sigma_modifier, fallback_sigma=0.0, xrec=xrec, out=z, sse=sse)
+        self._prox(z, sigma_modifier=self.sigma_modifier, fallback_sigma=0.0, xrec=xrec, out=z, sse=sse)
         return True
 
 

@@ -347,29 +347,42 @@ class PrBatch(_BatchBase):
 
 # ---------------------------------------------------------------------------------------------------------- prox
 class TVProx:
-    """denoisers/TV.py semantics for the engines (fused estimate_sigma + BayesShrink + error sum)."""
+    """denoisers/TV.py semantics for the engines (fused estimate_sigma + BayesShrink + error sum).
+    multi=True: the per-column 1-D prox (pnp_prox_tv), which the one-kernel iteration holds inside the gradient kernel.
+    multi=False: the 2-D wavelet prox (pnp_prox_wavelet2d): a kernel of its own after the gradient kernel, which in the
+    one-kernel iteration makes step + noise estimate (the DnCNNProx pattern) -- the engine then steps per iteration."""
 
-    def __init__(self, sigma_modifier=1.0, decay=1.0, denoise_strength=0.0):
+    def __init__(self, sigma_modifier=1.0, decay=1.0, denoise_strength=0.0, multi=True):
         self.sigma_modifier, self.decay, self.denoise_strength, self.t = sigma_modifier, decay, denoise_strength, 0
+        self.multi = multi
+        self.fused_denoise = bool(multi)                        # one-kernel iteration: only the 1-D prox runs inside it
 
     def bind(self, batch):
         self.sig = torch.empty(batch.B, dtype=batch.dtype, device=batch.xrec.device)
 
     def __call__(self, z, xrec, sse_out):
         self.t += 1
-        ops.prox_tv(z, sigma_modifier=self.sigma_modifier, fallback_sigma=self.denoise_strength * self.decay ** self.t,
-                    xrec=xrec, out=z, sse=sse_out, sigma_out=self.sig)
+        prox = ops.prox_tv if self.multi else ops.prox_wavelet2d
+        prox(z, sigma_modifier=self.sigma_modifier, fallback_sigma=self.denoise_strength * self.decay ** self.t,
+             xrec=xrec, out=z, sse=sse_out, sigma_out=self.sig)
         return z
 
     inplace = True                                              # writes its result into the iterate it was given
-    # one-kernel iteration (pnp_csmri_svrg_step): the prox runs inside the gradient kernel
-    fused_denoise = True
 
+    # one-kernel iteration (pnp_csmri_svrg_step): the 1-D prox runs inside the gradient kernel (fused_denoise); for the
+    # 2-D prox that kernel stops after the noise estimate and after_fused shrinks with it
     def fused_args(self):
+        if not self.multi:
+            return dict(sigma_out=self.sig)
         self.t += 1
         return dict(sigma_modifier=self.sigma_modifier, fallback_sigma=self.denoise_strength * self.decay ** self.t, sigma_out=self.sig)
 
     def after_fused(self, z, xrec, sse_out):
+        if not self.multi:
+            self.t += 1
+            ops.prox_wavelet2d(z, sigma_in=self.sig, sigma_modifier=self.sigma_modifier,
+                               fallback_sigma=self.denoise_strength * self.decay ** self.t, xrec=xrec, out=z, sse=sse_out,
+                               sigma_out=self.sig)
         return z
 
 

@@ -300,6 +300,20 @@ def prox_tv(z, sigma_in=None, sigma_modifier=1.0, fallback_sigma=0.0, xrec=None,
     return out, sse, sigma_out
 
 
+def prox_wavelet2d(z, sigma_in=None, sigma_modifier=1.0, fallback_sigma=0.0, xrec=None, out=None, sse=None, sigma_out=None):
+    """Fused estimate_sigma + 2-D multi-level Haar BayesShrink prox (TVDenoiser(multi=False)) (+ squared error vs xrec).
+    Signature and result of `prox_tv`: (denoised [B,H,W], sse [B] float64 or None, sigma_est [B])."""
+    require_gpu()
+    B, H, W = z.shape
+    out = out if out is not None else torch.empty_like(z)
+    if xrec is not None and sse is None:
+        sse = torch.empty(B, dtype=torch.float64, device=z.device)
+    sigma_out = sigma_out if sigma_out is not None else torch.empty(B, dtype=z.dtype, device=z.device)
+    N.call('pnp_prox_wavelet2d', _p(z), _p(out), H, W, B, _DT[z.dtype], _p(sigma_in), float(sigma_modifier),
+           float(fallback_sigma), _p(xrec), _p(sse), _p(sigma_out), _stream())
+    return out, sse, sigma_out
+
+
 def sse(z, xrec, out=None):
     require_gpu()
     B = z.shape[0]
