@@ -79,6 +79,32 @@ int pnp_csmri_sel_from_dense(pnp_csmri_plan* plan, const uint8_t* sel, uint8_t* 
  * YT: [batch][W][H] complex = Y transposed (measurements, CSMRI.py:32-33).               */
 int pnp_csmri_pack_y(pnp_csmri_plan* plan, const void* YT, const uint8_t* selT, void* yh, void* stream);
 
+/* A batch of problems GENERATED on the device (problems/CSMRI.py:12-59 per problem: Bernoulli mask :43-45, Y0 = mask o fft2(x)
+ * :27,53-59, real noise on the support :32-33, Xinit = minmax |ifft2 Y| :35-36) from a counter-based stream, published here so
+ * that a caller can restate it.  For an item with 64-bit `seed` and `id`, and a sub-stream tag k (mix64 and the per-position key
+ * exactly as in the minibatch draw above):
+ *     state_k = mix64(mix64(mix64(seed) + id) + k)
+ *     key_k(i) = key(state_k, i)              i = flat row-major k-space index ky*W + kx (np.flatnonzero order)
+ *   mask  (k = 0)   : position i is sampled iff (uint64)key_0(i) < T, T = floor(alpha * 2^32) clipped to [0, 2^32] (computed by
+ *                     the caller in float64; T = 2^32 samples every position) -- Bernoulli per entry, so M0 differs per item;
+ *   data            : Y0 = mask o fft2(x);  sigma = sqrt(||Y0||_2 * snr_fac / H / W), snr_fac = 10^(-snr/10)  (problem.py:58-61:
+ *                     the norm, not its square); the sum of squares is taken in double in a fixed order;
+ *   noise (k = 1, 2): u1 = (key_1(i) + 1) * 2^-32 in (0, 1], u2 = key_2(i) * 2^-32 in [0, 1), n(i) = sqrt(-2 ln u1) * cos(2 pi u2)
+ *                     (Box-Muller in double for both plan dtypes), Y = Y0 + mask * sigma * n, into the REAL part only.  The 32-bit
+ *                     uniforms end the tails at sqrt(-2 ln 2^-32) = 6.66 sigma.  An f32 and an f64 plan hold the same problem up to
+ *                     the final rounding;
+ *   init            : Xinit = minmax(|ifft2(Y)|) (Y is not Hermitian: both the real and the imaginary part of the inverse count).
+ * Inputs: images [n_images][H][W] (`dtype`, already normalised to [0, 1]); per item [batch] device arrays image_idx (int32, in
+ * [0, n_images)), thresh (uint64 T), snr_fac (double), seed, id (uint64).  Outputs, in the layouts the gradient calls read:
+ * xrec [batch][H][W]; bitsT [batch][W][H/32]; maskT [batch][W][H] uint8 (may be NULL); YT [batch][W][H] complex; yh_full = the packed
+ * half spectrum pnp_csmri_pack_y makes from this YT and maskT, bit for bit; xinit [batch][H][W]; M0 [batch] int32; inv_m0 [batch]
+ * (`dtype`); sigma [batch] double.  Uses the plan's workspace; no allocation, no synchronisation.  An item's outputs do not
+ * depend on the batch size or on its index in the batch (fixed-order reductions, no atomics).                                 */
+int pnp_csmri_generate(pnp_csmri_plan* plan, const void* images, int n_images, const int32_t* image_idx, const uint64_t* thresh,
+                       const double* snr_fac, const uint64_t* seed, const uint64_t* id, void* xrec, uint32_t* bitsT,
+                       uint8_t* maskT, void* YT, void* yh_full, void* xinit, int32_t* M0, void* inv_m0, double* sigma,
+                       void* stream);
+
 /* out = alpha * Re ifft2( sel o fft2(a - b) - sel o Y ) + beta * c1 + gamma * c2
  *   b, yh, c1, c2 may be NULL (treated as zero).  out may alias a, c1 or c2.
  *   grad_full(z)            : a=z, sel=mask,   yh=pack(mask),    alpha=1/M0

@@ -5,80 +5,17 @@
 // The real part of an inverse FFT only sees the Hermitian part of its argument, so the
 // whole thing runs on the half spectrum with real<->complex transforms:
 //
-//   k_rows_fwd   two real image rows -> one complex FFT-W -> split -> packed half spectrum,
-//                written TRANSPOSED ([kx][h]) through an LDS tile (256-B segments)
+//   k_rows_fwd   (csmri_rows.h) real rows -> packed transposed half spectrum
 //   k_cols       per kx column: FFT-H -> symmetrised selector (and data term) -> inverse FFT-H,
 //                in one kernel, in place (forward and inverse share the axis)
-//   k_rows_inv   transposed read -> Hermitian re-expansion -> one complex inverse FFT-W gives two
-//                real rows -> fused epilogue  out = alpha*g + beta*c1 + gamma*c2
-//
-// "Packed": column kx=0 stores (X[.,0], X[.,W/2]) as (re,im) -- both are real after the row
-// pass -- so the half spectrum is exactly [W/2][H] complex = the bytes of the real image.
-#include "fft.h"
+//   k_rows_inv   (csmri_rows.h) Hermitian re-expansion, inverse row FFT, fused epilogue
+#include "csmri_rows.h"
 #include "draw.h"
 #include <vector>
 #include <cstdlib>
 #include <cmath>
 
 namespace pnp {
-
-template <typename T> struct alignas(4 * sizeof(T)) vec4 { T a, b, c, d; };
-
-// RA x LA = the register x lane split of one length-N transform (fft.h: fft_gen); RA == LA for N = 64, 256,
-// <8,16> for N = 128.  A lane group is LG = max(RA, LA) lanes.
-template <typename T, int RA, int LA> struct FftSmem {
-    static constexpr int N = RA * LA;
-    static constexpr int LG = RA > LA ? RA : LA;
-    static constexpr int G = 256 / LG;                       // lane groups per 256-thread block
-    static constexpr int TILE = G * (N + 1);                 // [group][N+1] complex
-    static constexpr int SCR = G * LG * (LG + 1);            // [group][LG][LG+1] complex
-    static constexpr int ELEMS = TILE > SCR ? TILE : SCR;
-};
-
-// ------------------------------------------------------------------------------- rows forward
-template <typename T, int RA, int LA>
-__global__ __launch_bounds__(256) void k_rows_fwd(const T* __restrict__ a, const T* __restrict__ b,
-                                                  cx<T>* __restrict__ S1T, const cx<T>* __restrict__ twtab, int H) {
-    using S = FftSmem<T, RA, LA>;
-    constexpr int N = S::N, G = S::G, LG = S::LG;
-    __shared__ cx<T> smem[S::ELEMS];
-    const int t = threadIdx.x, g = t / LG, lane = t % LG;
-    const int prob = blockIdx.y, h0 = blockIdx.x * 2 * G;
-    const size_t img = (size_t)prob * H * N;
-    const size_t ra = img + (size_t)(h0 + 2 * g) * N, rb = ra + N;
-
-    cx<T> v[LG], tw[LG];
-    load_twiddles_gen<T, LG>(tw, twtab, lane, N);
-#pragma unroll
-    for (int r = 0; r < RA; ++r) {
-        const int w = (lane < LA ? lane : 0) + LA * r;
-        T va = a[ra + w], vb = a[rb + w];
-        if (b != nullptr) { va -= b[ra + w]; vb -= b[rb + w]; }
-        v[r] = {va, vb};
-    }
-    fft_gen<T, RA, LA, false>(v, tw, smem + g * LG * (LG + 1), lane);
-    __syncthreads();
-    if (lane < RA) {
-#pragma unroll
-        for (int r = 0; r < LA; ++r) smem[g * (N + 1) + lane + RA * r] = v[r];
-    }
-    __syncthreads();
-
-    // split the two interleaved real transforms and store transposed
-    const int p = t % G;
-    const cx<T>* zp = smem + p * (N + 1);
-    for (int kx = t / G; kx < N / 2; kx += 256 / G) {
-        const cx<T> zk = zp[kx], zm = zp[(N - kx) & (N - 1)];
-        vec4<T> o;
-        if (kx == 0) {
-            const cx<T> zn = zp[N / 2];
-            o = {zk.x, zn.x, zk.y, zn.y};
-        } else {
-            o = {(T)0.5 * (zk.x + zm.x), (T)0.5 * (zk.y - zm.y), (T)0.5 * (zk.y + zm.y), (T)-0.5 * (zk.x - zm.x)};
-        }
-        *reinterpret_cast<vec4<T>*>(S1T + ((size_t)prob * (N / 2) + kx) * H + h0 + 2 * p) = o;
-    }
-}
 
 // ------------------------------------------------------------------------------- columns
 // Selector forms of the column pass:
@@ -180,51 +117,6 @@ __global__ __launch_bounds__(256) void k_cols(cx<T>* __restrict__ S1T, const uin
     }
 }
 
-// ------------------------------------------------------------------------------- rows inverse + epilogue
-template <typename T, int RA, int LA>
-__global__ __launch_bounds__(256) void k_rows_inv(const cx<T>* __restrict__ S1T, const cx<T>* __restrict__ twtab, int H,
-                                                  T alpha, const T* __restrict__ alpha_vec, T beta, const T* c1, T gamma,
-                                                  const T* c2, T* out) {
-    using S = FftSmem<T, RA, LA>;
-    constexpr int N = S::N, G = S::G, LG = S::LG;
-    __shared__ cx<T> smem[S::ELEMS];
-    const int t = threadIdx.x, g = t / LG, lane = t % LG;
-    const int prob = blockIdx.y, h0 = blockIdx.x * 2 * G;
-    if (alpha_vec != nullptr) alpha *= alpha_vec[prob];        // per-problem 1/M0 of a mixed-mask batch
-
-    const int p = t % G;
-    cx<T>* zp = smem + p * (N + 1);
-    for (int kx = t / G; kx < N / 2; kx += 256 / G) {
-        const vec4<T> q = *reinterpret_cast<const vec4<T>*>(S1T + ((size_t)prob * (N / 2) + kx) * H + h0 + 2 * p);
-        if (kx == 0) {
-            zp[0] = {q.a, q.c};
-            zp[N / 2] = {q.b, q.d};
-        } else {
-            zp[kx] = {q.a - q.d, q.b + q.c};                 // A + iB
-            zp[N - kx] = {q.a + q.d, q.c - q.b};             // conj(A) + i conj(B)
-        }
-    }
-    __syncthreads();
-    cx<T> v[LG], tw[LG];
-    load_twiddles_gen<T, LG>(tw, twtab, lane, N);
-#pragma unroll
-    for (int r = 0; r < LA; ++r) v[r] = smem[g * (N + 1) + (lane < RA ? lane : 0) + RA * r];
-    fft_gen<T, LA, RA, true>(v, tw, smem + g * LG * (LG + 1), lane);
-
-    const size_t ra = (size_t)prob * H * N + (size_t)(h0 + 2 * g) * N, rb = ra + N;
-    if (lane < LA) {
-#pragma unroll
-        for (int r = 0; r < RA; ++r) {
-            const int w = lane + LA * r;
-            T oa = alpha * v[r].x, ob = alpha * v[r].y;
-            if (c1 != nullptr) { oa += beta * c1[ra + w]; ob += beta * c1[rb + w]; }
-            if (c2 != nullptr) { oa += gamma * c2[ra + w]; ob += gamma * c2[rb + w]; }
-            out[ra + w] = oa;
-            out[rb + w] = ob;
-        }
-    }
-}
-
 // ------------------------------------------------------------------------------- data term
 template <typename T>
 __global__ void k_pack_y(const cx<T>* __restrict__ YT, const uint8_t* __restrict__ selT, cx<T>* __restrict__ yh, int H, int W) {
@@ -317,14 +209,6 @@ template <typename T> void fill_twiddles(std::vector<cx<T>>& tab, int N) {
 }  // namespace pnp
 
 using namespace pnp;
-
-struct pnp_csmri_plan {
-    int H, W, batch, dtype, NL;              // NL: 16 -> N = 256, 8 -> N = 64, 12 -> N = 128 (8 x 16 split)
-    void* work;     // [batch][W/2][H] complex
-    void* twtab;    // [N] complex
-    void* mbd;      // [batch] MbDesc scratch of pnp_csmri_draw_minibatch
-    int fused_min_batch;   // batches at least this large take the one-kernel gradient (env PNP_CSMRI_FUSED_MIN_BATCH)
-};
 
 extern "C" int pnp_csmri_plan_create(pnp_csmri_plan** out, int H, int W, int batch, int dtype) {
     PNP_CHECK_ARG(out != nullptr, "null plan pointer");

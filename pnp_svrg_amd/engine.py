@@ -105,6 +105,58 @@ class CsmriBatch(_BatchBase):
             xinit[b] = (xi - xi.min()) / (xi.max() - xi.min())
         return cls(xrec, mask.reshape(B, H, W), Y, xinit, dtype=dtype)
 
+    @property
+    def mask_np(self):
+        """[B, H, W] uint8 sampling masks on the host; a generated batch reads them back on first use."""
+        if self._mask_np is None:
+            self._mask_np = np.ascontiguousarray(self.maskT.cpu().numpy().swapaxes(1, 2))
+        return self._mask_np
+
+    @mask_np.setter
+    def mask_np(self, m):
+        self._mask_np = m
+
+    @staticmethod
+    def upload_images(images, H=256, W=256, dtype=torch.float32, device='cuda'):
+        """The image set of `generate`, each image min-max normalised in float64 (sweep._norm01), as one [n, H, W] device tensor."""
+        xs = []
+        for img in images:
+            x = np.asarray(img, np.float64)
+            if x.shape != (H, W):
+                raise ValueError(f'image of shape {x.shape}: generate needs {H} x {W} images')
+            xs.append((x - x.min()) / (x.max() - x.min()))
+        return torch.from_numpy(np.stack(xs)).to(device, dtype).contiguous()
+
+    @classmethod
+    def generate(cls, images, items, H=256, W=256, dtype=torch.float32, device='cuda'):
+        """The problems of `items` (dicts of sweep.make_items: id, image, alpha, snr, seed) generated ON THE DEVICE from the
+        counter-based stream of include/pnp_hip.h (pnp_csmri_generate): Bernoulli mask, masked spectrum, real noise on the
+        support, Xinit -- problems/CSMRI.py:12-59 per item, NOT NumPy's streams.  images: a list of H x W arrays, or the
+        tensor `upload_images` made of them (upload once, generate many batches).  Host work: the [B] parameter vectors and
+        one read-back of M0."""
+        ops.require_gpu()
+        if not isinstance(images, torch.Tensor):
+            images = cls.upload_images(images, H, W, dtype, device)
+        B = len(items)
+        if B < 1 or any(not 0 <= it['image'] < images.shape[0] for it in items):
+            raise ValueError('generate needs at least one item and image indices inside the image set')
+        self = cls.__new__(cls)
+        self.B, self.H, self.W, self.N, self.dtype = B, H, W, H * W, dtype
+        self.device = images.device
+        self.plan = ops.CsmriPlan(H, W, B, dtype)
+        u64 = lambda v: np.array([int(x) & (2 ** 64 - 1) for x in v], np.uint64).view(np.int64)
+        thr = [min(max(int(np.floor(np.float64(it['alpha']) * 2.0 ** 32)), 0), 2 ** 32) for it in items]
+        par = [np.array([it['image'] for it in items], np.int32), np.array(thr, np.int64),
+               np.array([10.0 ** (-np.float64(it['snr']) / 10) for it in items], np.float64),
+               u64([it['seed'] for it in items]), u64([it['id'] for it in items])]
+        o = self.plan.generate(images, *[torch.from_numpy(a).to(self.device) for a in par])
+        self.xrec, self.xinit, self.maskT, self.bits = o['xrec'], o['xinit'], o['maskT'], o['bits']
+        self.YT, self.yh_full, self.inv_m0, self.sigma = o['YT'], o['yh_full'], o['inv_m0'], o['sigma']
+        self.M0 = o['M0'].cpu().numpy().astype(np.int64)
+        self.max_mb = int(self.M0.min())
+        self._mask_np = None
+        return self
+
     @classmethod
     def from_problems(cls, probs, dtype=torch.float32, device='cuda'):
         """From reference-style problem objects (anything with Xrec, mask, Y, Xinit: problems.CSMRI, the oracle's)."""

@@ -120,6 +120,30 @@ class CsmriPlan:
                float(beta), _p(c1), float(gamma), _p(c2), _p(out), _stream())
         return out
 
+    def generate(self, images, image_idx, thresh, snr_fac, seed, item_id, with_mask=True):
+        """pnp_csmri_generate: the B problems of this plan generated on the device from the counter-based stream of
+        include/pnp_hip.h.  images: [n, H, W] of the plan's dtype (normalised); per item device vectors image_idx (int32),
+        thresh (int64 holding T = floor(alpha 2^32)), snr_fac (float64, 10^(-snr/10)), seed, item_id (int64 holding the
+        64-bit values).  Returns a dict of device tensors: xrec, bits, maskT (None without with_mask), YT, yh_full, xinit,
+        M0 (int32), inv_m0, sigma (float64)."""
+        B, H, W, dt, dev = self.B, self.H, self.W, self.dtype, images.device
+        assert images.dtype == dt and images.dim() == 3 and tuple(images.shape[1:]) == (H, W)
+        for t, d in ((image_idx, torch.int32), (thresh, torch.int64), (snr_fac, torch.float64), (seed, torch.int64),
+                     (item_id, torch.int64)):
+            assert t.dtype == d and tuple(t.shape) == (B,)
+        o = dict(xrec=torch.empty((B, H, W), dtype=dt, device=dev),
+                 bits=torch.empty((B, W, H // 32), dtype=torch.int32, device=dev),
+                 maskT=torch.empty((B, W, H), dtype=torch.uint8, device=dev) if with_mask else None,
+                 YT=torch.empty((B, W, H), dtype=_CDT[dt], device=dev),
+                 yh_full=torch.empty((B, W // 2, H), dtype=_CDT[dt], device=dev),
+                 xinit=torch.empty((B, H, W), dtype=dt, device=dev),
+                 M0=torch.empty(B, dtype=torch.int32, device=dev),
+                 inv_m0=torch.empty(B, dtype=dt, device=dev),
+                 sigma=torch.empty(B, dtype=torch.float64, device=dev))
+        N.call('pnp_csmri_generate', self._h, _p(images), images.shape[0], _p(image_idx), _p(thresh), _p(snr_fac), _p(seed),
+               _p(item_id), _p(o['xrec']), _p(o['bits']), _p(o['maskT']), _p(o['YT']), _p(o['yh_full']), _p(o['xinit']),
+               _p(o['M0']), _p(o['inv_m0']), _p(o['sigma']), _stream())
+        return o
 
     def svrg_step(self, a, b, bits, alpha=1.0, beta=0.0, c1=None, gamma=0.0, c2=None, out=None, *, alpha_vec=None, denoise=True,
                   sigma_modifier=1.0, fallback_sigma=0.0, xrec=None, sse=None, sigma_out=None):

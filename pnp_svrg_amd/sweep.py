@@ -161,7 +161,10 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
     A rank's items run as batches on the engines of `engine.py`: CSMRI items of ANY mix of sampling ratios together (per-problem
     1/M0 and minibatch thresholds); Deblur / PR items are grouped by alpha, which fixes the operator's shape (scale_percent =
     100 alpha; num_meas = alpha H W).
-    seeding='generator': per-item data from a Generator stream keyed by the item, minibatches drawn on the device;
+    seeding='generator': per-item data from a Generator stream keyed by the item, built on the host, minibatches drawn on the device;
+    seeding='device'   : (problem='csmri') per-item data generated ON THE DEVICE from the counter-based stream of include/pnp_hip.h
+                         (engine.CsmriBatch.generate; the normalised image set is uploaded once per runner), minibatches drawn on
+                         the device and graph replay as with 'generator'; a third stream: not the data of the other two modes;
     seeding='legacy'   : per item exactly the reference's RNG use -- np.random.seed(item seed), the problem constructor's draws
                          in its order, np.random.seed(run_seed), then the loop's draws in ITS order (one select_mb per inner
                          iteration; pnp_saga: one select_mb for the table, then select_mb + np.random.choice(hist_size, 1) per
@@ -175,7 +178,10 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
         raise ValueError('mini_batch_size is required')
     if algorithm in ('svrg', 'sarah') and T2 is None:
         raise ValueError('T2 is required')
+    if seeding == 'device' and problem != 'csmri':
+        raise ValueError(f"seeding='device' is supported for problem='csmri' only (got {problem!r}); use 'generator' or 'legacy'")
     mb, dkw = mini_batch_size, dict(denoiser_kwargs or {})
+    dev_images = []                                              # seeding='device': the image set in HBM, uploaded on first use
 
     def group_key(it):
         return None if problem == 'csmri' else it['alpha']
@@ -252,6 +258,10 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
                 self.batch, draws = build_legacy(chunk)
                 self.idx_d = torch.from_numpy(np.stack([d[0] for d in draws], axis=1)).to(self.batch.device) if algorithm != 'gd' else None
                 self.rs = np.stack([d[1] for d in draws], axis=1)                  # [n_inner][B]
+            elif seeding == 'device':
+                if not dev_images:
+                    dev_images.append(E.CsmriBatch.upload_images(images, H, W, dtype))
+                self.batch, self.idx_d, self.rs = E.CsmriBatch.generate(dev_images[0], chunk, H, W, dtype), None, None
             else:
                 self.batch, self.idx_d, self.rs = build_generator(chunk), None, None
             kw = dict(seed=chunk[0]['id'] + 1)
