@@ -20,6 +20,7 @@
 //     chunk k + 2 is in flight; one barrier per chunk.
 #include "common.h"
 #include "wino44.h"
+#include "wino44_common.h"
 #include "tilewalk.h"
 #include <vector>
 #include <utility>
@@ -28,50 +29,19 @@
 namespace pnp {
 namespace w44 {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using f32x2 = __attribute__((ext_vector_type(2))) float;
+using namespace w44c;              // transform arithmetic, halo front end, Patch, weight cursor, C / TC / PC / KC / NCH
 
-constexpr int C = 64;
-constexpr int TC = 64;                                // region width: 16 blocks of 4 x 4
-constexpr int PC = 72;                                // LDS row: image columns [tx0 - 4, tx0 + 68) = eighteen 16-byte chunks
-constexpr int KC = 8;                                 // input channels per chunk
-constexpr int NCH = C / KC;
 // NG = block rows per region: 2 (8 x 64 outputs, 72 accumulator quads per wave; the throughput form) or 1 (4 x 64, 36 quads:
 // twice the regions for launches that would otherwise leave CUs idle -- a single 256 x 256 image is 128 regions of 8 x 64)
-template <int NG_> struct Geo {
+template <int NG_> struct Geo : HaloGeo<NG_> {                     // TR, PR, PLANE, DBUF, PPW: wino44_common.h
     static constexpr int NG = NG_;
-    static constexpr int TR = 4 * NG, PR = TR + 2;                 // output rows, halo rows
-    static constexpr int PLANE = NG == 2 ? 768 : 512;              // PR x 72 payload + pad: 0 mod 64 dwords (ds_read_b128 lane groups mix two planes)
-    static constexpr int DBUF = KC * PLANE;                        // 24 / 16 DMA pieces of 1 KiB
-    static constexpr int PPW = DBUF / 256 / 4;                     // 6 / 4 pieces per wave
     static constexpr int VPL = 128 * NG;                           // floats per xi plane of V: [4 k-rows][16 blocks][NG block rows][2 k-steps]
     static constexpr int VBUF = 36 * VPL;
-    static constexpr int LDS_FLOATS = 2 * DBUF + 2 * VBUF;         // 120 KiB / 68 KiB
+    static constexpr int LDS_FLOATS = 2 * HaloGeo<NG_>::DBUF + 2 * VBUF;         // 120 KiB / 68 KiB
     static constexpr int NQ_AGPR = NG == 2 ? 64 : 36;              // accumulator quads kept in AGPRs (of 72: block row 0 and xi < 28 of row 1; of 36: all)
     static constexpr bool in_agpr(int g, int xi) { return g * 36 + xi < NQ_AGPR; }
 };
 constexpr int URING = 18;                              // weight loads in flight per lane
-constexpr unsigned DUMMY = 1u << 27;                  // descriptor flag: padding chunk of a plane
-
-// B^T of F(4,3) applied to six values
-__device__ __forceinline__ void bt6(float d0, float d1, float d2, float d3, float d4, float d5, float (&v)[6]) {
-    const float t1 = __builtin_fmaf(-4.f, d2, d4), t2 = __builtin_fmaf(-4.f, d1, d3);
-    const float t3 = d4 - d2, sd = d3 - d1;
-    v[0] = __builtin_fmaf(4.f, d0, __builtin_fmaf(-5.f, d2, d4));
-    v[1] = t1 + t2;
-    v[2] = t1 - t2;
-    v[3] = __builtin_fmaf(2.f, sd, t3);
-    v[4] = __builtin_fmaf(-2.f, sd, t3);
-    v[5] = __builtin_fmaf(4.f, d1, __builtin_fmaf(-5.f, d3, d5));
-}
-// A^T of F(4,3) applied to six values
-template <typename T> __device__ __forceinline__ void at6(T m0, T m1, T m2, T m3, T m4, T m5, T (&y)[4]) {
-    const T s12 = m1 + m2, d12 = m1 - m2, s34 = m3 + m4, d34 = m3 - m4;
-    y[0] = (m0 + s12) + s34;
-    y[1] = 2.f * d34 + d12;                                 // contracted to (packed) fma
-    y[2] = 4.f * s34 + s12;
-    y[3] = (8.f * d34 + d12) + m5;
-}
 
 // hand-issued MFMAs: the accumulator quad lives in AGPRs (AG) or VGPRs; the first product of a tile takes the constant-zero
 // SrcC form.  (Left to the compiler, all 72 quads are sent to the 256 AGPRs and the overflow is shuffled around.)
@@ -92,28 +62,12 @@ template <bool AG> __device__ __forceinline__ void mfma_first(f32x4& acc, float 
 }
 
 // ---- memory streams of the main loop ------------------------------------------------------------------------------------------
-// * LDS-DMA (activations): inline asm, invisible to the compiler's s_waitcnt insertion -- visible, it makes every LDS read
-//   after a DMA wait for vmcnt(0), which drains the weight ring at every step.  One hand-counted vmcnt wait per chunk
-//   (vector-memory operations leave the queue in issue order; sched_barriers pin the order of everything else around it).
+// * LDS-DMA (activations): the halo front end of wino44_common.h, inline asm the compiler does not count.  One hand-counted
+//   vmcnt wait per chunk (sched_barriers pin the order of everything else around it).
 // * weights: plain loads, a ring of URING 16-byte values per lane; the compiler waits for them itself (its counts do not
 //   include the DMA pieces, so its waits are stricter than needed while pieces are in flight, never weaker).
 // * LDS: plain reads / writes, software-pipelined in the source (B operands one xi ahead, patch rows one slice ahead).
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) float lds_f;
-typedef __attribute__((address_space(3))) f32x2 lds_f2;
-typedef __attribute__((address_space(3))) f32x4 lds_f4;
-
-// one 1-KiB piece global -> LDS: lane's 16 bytes from rsrc.base + voff (an offset beyond num_records reads zeros)
-__device__ __forceinline__ void dma_piece_asm(unsigned voff, i32x4 rsrc, unsigned lds_byte_addr) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, 0 offen lds" :: "v"(voff), "s"(rsrc), "s"(lds_byte_addr) : "memory");
-}
-
-struct Patch {
-    f32x2 a; f32x4 m; f32x2 e;                                 // one patch row in flight: LDS columns 4tc + 2..3, 4..7, 8..9
-    f32x2 t[6][3];                                             // row transforms as register pairs: (V0, V5), (V1, V2), (V3, V4) of row r
-    f32x2 v[6];                                                // one transformed pair of columns on its way to the V image
-};
-template <int NG_> struct Ctx {
+template <int NG_> struct Ctx : WeightCursor {              // + the weight stream of this wave (ucur, ulane, uload_next)
     static constexpr int NG = NG_;
     using G = Geo<NG_>;
     f32x4 acc[NG_][36];
@@ -123,16 +77,6 @@ template <int NG_> struct Ctx {
     const lds_f* dsrc[2];                                      // this lane's patch in the two d buffers
     lds_f* vdst[2];                                            // its V item in the two V buffers
     const lds_f* vsrc0[2];                                     // its B operands (both block rows: 16 bytes) in the two V buffers
-    // weight stream of this wave: a scalar cursor (1 KiB per load; advanced on the scalar ALU, re-defined through an empty asm so
-    // that it stays ONE register pair instead of 144 hoisted addresses) + the lane's 16 bytes as a 32-bit vector offset
-    const __attribute__((address_space(1))) char* ucur;
-    unsigned ulane;
-    __device__ __forceinline__ f32x4 uload_next() {
-        const f32x4 u = *(const __attribute__((address_space(1))) f32x4*)(ucur + ulane);
-        ucur += 1024;
-        asm volatile("" : "+s"(ucur));
-        return u;
-    }
 };
 // One memory instruction beside an f32 MFMA is free, two per gap kept up cost up to an MFMA (tools/microbench/
 // mfma_f32_fillers.hip; an isolated pair costs far less: DESIGN 3.1), and vector-ALU work is cheapest in blocks; so a step (two xi = 8 MFMAs) has fixed slots, pinned by
@@ -149,41 +93,6 @@ template <int NG_> struct Ctx {
 //     M1 | B(xi1) | M3 | VALU block of transform slice p, slice LDS op 1 | M5 | B(xi0') | M7 | DMA piece p, slice LDS ops 2, 3, ring reload
 #define PNP_SLOT() __builtin_amdgcn_sched_barrier(0)
 
-// patch row R of d buffer DPAR, in two halves; all ten floats are "used" (slice_valu) so that the reads stay one
-// conflict-free ds_read_b128 and two ds_read_b64 (narrowed to the six needed values they become three 4-way
-// bank-conflicting ds_read2_b32)
-template <int DPAR, int R, int HALF, typename CT> __device__ __forceinline__ void patch_load(CT& c) {
-    const lds_f* row = c.dsrc[DPAR] + R * PC;                    // 16-byte aligned
-    if (HALF == 0) { c.P.a = *(const lds_f2*)(row + 2); c.P.e = *(const lds_f2*)(row + 8); }
-    else c.P.m = *(const lds_f4*)(row + 4);
-}
-// The transform on the packed-f32 ALU (a v_pk_* beside f32 MFMAs costs what one plain instruction does).  Row pass of
-// B^T d B: the loaded row holds (d1, d2) and (d3, d4) as aligned register pairs, so
-//     (t2, t1) = (d3, d4) - 4 (d1, d2)      (sd, t3) = (d3, d4) - (d1, d2)
-//     (V1, V2) = (t1 + t2, t1 - t2)         (V3, V4) = (t3 + 2 sd, t3 - 2 sd)        [half-selects: op_sel, hand-written]
-// and V0, V5 (their inputs straddle the pairs) stay scalar: 8 instructions instead of 12.  The results are kept as the
-// pairs (V0, V5), (V1, V2), (V3, V4), so the column pass runs on whole pairs: 12 packed instructions for two columns.
-__device__ __forceinline__ f32x2 pk_sum_diff(f32x2 a) {             // (a.lo + a.hi, a.hi - a.lo)
-    f32x2 r;
-    asm("v_pk_add_f32 %0, %1, %1 op_sel:[0,1] op_sel_hi:[1,0] neg_hi:[0,1]" : "=v"(r) : "v"(a));
-    return r;
-}
-__device__ __forceinline__ f32x2 pk_hi_pm_2lo(f32x2 a) {            // (a.hi + 2 a.lo, a.hi - 2 a.lo)
-    f32x2 r;
-    asm("v_pk_fma_f32 %0, %1, 2.0, %1 op_sel:[0,0,1] op_sel_hi:[0,0,1] neg_hi:[1,0,0]" : "=v"(r) : "v"(a));
-    return r;
-}
-// B^T of F(4,3) on six pairs
-__device__ __forceinline__ void bt6_pk(f32x2 q0, f32x2 q1, f32x2 q2, f32x2 q3, f32x2 q4, f32x2 q5, f32x2 (&v)[6]) {
-    const f32x2 t1 = q4 - 4.f * q2, t2 = q3 - 4.f * q1;
-    const f32x2 t3 = q4 - q2, sd = q3 - q1;
-    v[0] = 4.f * q0 + (q4 - 5.f * q2);
-    v[1] = t1 + t2;
-    v[2] = t1 - t2;
-    v[3] = 2.f * sd + t3;
-    v[4] = t3 - 2.f * sd;
-    v[5] = 4.f * q1 + (q5 - 5.f * q3);
-}
 // transform slice SL of the patch (d buffer DPAR -> V buffer DPAR): 0..5 = row transforms, 6 / 8 / 10 = column transforms of
 // the column pairs (0, 5) / (1, 2) / (3, 4); the six value pairs wait in P.v for their write slots
 constexpr int col_pair(int sl) { return (sl - 6) / 2; }
@@ -397,21 +306,13 @@ __global__ __launch_bounds__(256, 1) void k_mid_wino44(const float* __restrict__
                                                        unsigned long long* __restrict__ stamps = nullptr, int tile0 = 0,
                                                        const float* __restrict__ wlast = nullptr, float* __restrict__ part = nullptr) {
     using G = Geo<NG>;
-    constexpr int TR = G::TR, PR = G::PR, PLANE = G::PLANE, DBUF = G::DBUF, PPW = G::PPW, VPL = G::VPL, VBUF = G::VBUF;
+    constexpr int PLANE = G::PLANE, DBUF = G::DBUF, PPW = G::PPW, VPL = G::VPL, VBUF = G::VBUF;
     static_assert(!(FL && LEAKY), "the fused last layer is built for the ReLU net");
     __shared__ __attribute__((aligned(16))) float lds[G::LDS_FLOATS + fl_lds_floats<NG, FL>()];
     const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // Regions are numbered in units of 8 x 64 pixels (`tile0` + ...) whatever the form: a 4 x 64 region u is sub-row u & 1 of
-    // unit tile0 + (u >> 1), so that a launch of the one-row form can take over the units a two-row launch left (the last,
-    // partly filled wave of workgroups: wino44_layer)
-    const int tiles_x = W / TC, units_per_img = tiles_x * (H / 8);
-    auto region = [&](int u, int& b, int& ty0, int& tx0) {
-        const int t = tile0 + (NG == 2 ? u : u >> 1);
-        b = t / units_per_img;
-        const int t2 = t - b * units_per_img;
-        ty0 = (t2 / tiles_x) * 8 + (NG == 2 ? 0 : 4 * (u & 1));
-        tx0 = (t2 % tiles_x) * TC;
-    };
+    // regions are numbered in units of 8 x 64 pixels from `tile0`, so that a launch of the one-row form can take over the units
+    // a two-row launch left (the last, partly filled wave of workgroups: wino44_layer)
+    const Regions<NG> region(H, W, tile0);
 
     float bv[4];
 #pragma unroll
@@ -426,43 +327,21 @@ __global__ __launch_bounds__(256, 1) void k_mid_wino44(const float* __restrict__
     // V item: [k-row wv][block tc][block row g][k-step j] -- the 64 lanes of a wave write 64 consecutive dwords per point
     const int v_off = NG == 2 ? wv * 64 + tc * 4 + g * 2 + j : wv * 32 + tc * 2 + j;
 
-    // DMA piece descriptors: bits 0..26 = element offset of the lane's 16-byte chunk inside the chunk's 8 channel planes,
-    // bit 27 = padding, bits 28..31 = which image edge would put the chunk outside
+    // halo front end (wino44_common.h): this wave's DMA pieces, and the DMA state of tile t (t == ntiles: "none", zeros)
     unsigned pdesc[PPW];
 #pragma unroll
-    for (int i = 0; i < PPW; ++i) {
-        const int q = (wv + 4 * i) * 64 + lane;
-        const int c = q / (PLANE / 4), r = q - c * (PLANE / 4);
-        const int ry = r / 18, cx4 = 4 * (r - ry * 18);
-        const unsigned edge = (ry == 0 ? 1u : 0u) | (ry == PR - 1 ? 2u : 0u) | (cx4 == 0 ? 4u : 0u) | (cx4 == TC + 4 ? 8u : 0u);
-        pdesc[i] = r < PR * 18 ? ((unsigned)((c * H + ry) * W + cx4) | (edge << 28)) : DUMMY;
-    }
+    for (int i = 0; i < PPW; ++i) pdesc[i] = piece_desc<NG>(wv, i, lane, H, W);
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) float*)lds;
-    // DMA state of a tile t (t == ntiles: "none", every lane reads zeros): the buffer base of its chunk 0 and, per piece, the
-    // lane's byte offset (or an offset beyond num_records) -- the same for all chunks of the tile, whose bases are
-    // chunk_bytes apart
-    struct TileDma { size_t base; unsigned voff[PPW]; };
     const size_t chunk_bytes = (size_t)KC * H * W * 4;
     auto tile_dma = [&](int t) {
-        TileDma td;
+        TileDma<NG> td;
         int b, ty0, tx0;
         region(t, b, ty0, tx0);
         td.base = (size_t)in + 4 * ((((size_t)b * C) * H + ty0 - 1) * (size_t)W + tx0 - 4);
-        const unsigned bad = t < ntiles ? ((((ty0 == 0 ? 1u : 0u) | (ty0 + TR == H ? 2u : 0u) | (tx0 == 0 ? 4u : 0u) | (tx0 + TC == W ? 8u : 0u)) << 28) | DUMMY)
-                                        : 0xFFFFFFFFu;
+        const unsigned bad = bad_mask<NG>(t, ntiles, ty0, tx0, H, W);
 #pragma unroll
-        for (int i = 0; i < PPW; ++i) td.voff[i] = (pdesc[i] & bad) == 0u ? 4u * (pdesc[i] & 0x07FFFFFFu) : 0x80000000u;
+        for (int i = 0; i < PPW; ++i) td.voff[i] = piece_voff(pdesc[i], bad);
         return td;
-    };
-    auto chunk_rsrc = [&](const TileDma& td, int k) {
-        const size_t base = td.base + (size_t)k * chunk_bytes;
-        i32x4 rs;
-        rs.x = (int)(unsigned)base; rs.y = (int)(unsigned)(base >> 32) & 0xFFFF; rs.z = (int)0x80000000u; rs.w = 0x00020000;
-        return rs;
-    };
-    // piece i of a chunk -> d buffer `buf`
-    auto dma_piece = [&](const TileDma& td, i32x4 rs, int buf, int i) {
-        dma_piece_asm(td.voff[i], rs, lds0 + 4u * (unsigned)(buf * DBUF + (wv + 4 * i) * 256));
     };
 
     float* const dbuf = lds;
@@ -489,11 +368,11 @@ __global__ __launch_bounds__(256, 1) void k_mid_wino44(const float* __restrict__
     if constexpr (FL)
         for (int i = tid; i < C * 9; i += 256) flw[i] = wlast[i];
     {
-        const TileDma td0 = tile_dma(tile < limit ? tile : ntiles);
+        const TileDma<NG> td0 = tile_dma(tile < limit ? tile : ntiles);
 #pragma unroll
-        for (int i = 0; i < PPW; ++i) dma_piece(td0, chunk_rsrc(td0, 0), 0, i);
+        for (int i = 0; i < PPW; ++i) dma_piece(td0, chunk_rsrc(td0, 0, chunk_bytes), lds0, wv, 0, i);
 #pragma unroll
-        for (int i = 0; i < PPW; ++i) dma_piece(td0, chunk_rsrc(td0, 1), 1, i);
+        for (int i = 0; i < PPW; ++i) dma_piece(td0, chunk_rsrc(td0, 1, chunk_bytes), lds0, wv, 1, i);
 #pragma unroll
         for (int i = 0; i < URING; ++i) c.ur[i] = c.uload_next();
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -510,13 +389,13 @@ __global__ __launch_bounds__(256, 1) void k_mid_wino44(const float* __restrict__
         region(tile, b, ty0, tx0);
         const int ntile = tile + tw_.step < limit ? tile + tw_.step : ntiles;      // ntiles = "none": zeros
 
-        const TileDma cur = tile_dma(tile), nxt = tile_dma(ntile);
+        const TileDma<NG> cur = tile_dma(tile), nxt = tile_dma(ntile);
         all_chunks<STAMP, VAR>(c, [&](auto kc) {
             constexpr int K = decltype(kc)::value;
             // chunk K + 2 (of this tile, or chunk 0 / 1 of the next) -> the d buffer chunk K was transformed from
-            const TileDma& td = K + 2 < NCH ? cur : nxt;
-            const i32x4 rs = chunk_rsrc(td, (K + 2) % NCH);
-            return [&, rs](int piece) { dma_piece(td, rs, K & 1, piece); };
+            const TileDma<NG>& td = K + 2 < NCH ? cur : nxt;
+            const i32x4 rs = chunk_rsrc(td, (K + 2) % NCH, chunk_bytes);
+            return [&, rs](int piece) { dma_piece(td, rs, lds0, wv, K & 1, piece); };
         }, t_wait, std::make_integer_sequence<int, NCH>{});
 
         unsigned long long te = 0;
@@ -670,8 +549,6 @@ size_t wino44_layer_bytes() { return (size_t)4 * w44::NCH * 18 * 64 * 4 * sizeof
 // w_mid [n_mid][64][64][3][3] (BN folded) -> upack[l][wv][chunk k][xi pair p][lane][e]:  xi = 2 p + (e >> 1), k-step j = e & 1,
 // U_xi[cout = 16 wv + (lane & 15)][cin = 8 k + 2 (lane >> 4) + j],  U = G g G^T,  xi = 6 xi_y + xi_x
 void wino44_pack(const float* w_mid, int n_mid, void* out_) {
-    static const double G[6][3] = {{1.0 / 4, 0, 0}, {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
-                                   {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6}, {0, 0, 1}};
     float* out = (float*)out_;
     for (int l = 0; l < n_mid; ++l)
         for (int wv = 0; wv < 4; ++wv)
@@ -680,14 +557,12 @@ void wino44_pack(const float* w_mid, int n_mid, void* out_) {
                     for (int j = 0; j < 2; ++j) {
                         const int cout = 16 * wv + (lane & 15), cin = w44::KC * k + 2 * (lane >> 4) + j;
                         const float* g = w_mid + (((size_t)l * w44::C + cout) * w44::C + cin) * 9;
-                        for (int xy = 0; xy < 6; ++xy)
-                            for (int xx = 0; xx < 6; ++xx) {
-                                double u = 0;
-                                for (int dy = 0; dy < 3; ++dy)
-                                    for (int dx = 0; dx < 3; ++dx) u += G[xy][dy] * G[xx][dx] * (double)g[dy * 3 + dx];
-                                const int xi = 6 * xy + xx, p = xi >> 1, e = 2 * (xi & 1) + j;
-                                out[((((size_t)(l * 4 + wv) * w44::NCH + k) * 18 + p) * 64 + lane) * 4 + e] = (float)u;
-                            }
+                        float u[36];
+                        w44c::filter_u(g, u);
+                        for (int xi = 0; xi < 36; ++xi) {
+                            const int p = xi >> 1, e = 2 * (xi & 1) + j;
+                            out[((((size_t)(l * 4 + wv) * w44::NCH + k) * 18 + p) * 64 + lane) * 4 + e] = u[xi];
+                        }
                     }
 }
 
@@ -750,12 +625,7 @@ int wino44_debug_clock(const ConvLayerArgs& a, int reps, std::vector<double>& cy
         return PNP_OK;
     }, h, cycles, ticks);
     if (rc != PNP_OK) return rc;
-    if (getenv("PNP_DEBUG_STAMPS")) {
-        double wsum = 0, esum = 0, rsum = 0;
-        for (int i = 0; i < grid; ++i) { wsum += (double)(h[4 * i + 2] & 0xFFFFFFFFull); rsum += (double)(h[4 * i + 2] >> 32); esum += h[4 * i + 3]; }
-        fprintf(stderr, "[k_mid_wino44 stamps] mean cycles per WG: chunk-end wait + barrier %.0f  epilogue %.0f  (mode 6: steps 0..5 of the chunks %.0f)\n",
-                wsum / grid, esum / grid, rsum / grid);
-    }
+    if (getenv("PNP_DEBUG_STAMPS")) w44c::print_stamp_summary("k_mid_wino44", h, grid);
     return PNP_OK;
 }
 

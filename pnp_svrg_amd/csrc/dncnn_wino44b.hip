@@ -20,10 +20,12 @@
 //     24 KB input buffers of the LDS-DMA is 156 KB of the CU's 160 KB.  A thread transforms one (channel, block) patch as
 //     before; the terms are the high halves of (v, v - v1, v - v1 - v2), paired with the neighbour channel's by v_permlane16_swap
 //     and stored four bytes at a time (put_pair).
-// Everything else (persistent workgroups in the XCD-aware order, LDS-DMA of the halo planes with range-checked padding, the
-// patch transform on the packed-f32 ALU, the chunk pipeline MFMA(k) | transform(k + 1) | DMA(k + 2)) is as in dncnn_wino44.hip.
+// Everything else is as in dncnn_wino44.hip: the LDS-DMA of the halo planes with range-checked padding, the patch transform on
+// the packed-f32 ALU and the weight cursor ARE the fp32 kernel's (wino44_common.h, the two-block-row geometry); the persistent
+// workgroups in the XCD-aware order and the chunk pipeline MFMA(k) | transform(k + 1) | DMA(k + 2) are built the same way.
 #include "common.h"
 #include "wino44b.h"
+#include "wino44_common.h"
 #include "tilewalk.h"
 #include <vector>
 #include <utility>
@@ -34,18 +36,10 @@ namespace pnp {
 namespace w44b {
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using f32x2 = __attribute__((ext_vector_type(2))) float;
+using namespace w44c;              // transform arithmetic, halo front end, Patch, weight cursor, C / TC / PC / KC / NCH
 
-constexpr int C = 64;
-constexpr int TC = 64;                                // region: 8 rows x 64 columns = 2 x 16 blocks of 4 x 4
-constexpr int TR = 8, PR = TR + 2;
-constexpr int PC = 72;                                // LDS row: image columns [tx0 - 4, tx0 + 68)
-constexpr int KC = 8;                                 // input channels per chunk
-constexpr int NCH = C / KC;
-constexpr int PLANE = 768;                            // PR x 72 payload + pad (0 mod 64 dwords)
-constexpr int DBUF = KC * PLANE;                      // floats per input buffer: 24 DMA pieces of 1 KiB
-constexpr int PPW = DBUF / 256 / 4;                   // 6 pieces per wave
+constexpr int NG = 2;                                 // region: 8 rows x 64 columns = 2 x 16 blocks of 4 x 4
+constexpr int PLANE = HaloGeo<NG>::PLANE, DBUF = HaloGeo<NG>::DBUF, PPW = HaloGeo<NG>::PPW;
 constexpr int VPLB = 512;                             // bytes per plane of a point: [32 blocks][8 channels] bf16
 constexpr int VXI = 3 * VPLB;                         // bytes per transform point
 constexpr int VBUF = 36 * VXI;                        // 55 296 bytes
@@ -53,34 +47,9 @@ constexpr int D_BYTES = 2 * DBUF * 4;                 // 49 152
 constexpr int LDS_BYTES = D_BYTES + 2 * VBUF + 256;   // + the layer's 64 biases: 160 000 of 163 840
 constexpr int URING = 20;                             // weight loads in flight per lane
 constexpr int NLOADS = NCH * 18 * 2;                  // weight loads per region and lane
-constexpr unsigned DUMMY = 1u << 27;                  // descriptor flag: padding chunk of a plane
 
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) float lds_f;
-typedef __attribute__((address_space(3))) f32x2 lds_f2;
-typedef __attribute__((address_space(3))) f32x4 lds_f4;
 typedef __attribute__((address_space(3))) char lds_c;
 typedef __attribute__((address_space(3))) unsigned short lds_u16;
-
-// B^T of F(4,3) applied to six values
-__device__ __forceinline__ void bt6(float d0, float d1, float d2, float d3, float d4, float d5, float (&v)[6]) {
-    const float t1 = __builtin_fmaf(-4.f, d2, d4), t2 = __builtin_fmaf(-4.f, d1, d3);
-    const float t3 = d4 - d2, sd = d3 - d1;
-    v[0] = __builtin_fmaf(4.f, d0, __builtin_fmaf(-5.f, d2, d4));
-    v[1] = t1 + t2;
-    v[2] = t1 - t2;
-    v[3] = __builtin_fmaf(2.f, sd, t3);
-    v[4] = __builtin_fmaf(-2.f, sd, t3);
-    v[5] = __builtin_fmaf(4.f, d1, __builtin_fmaf(-5.f, d3, d5));
-}
-// A^T of F(4,3) applied to six values
-template <typename T> __device__ __forceinline__ void at6(T m0, T m1, T m2, T m3, T m4, T m5, T (&y)[4]) {
-    const T s12 = m1 + m2, d12 = m1 - m2, s34 = m3 + m4, d34 = m3 - m4;
-    y[0] = (m0 + s12) + s34;
-    y[1] = 2.f * d34 + d12;
-    y[2] = 4.f * s34 + s12;
-    y[3] = (8.f * d34 + d12) + m5;
-}
 
 // hand-issued MFMAs (see dncnn_wino44.hip: left to the compiler the 288 accumulators do not stay put); the three MFMAs of a
 // point are one accumulation chain on the same 16 registers, which the matrix pipe runs back to back
@@ -94,17 +63,7 @@ template <bool AG> __device__ __forceinline__ void mfma_first(f32x16& acc, f32x4
 }
 constexpr bool in_agpr(int t) { return t < 16; }
 
-// one 1-KiB piece global -> LDS: lane's 16 bytes from rsrc.base + voff (an offset beyond num_records reads zeros)
-__device__ __forceinline__ void dma_piece_asm(unsigned voff, i32x4 rsrc, unsigned lds_byte_addr) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, 0 offen lds" :: "v"(voff), "s"(rsrc), "s"(lds_byte_addr) : "memory");
-}
-
-struct Patch {
-    f32x2 a; f32x4 m; f32x2 e;                                 // one patch row in flight: LDS columns 4tc + 2..3, 4..7, 8..9
-    f32x2 t[6][3];                                             // row transforms as register pairs: (V0, V5), (V1, V2), (V3, V4) of row r
-    f32x2 v[6];                                                // one transformed pair of columns on its way to the V image
-};
-struct Ctx {
+struct Ctx : WeightCursor {                                    // + the weight stream of this wave (ucur, ulane, uload_next)
     f32x16 acc[18];
     f32x4 ur[URING];
     Patch P;
@@ -113,42 +72,9 @@ struct Ctx {
     lds_c* vdst[2];                                            // where its 4-byte stores go in the two V buffers (put_pair)
     const lds_c* vsrcA[2];                                     // its B operands: plane b1 of the wave's first point, block lane & 31 ...
     const lds_c* vsrcB[2];                                     //   ... and plane b1 (lower half-wave) / b3 (upper) for the third MFMA
-    const __attribute__((address_space(1))) char* ucur;        // weight stream of this wave: scalar cursor (1 KiB per load) ...
-    unsigned ulane;                                            //   ... + the lane's 16 bytes
-    __device__ __forceinline__ f32x4 uload_next() {
-        const f32x4 u = *(const __attribute__((address_space(1))) f32x4*)(ucur + ulane);
-        ucur += 1024;
-        asm volatile("" : "+s"(ucur));
-        return u;
-    }
 };
 #define PNP_SLOT() __builtin_amdgcn_sched_barrier(0)
 
-template <int DPAR, int R, int HALF> __device__ __forceinline__ void patch_load(Ctx& c) {
-    const lds_f* row = c.dsrc[DPAR] + R * PC;                    // 16-byte aligned
-    if (HALF == 0) { c.P.a = *(const lds_f2*)(row + 2); c.P.e = *(const lds_f2*)(row + 8); }
-    else c.P.m = *(const lds_f4*)(row + 4);
-}
-__device__ __forceinline__ f32x2 pk_sum_diff(f32x2 a) {             // (a.lo + a.hi, a.hi - a.lo)
-    f32x2 r;
-    asm("v_pk_add_f32 %0, %1, %1 op_sel:[0,1] op_sel_hi:[1,0] neg_hi:[0,1]" : "=v"(r) : "v"(a));
-    return r;
-}
-__device__ __forceinline__ f32x2 pk_hi_pm_2lo(f32x2 a) {            // (a.hi + 2 a.lo, a.hi - 2 a.lo)
-    f32x2 r;
-    asm("v_pk_fma_f32 %0, %1, 2.0, %1 op_sel:[0,0,1] op_sel_hi:[0,0,1] neg_hi:[1,0,0]" : "=v"(r) : "v"(a));
-    return r;
-}
-__device__ __forceinline__ void bt6_pk(f32x2 q0, f32x2 q1, f32x2 q2, f32x2 q3, f32x2 q4, f32x2 q5, f32x2 (&v)[6]) {
-    const f32x2 t1 = q4 - 4.f * q2, t2 = q3 - 4.f * q1;
-    const f32x2 t3 = q4 - q2, sd = q3 - q1;
-    v[0] = 4.f * q0 + (q4 - 5.f * q2);
-    v[1] = t1 + t2;
-    v[2] = t1 - t2;
-    v[3] = 2.f * sd + t3;
-    v[4] = t3 - 2.f * sd;
-    v[5] = 4.f * q1 + (q5 - 5.f * q3);
-}
 // The exact three-way split of a transformed value: the high halves of v, r1 = v - hi(v) and r2 = r1 - hi(r1) (both differences are
 // exact; r2 has at most 8 significant bits left) are the bf16 terms.
 // A lane transforms ONE channel; 2-byte stores of single terms put four lanes on every LDS bank (the loop was bound by the LDS
@@ -424,13 +350,7 @@ __global__ __launch_bounds__(256, 1) void k_mid_wino44b(const float* __restrict_
     __shared__ __attribute__((aligned(16))) char lds[LDS_BYTES];
     const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int ch = wv & 1, xh = wv >> 1;                           // the wave's half of the output channels / of the transform points
-    const int tiles_x = W / TC, units_per_img = tiles_x * (H / 8);
-    auto region = [&](int t, int& b, int& ty0, int& tx0) {
-        b = t / units_per_img;
-        const int t2 = t - b * units_per_img;
-        ty0 = (t2 / tiles_x) * 8;
-        tx0 = (t2 % tiles_x) * TC;
-    };
+    const Regions<NG> region(H, W, 0);
     lds_c* const ldsp = (lds_c*)lds;
     lds_f* const bias_lds = (lds_f*)(ldsp + D_BYTES + 2 * VBUF);
     if (tid < C) bias_lds[tid] = bias[tid];
@@ -446,37 +366,21 @@ __global__ __launch_bounds__(256, 1) void k_mid_wino44b(const float* __restrict_
     const int n = lane & 31, h = lane >> 5;
     const unsigned st_off = 4u * (unsigned)((4 * h) * H * W + (4 * (n >> 4)) * W + 4 * (n & 15));
 
+    // halo front end (wino44_common.h): this wave's DMA pieces, and the DMA state of tile t (t == ntiles: "none", zeros)
     unsigned pdesc[PPW];
 #pragma unroll
-    for (int i = 0; i < PPW; ++i) {
-        const int q = (wv + 4 * i) * 64 + lane;
-        const int c = q / (PLANE / 4), r = q - c * (PLANE / 4);
-        const int ry = r / 18, cx4 = 4 * (r - ry * 18);
-        const unsigned edge = (ry == 0 ? 1u : 0u) | (ry == PR - 1 ? 2u : 0u) | (cx4 == 0 ? 4u : 0u) | (cx4 == TC + 4 ? 8u : 0u);
-        pdesc[i] = r < PR * 18 ? ((unsigned)((c * H + ry) * W + cx4) | (edge << 28)) : DUMMY;
-    }
+    for (int i = 0; i < PPW; ++i) pdesc[i] = piece_desc<NG>(wv, i, lane, H, W);
     const unsigned lds0 = (unsigned)(size_t)ldsp;
-    struct TileDma { size_t base; unsigned voff[PPW]; };
     const size_t chunk_bytes = (size_t)KC * H * W * 4;
     auto tile_dma = [&](int t) {
-        TileDma td;
+        TileDma<NG> td;
         int b, ty0, tx0;
         region(t, b, ty0, tx0);
         td.base = (size_t)in + 4 * ((((size_t)b * C) * H + ty0 - 1) * (size_t)W + tx0 - 4);
-        const unsigned bad = t < ntiles ? ((((ty0 == 0 ? 1u : 0u) | (ty0 + TR == H ? 2u : 0u) | (tx0 == 0 ? 4u : 0u) | (tx0 + TC == W ? 8u : 0u)) << 28) | DUMMY)
-                                        : 0xFFFFFFFFu;
+        const unsigned bad = bad_mask<NG>(t, ntiles, ty0, tx0, H, W);
 #pragma unroll
-        for (int i = 0; i < PPW; ++i) td.voff[i] = (pdesc[i] & bad) == 0u ? 4u * (pdesc[i] & 0x07FFFFFFu) : 0x80000000u;
+        for (int i = 0; i < PPW; ++i) td.voff[i] = piece_voff(pdesc[i], bad);
         return td;
-    };
-    auto chunk_rsrc = [&](const TileDma& td, int k) {
-        const size_t base = td.base + (size_t)k * chunk_bytes;
-        i32x4 rs;
-        rs.x = (int)(unsigned)base; rs.y = (int)(unsigned)(base >> 32) & 0xFFFF; rs.z = (int)0x80000000u; rs.w = 0x00020000;
-        return rs;
-    };
-    auto dma_piece = [&](const TileDma& td, i32x4 rs, int buf, int i) {
-        dma_piece_asm(td.voff[i], rs, lds0 + 4u * (unsigned)(buf * DBUF + (wv + 4 * i) * 256));
     };
 
     Ctx c;
@@ -493,11 +397,11 @@ __global__ __launch_bounds__(256, 1) void k_mid_wino44b(const float* __restrict_
     int tile = tw_.first;
     const int limit = tw_.limit < ntiles ? tw_.limit : ntiles;
     {
-        const TileDma td0 = tile_dma(tile < limit ? tile : ntiles);
+        const TileDma<NG> td0 = tile_dma(tile < limit ? tile : ntiles);
 #pragma unroll
-        for (int i = 0; i < PPW; ++i) dma_piece(td0, chunk_rsrc(td0, 0), 0, i);
+        for (int i = 0; i < PPW; ++i) dma_piece(td0, chunk_rsrc(td0, 0, chunk_bytes), lds0, wv, 0, i);
 #pragma unroll
-        for (int i = 0; i < PPW; ++i) dma_piece(td0, chunk_rsrc(td0, 1), 1, i);
+        for (int i = 0; i < PPW; ++i) dma_piece(td0, chunk_rsrc(td0, 1, chunk_bytes), lds0, wv, 1, i);
 #pragma unroll
         for (int i = 0; i < URING; ++i) c.ur[i] = c.uload_next();
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -515,12 +419,12 @@ __global__ __launch_bounds__(256, 1) void k_mid_wino44b(const float* __restrict_
         region(tile, b, ty0, tx0);
         const int ntile = tile + tw_.step < limit ? tile + tw_.step : ntiles;      // ntiles = "none": zeros
 
-        const TileDma cur = tile_dma(tile), nxt = tile_dma(ntile);
+        const TileDma<NG> cur = tile_dma(tile), nxt = tile_dma(ntile);
         all_chunks<STAMP, VAR>(c, [&](auto kc) {
             constexpr int K = decltype(kc)::value;
-            const TileDma& td = K + 2 < NCH ? cur : nxt;
-            const i32x4 rs = chunk_rsrc(td, (K + 2) % NCH);
-            return [&, rs](int piece) { dma_piece(td, rs, K & 1, piece); };
+            const TileDma<NG>& td = K + 2 < NCH ? cur : nxt;
+            const i32x4 rs = chunk_rsrc(td, (K + 2) % NCH, chunk_bytes);
+            return [&, rs](int piece) { dma_piece(td, rs, lds0, wv, K & 1, piece); };
         }, t_wait, t_rows, std::make_integer_sequence<int, NCH>{});
 
         unsigned long long te = 0;
@@ -570,8 +474,6 @@ size_t wino44b_layer_bytes() { return (size_t)4 * w44b::NLOADS * 64 * 8 * sizeof
 // half-wave (lane >> 5), with U = G g G^T evaluated in float64, rounded to fp32 (the fp32 kernel's value) and split by truncation
 void wino44b_pack(const float* w_mid, int n_mid, void* out_) {
     uint16_t* out = (uint16_t*)out_;
-    static const double G[6][3] = {{1.0 / 4, 0, 0}, {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
-                                   {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6}, {0, 0, 1}};
     auto bits = [](float f) { uint32_t u; memcpy(&u, &f, 4); return u; };
     auto flt = [](uint32_t u) { float f; memcpy(&f, &u, 4); return f; };
     for (int l = 0; l < n_mid; ++l)
@@ -579,25 +481,23 @@ void wino44b_pack(const float* w_mid, int n_mid, void* out_) {
             for (int cin = 0; cin < w44b::C; ++cin) {
                 const float* g = w_mid + (((size_t)l * w44b::C + cout) * w44b::C + cin) * 9;
                 const int ch = cout >> 5, r = cout & 31, k = cin / w44b::KC, e = cin % w44b::KC;
-                for (int xy = 0; xy < 6; ++xy)
-                    for (int xx = 0; xx < 6; ++xx) {
-                        double u = 0;
-                        for (int dy = 0; dy < 3; ++dy)
-                            for (int dx = 0; dx < 3; ++dx) u += G[xy][dy] * G[xx][dx] * (double)g[dy * 3 + dx];
-                        const float a = (float)u;
-                        const uint32_t u1 = bits(a) & 0xFFFF0000u;
-                        const float r1 = a - flt(u1);
-                        const uint32_t u2 = bits(r1) & 0xFFFF0000u;
-                        const float r2 = r1 - flt(u2);
-                        const uint16_t a1 = (uint16_t)(u1 >> 16), a2 = (uint16_t)(u2 >> 16), a3 = (uint16_t)(bits(r2) >> 16);
-                        const int xi = 6 * xy + xx, xh = xi / 18, t = xi % 18, wave = 2 * xh + ch;
-                        const int es = (e + 4 * xh) & 7;                          // points 18..35 keep their channels in the order 4..7, 0..3 (put_pair)
-                        const size_t base = ((((size_t)(l * 4 + wave) * w44b::NCH + k) * 18 + t) * 2) * 512;
-                        out[base + (size_t)r * 8 + es] = a1;                      // operand 0, lower half-wave
-                        out[base + (size_t)(32 + r) * 8 + es] = a2;               // operand 0, upper half-wave
-                        out[base + 512 + (size_t)r * 8 + es] = a3;                // operand 1, lower
-                        out[base + 512 + (size_t)(32 + r) * 8 + es] = a1;         // operand 1, upper
-                    }
+                float u[36];
+                w44c::filter_u(g, u);
+                for (int xi = 0; xi < 36; ++xi) {
+                    const float a = u[xi];
+                    const uint32_t u1 = bits(a) & 0xFFFF0000u;
+                    const float r1 = a - flt(u1);
+                    const uint32_t u2 = bits(r1) & 0xFFFF0000u;
+                    const float r2 = r1 - flt(u2);
+                    const uint16_t a1 = (uint16_t)(u1 >> 16), a2 = (uint16_t)(u2 >> 16), a3 = (uint16_t)(bits(r2) >> 16);
+                    const int xh = xi / 18, t = xi % 18, wave = 2 * xh + ch;
+                    const int es = (e + 4 * xh) & 7;                          // points 18..35 keep their channels in the order 4..7, 0..3 (put_pair)
+                    const size_t base = ((((size_t)(l * 4 + wave) * w44b::NCH + k) * 18 + t) * 2) * 512;
+                    out[base + (size_t)r * 8 + es] = a1;                      // operand 0, lower half-wave
+                    out[base + (size_t)(32 + r) * 8 + es] = a2;               // operand 0, upper half-wave
+                    out[base + 512 + (size_t)r * 8 + es] = a3;                // operand 1, lower
+                    out[base + 512 + (size_t)(32 + r) * 8 + es] = a1;         // operand 1, upper
+                }
             }
 }
 
@@ -642,12 +542,7 @@ int wino44b_debug_clock(const ConvLayerArgs& a, int reps, std::vector<double>& c
         return PNP_OK;
     }, h, cycles, ticks);
     if (rc != PNP_OK) return rc;
-    if (getenv("PNP_DEBUG_STAMPS")) {
-        double wsum = 0, esum = 0, rsum = 0;
-        for (int i = 0; i < grid; ++i) { wsum += (double)(h[4 * i + 2] & 0xFFFFFFFFull); rsum += (double)(h[4 * i + 2] >> 32); esum += h[4 * i + 3]; }
-        fprintf(stderr, "[k_mid_wino44 stamps] mean cycles per WG: chunk-end wait + barrier %.0f  epilogue %.0f  (mode 6: steps 0..5 of the chunks %.0f)\n",
-                wsum / grid, esum / grid, rsum / grid);
-    }
+    if (getenv("PNP_DEBUG_STAMPS")) w44c::print_stamp_summary("k_mid_wino44b", h, grid);
     return PNP_OK;
 }
 

@@ -13,25 +13,16 @@ this script verifies on the ISA of every k_svrg_iter instantiation that
     python tools/check_fused_isa.py [listing.s]        (without argument: compiles csmri_fused.hip with hipcc -S first)
 
 Also prints, per kernel, the spill traffic between workgroup barriers (where the register pressure bites)."""
-import os
 import re
-import subprocess
 import sys
-import tempfile
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import hip_listing
+
 VMEM = ('global_', 'buffer_', 'scratch_', 'flat_')
 
 
 def listing(path=None, defines=()):
-    if path:
-        return open(path).read()
-    src = os.path.join(ROOT, 'pnp_svrg_amd', 'csrc', 'csmri_fused.hip')
-    with tempfile.TemporaryDirectory() as td:
-        out = os.path.join(td, 'f.s')
-        subprocess.run(['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-Wno-unused-function', *defines, '-x', 'hip',
-                        '--cuda-device-only', '-S', src, '-o', out], check=True, cwd=os.path.dirname(src), stderr=subprocess.DEVNULL)
-        return open(out).read()
+    return open(path).read() if path else hip_listing.listing('csmri_fused.hip', defines)
 
 
 def regs_of(text):

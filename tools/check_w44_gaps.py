@@ -7,10 +7,10 @@ W44_EPILOGUE_BEGIN and classifies what stands between an MFMA and the next one (
 LDS instructions (ds_*), vector-memory instructions (global_* / buffer_*) and vector-ALU instructions (other v_*).
 Prints the histogram per instantiation.  Exit code 0 = every NG = 2 instantiation has 1152 MFMAs, no gap with more than
 one memory instruction and no gap that mixes vector-ALU work with a memory instruction."""
-import collections, os, re, subprocess, sys, tempfile
+import collections, re, sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, 'pnp_svrg_amd', 'csrc', 'dncnn_wino44.hip')
+from hip_listing import listing
+
 MFMAS = {1: 576, 2: 1152}                                   # per region and wave: 36 points x NG block rows x 16 k-steps
 
 
@@ -60,12 +60,7 @@ def analyse(asm_text):
 
 
 def compile_asm():
-    with tempfile.TemporaryDirectory() as td:
-        out = os.path.join(td, 'w44.s')
-        subprocess.run(['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-mllvm',
-                        '-pragma-unroll-threshold=200000', '-fno-slp-vectorize', '-x', 'hip', '--cuda-device-only', '-S', SRC, '-o', out],
-                       check=True, stderr=subprocess.DEVNULL)
-        return open(out).read()
+    return listing('dncnn_wino44.hip')
 
 
 def main():

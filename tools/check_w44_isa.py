@@ -5,10 +5,10 @@ of an accumulator register next to an MFMA (live-range split, spill) reads the r
 script compiles the file to assembly and verifies, for every instantiation of the kernel, that between the first MFMA and
 the end of the tile loop NO instruction other than an MFMA reads or writes an accumulator register outside the epilogue
 (marked W44_EPILOGUE_BEGIN / _END, which starts with the required wait states).  Exit code 0 = clean."""
-import os, re, subprocess, sys, tempfile
+import re, sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, 'pnp_svrg_amd', 'csrc', 'dncnn_wino44.hip')
+from hip_listing import listing
+
 REG = re.compile(r'\b([av])(\d+)\b|\b([av])\[(\d+):(\d+)\]')
 
 
@@ -76,15 +76,7 @@ def check(asm_text):
 
 
 def main():
-    if len(sys.argv) > 1:
-        text = open(sys.argv[1]).read()
-    else:
-        with tempfile.TemporaryDirectory() as td:
-            out = os.path.join(td, 'w44.s')
-            subprocess.run(['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-mllvm',
-                            '-pragma-unroll-threshold=200000', '-fno-slp-vectorize', '-x', 'hip', '--cuda-device-only', '-S', SRC, '-o', out],
-                           check=True, stderr=subprocess.DEVNULL)
-            text = open(out).read()
+    text = open(sys.argv[1]).read() if len(sys.argv) > 1 else listing('dncnn_wino44.hip')
     kernels, problems, checked = check(text)
     print(f'{kernels} kernel instantiation(s) checked, {len(problems)} problem(s)')
     for name in checked:

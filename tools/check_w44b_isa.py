@@ -6,10 +6,10 @@ registers (16 in AGPRs, 2 in VGPRs), each the destination of exactly 24 MFMAs (8
 moved shows up as extra tuples with fewer; (b) from a tuple's first MFMA to the epilogue marker (behind which the wait states
 stand) no instruction other than an MFMA names one of its registers -- BEFORE its first MFMA of a region hipcc may, and does,
 park spilled values in a not-yet-live accumulator AGPR; (c) m0 is used by the LDS-DMA statements only.  Exit code 0 = clean."""
-import os, re, subprocess, sys, tempfile
+import re, sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, 'pnp_svrg_amd', 'csrc', 'dncnn_wino44b.hip')
+from hip_listing import listing
+
 REG = re.compile(r'\b([av])(\d+)\b|\b([av])\[(\d+):(\d+)\]')
 
 
@@ -72,15 +72,7 @@ def check(asm_text):
 
 
 def main():
-    if len(sys.argv) > 1:
-        text = open(sys.argv[1]).read()
-    else:
-        with tempfile.TemporaryDirectory() as td:
-            out = os.path.join(td, 'w44b.s')
-            subprocess.run(['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-mllvm',
-                            '-pragma-unroll-threshold=200000', '-fno-slp-vectorize', '-x', 'hip', '--cuda-device-only', '-S', SRC, '-o', out],
-                           check=True, stderr=subprocess.DEVNULL)
-            text = open(out).read()
+    text = open(sys.argv[1]).read() if len(sys.argv) > 1 else listing('dncnn_wino44b.hip')
     kernels, problems = check(text)
     print(f'{kernels} kernel instantiation(s) checked, {len(problems)} problem(s)')
     for p in problems[:40]:
