@@ -208,6 +208,49 @@ int pnp_pr_grad_batch(const void* A, const void* w, const void* y, const int32_t
 int pnp_pr_spectral_apply(const void* A, const void* v, const void* y, int M, int N, int dtype, double scale,
                           void* workspace, void* out, void* stream);
 
+/* ------------------------------------------------------------------ Deblur / PR sweep batches generated on the device
+ * The same stream for the other two problems (tags 0-2 keep the meaning above; state_k and key_k(i) are unchanged), so that a
+ * caller can restate a generated Deblur or phase-retrieval batch from this header alone:
+ *   measurement noise (k = 1, 2): indexed by the measurement index m: u1 = (key_1(m) + 1) * 2^-32, u2 = key_2(m) * 2^-32,
+ *                     n(m) = sqrt(-2 ln u1) * cos(2 pi u2), Box-Muller in double for both dtypes;
+ *   PR matrix (k = 3, 4): indexed by the pair index j = (m*N + n) >> 1: r = sqrt(-2 ln u1(key_3(j))), element m*N + n of
+ *                     A [M][N] is r * cos(2 pi u2(key_4(j))) when m*N + n is even and r * sin(2 pi u2(key_4(j))) when odd (both
+ *                     Box-Muller outputs of one pair, u1 and u2 formed as above), in double, rounded once to `dtype`; M*N <= 2^32,
+ *                     otherwise PNP_ERR_ARG;
+ *   Deblur Xinit (k = 5): Xinit(i) = key_5(i) * 2^-32 in [0, 1)  (np.random.uniform(0, 1, N), problems/DeblurSR.py:57), rounded
+ *                     to `dtype`;
+ *   sigma           : sigma = sqrt(||Y0||_2 * snr_fac / H / W) (the norm, not its square), the sum of squares of the stored Y0
+ *                     taken in double in a fixed order per item;  Y = Y0 + sigma * n, one more rounding to `dtype`.
+ * An f32 and an f64 call hold the same problem up to the final rounding.  Per item [batch] device arrays image_idx (int32),
+ * snr_fac (double), seed, id (uint64) and the image set as in pnp_csmri_generate.  No allocation, no synchronisation; an item's
+ * outputs do not depend on the batch size or on its index in the batch.
+ *
+ * pnp_deblur_generate (problems/DeblurSR.py:38-57 per item) on an existing plan (identity or bilinear): xrec [batch][H*W] =
+ * images[image_idx[b]]; Y [batch][M] = S B xrec (the plan's forward pass) + sigma * n; xinit [batch][H*W]; sigma [batch] double.  */
+int pnp_deblur_generate(pnp_deblur_plan* plan, const void* images, int n_images, const int32_t* image_idx,
+                        const double* snr_fac, const uint64_t* seed, const uint64_t* id, void* xrec, void* Y, void* xinit,
+                        double* sigma, void* stream);
+/* pnp_pr_generate (problems/PR.py:26-34 per item) for `batch` items sharing M and N = H*W: A [batch][M][N] from tags 3 and 4;
+ * xrec [batch][N]; Y [batch][M] = |A xrec| (row dot products accumulated in double) + sigma * n; sigma [batch] double.        */
+int pnp_pr_generate(const void* images, int n_images, const int32_t* image_idx, const double* snr_fac, const uint64_t* seed,
+                    const uint64_t* id, int H, int W, int M, int batch, int dtype, void* A, void* xrec, void* Y, double* sigma,
+                    void* stream);
+/* PhaseRetrieval.spec_init and the normalisation after it (problems/PR.py:50-63, :38) for `batch` items at once: the power
+ * iteration v <- A^T (Y o (A v)) / M from v = 2 * ones, lead = max(v), v <- v / lead, until the reference's rule
+ * |lead - lead_old| > 1e-5 and ||v - v_old||_2 > 1e-5 fails.  A and Y are read in `dtype`; v, lead, the change norm and every
+ * sum are double for both dtypes.  The rule is evaluated per item ON THE DEVICE after every step; an item whose rule has failed
+ * is frozen (its v, lead and iteration count are not touched again), so its result does not depend on the batch.  Then
+ * xinit [batch][N] = minmax( sqrt(lead) * v / ||v|| * ||xrec|| ), rounded to `dtype`.
+ * This is a SETUP call, the one exception to "no synchronisation": steps are launched `check_every` at a time, after which ONE
+ * int ("is any item active") is read back with a stream synchronisation; it cannot be captured in a hipGraph.  It stops after
+ * max_iters steps at the latest.  iters_out [batch] int32: steps taken per item; active_out [batch] int32: nonzero for an item
+ * that had not met its rule when max_iters was reached (the caller decides what that means; xinit is written regardless).
+ * workspace: pnp_pr_spectral_workspace_bytes(M, N, batch) bytes, 8-byte aligned.                                              */
+size_t pnp_pr_spectral_workspace_bytes(int M, int N, int batch);
+int pnp_pr_spectral_init_batch(const void* A, const void* Y, const void* xrec, int M, int N, int batch, int dtype,
+                               int max_iters, int check_every, void* workspace, void* xinit, int32_t* iters_out,
+                               int32_t* active_out, void* stream);
+
 /* ------------------------------------------------------------------ prox / noise estimate
  * estimate_sigma(z0, multichannel=True, average_sigmas=True) (algorithms/pnp_svrg.py:71):
  * per-column db2 MAD, mean over columns.  sigma_out: [batch] (dtype).                    */

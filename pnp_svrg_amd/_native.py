@@ -46,6 +46,10 @@ SIGNATURES = {
     'pnp_pr_grad': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _d, _vp, _vp, _vp]),
     'pnp_pr_grad_batch': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _d, _vp, _vp, _vp]),
     'pnp_pr_spectral_apply': (_i, [_vp, _vp, _vp, _i, _i, _i, _d, _vp, _vp, _vp]),
+    'pnp_deblur_generate': (_i, [_vp, _vp, _i] + [_vp] * 9),
+    'pnp_pr_generate': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    'pnp_pr_spectral_workspace_bytes': (_sz, [_i, _i, _i]),
+    'pnp_pr_spectral_init_batch': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'pnp_sigma_est': (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     'pnp_prox_tv': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _d, _d, _vp, _vp, _vp, _vp]),
     'pnp_prox_wavelet2d': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _d, _d, _vp, _vp, _vp, _vp]),

@@ -18,6 +18,7 @@
 // minibatch mask and the scaling).
 #include "fft.h"
 #include "draw.h"
+#include "deblur_plan.h"
 #include <vector>
 #include <cmath>
 
@@ -169,14 +170,6 @@ __global__ void k_csr(const T* __restrict__ y, const int32_t* __restrict__ rowpt
 
 using namespace pnp;
 
-struct pnp_deblur_plan {
-    int n, N, NL, batch, dtype, M;            // N = n*n = H*W; M = number of measurements
-    void *tw_line, *tw_big, *FB;              // [n], [N], [N] complex
-    void *w0, *r0, *r1;                       // complex [batch][N]; real [batch][N] x2
-    // optional bilinear operator
-    int32_t *g_idx, *a_rowptr, *a_col;
-    void *g_w, *a_val, *down;                 // [M][4], [nnz], real [batch][M]
-};
 
 namespace {
 // real [batch][N] -> Y[k1][b] (complex, work buffer w0)

@@ -44,6 +44,34 @@ class _BatchBase:
             # np.random.choice(..., replace=False) raises the same way (problems/problem.py:110-117, CSMRI.py:66-74)
             raise ValueError(f"Cannot take a larger sample than population when 'replace=False' (mini_batch_size {mb} > {self.max_mb})")
 
+    @staticmethod
+    def upload_images(images, H=256, W=256, dtype=torch.float32, device='cuda'):
+        """The image set of `generate`, each image min-max normalised in float64 (sweep._norm01), as one [n, H, W] device tensor."""
+        xs = []
+        for img in images:
+            x = np.asarray(img, np.float64)
+            if x.shape != (H, W):
+                raise ValueError(f'image of shape {x.shape}: generate needs {H} x {W} images')
+            xs.append((x - x.min()) / (x.max() - x.min()))
+        return torch.from_numpy(np.stack(xs)).to(device, dtype).contiguous()
+
+    @classmethod
+    def _generate_inputs(cls, images, items, H, W, dtype, device):
+        """What every `generate` starts from: the image set on the device and the per-item [B] parameter vectors of the
+        counter-based stream (image_idx int32, snr_fac float64, seed, id as int64 holding the 64-bit values)."""
+        ops.require_gpu()
+        if not isinstance(images, torch.Tensor):
+            images = cls.upload_images(images, H, W, dtype, device)
+        if images.dtype != dtype or tuple(images.shape[1:]) != (H, W):
+            raise ValueError(f'image set of dtype {images.dtype}, shape {tuple(images.shape)}: generate needs [n, {H}, {W}] {dtype}')
+        if len(items) < 1 or any(not 0 <= it['image'] < images.shape[0] for it in items):
+            raise ValueError('generate needs at least one item and image indices inside the image set')
+        u64 = lambda v: np.array([int(x) & (2 ** 64 - 1) for x in v], np.uint64).view(np.int64)
+        par = [np.array([it['image'] for it in items], np.int32),
+               np.array([10.0 ** (-np.float64(it['snr']) / 10) for it in items], np.float64),
+               u64([it['seed'] for it in items]), u64([it['id'] for it in items])]
+        return images, [torch.from_numpy(a).to(images.device) for a in par]
+
     def psnr_init(self):
         """rounded PSNR of Xinit per problem (problems/problem.py:33-35)."""
         sse = ops.sse(self.xinit, self.xrec).cpu().numpy()
@@ -115,17 +143,6 @@ class CsmriBatch(_BatchBase):
     @mask_np.setter
     def mask_np(self, m):
         self._mask_np = m
-
-    @staticmethod
-    def upload_images(images, H=256, W=256, dtype=torch.float32, device='cuda'):
-        """The image set of `generate`, each image min-max normalised in float64 (sweep._norm01), as one [n, H, W] device tensor."""
-        xs = []
-        for img in images:
-            x = np.asarray(img, np.float64)
-            if x.shape != (H, W):
-                raise ValueError(f'image of shape {x.shape}: generate needs {H} x {W} images')
-            xs.append((x - x.min()) / (x.max() - x.min()))
-        return torch.from_numpy(np.stack(xs)).to(device, dtype).contiguous()
 
     @classmethod
     def generate(cls, images, items, H=256, W=256, dtype=torch.float32, device='cuda'):
@@ -224,6 +241,25 @@ class DeblurBatch(_BatchBase):
         self.xinit = torch.from_numpy(np.ascontiguousarray(xinit, np.float64)).to(device, dtype).reshape(B, H, W)
         self.Y = torch.from_numpy(np.ascontiguousarray(Y, np.float64)).to(device, dtype).reshape(B, self.M)
         self._tmp = None
+
+    @classmethod
+    def generate(cls, images, items, H=256, W=256, dtype=torch.float32, kernel='Minimal', scale_percent=100, device='cuda'):
+        """The problems of `items` (dicts of sweep.make_items; their alpha is NOT read: the operator comes from `kernel` and
+        `scale_percent`) generated ON THE DEVICE from the counter-based stream of include/pnp_hip.h (pnp_deblur_generate):
+        Y = S B x + noise, Xinit uniform in [0, 1) -- problems/DeblurSR.py:38-57 per item, NOT NumPy's streams.  images: a list of
+        H x W arrays, or the tensor `upload_images` made of them.  Also sets `sigma` ([B] float64, device)."""
+        from .problems import _deblur_taps
+        from .sweep import _minimal_kernel
+        images, par = cls._generate_inputs(images, items, H, W, dtype, device)
+        self = cls.__new__(cls)
+        self.B, self.H, self.W, self.N, self.dtype = len(items), H, W, H * W, dtype
+        self.device = images.device
+        self.plan = ops.DeblurPlan(H, W, self.B, dtype, _minimal_kernel(H, W, kernel), bilinear=_deblur_taps(H, W, scale_percent))
+        self.M = self.max_mb = self.plan.M
+        o = self.plan.generate(images, *par)
+        self.xrec, self.xinit, self.Y, self.sigma = o['xrec'], o['xinit'], o['Y'], o['sigma']
+        self._tmp = None
+        return self
 
     @classmethod
     def from_problems(cls, probs, dtype=torch.float32, device='cuda'):
@@ -331,6 +367,33 @@ class PrBatch(_BatchBase):
         self._ws = torch.empty(B * N.lib().pnp_pr_workspace_elems(self.M, self.N), dtype=dtype, device=device)
         self._tmp = None
         self._mb = None
+
+    @classmethod
+    def generate(cls, images, items, H, W, M, dtype=torch.float32, max_iters=1000, check_every=8, device='cuda'):
+        """The problems of `items` (dicts of sweep.make_items; their alpha is NOT read: `M` is the number of measurements)
+        generated ON THE DEVICE from the counter-based stream of include/pnp_hip.h: the Gaussian A in HBM, Y = |A x| + noise
+        (pnp_pr_generate) and the spectral initialisation of all items at once with the stopping rule evaluated per item on the
+        device (pnp_pr_spectral_init_batch; one host synchronisation per `check_every` steps) -- problems/PR.py:26-63 per item,
+        NOT NumPy's streams.  Also sets `sigma` ([B] float64, device) and `spec_iters` ([B] int array: power-iteration steps per
+        item).  Raises ValueError naming the items that have not met the rule after `max_iters` steps."""
+        from . import _native as N
+        images, par = cls._generate_inputs(images, items, H, W, dtype, device)
+        self = cls.__new__(cls)
+        self.B, self.H, self.W, self.N, self.dtype = len(items), H, W, H * W, dtype
+        self.device = images.device
+        self.M = self.max_mb = int(M)
+        o = ops.pr_generate(images, *par, self.M)
+        self.xrec, self.A, self.Y, self.sigma = o['xrec'], o['A'], o['Y'], o['sigma']
+        self.xinit, iters, active = ops.pr_spectral_init_batch(self.A, self.Y, self.xrec, max_iters, check_every)
+        self.spec_iters = iters.cpu().numpy().astype(np.int64)
+        late = np.flatnonzero(active.cpu().numpy())
+        if late.size:
+            raise ValueError(f'spectral initialisation: items {[items[j]["id"] for j in late]} (batch positions {late.tolist()}) '
+                             f'still active after max_iters = {max_iters} steps')
+        self._ws = torch.empty(self.B * N.lib().pnp_pr_workspace_elems(self.M, self.N), dtype=dtype, device=self.device)
+        self._tmp = None
+        self._mb = None
+        return self
 
     @classmethod
     def from_problems(cls, probs, dtype=torch.float32, device='cuda'):

@@ -442,6 +442,60 @@ class DeblurPlan:
         N.call('pnp_deblur_forward', self._h, _p(x), _p(out), _stream())
         return out
 
+    def generate(self, images, image_idx, snr_fac, seed, item_id):
+        """pnp_deblur_generate: the B problems of this plan generated on the device from the counter-based stream of
+        include/pnp_hip.h.  images: [n, H, W] of the plan's dtype (normalised); per item device vectors image_idx (int32),
+        snr_fac (float64, 10^(-snr/10)), seed, item_id (int64 holding the 64-bit values).  Returns a dict of device tensors:
+        xrec [B, H, W], Y [B, M], xinit [B, H, W], sigma [B] (float64)."""
+        B, dt, dev = self.B, self.dtype, images.device
+        assert images.dtype == dt and images.dim() == 3 and tuple(images.shape[1:]) == (self.H, self.W) and images.is_contiguous()
+        _check_item_vectors(B, image_idx, snr_fac, seed, item_id)
+        o = dict(xrec=torch.empty((B, self.H, self.W), dtype=dt, device=dev), Y=torch.empty((B, self.M), dtype=dt, device=dev),
+                 xinit=torch.empty((B, self.H, self.W), dtype=dt, device=dev), sigma=torch.empty(B, dtype=torch.float64, device=dev))
+        N.call('pnp_deblur_generate', self._h, _p(images), images.shape[0], _p(image_idx), _p(snr_fac), _p(seed), _p(item_id),
+               _p(o['xrec']), _p(o['Y']), _p(o['xinit']), _p(o['sigma']), _stream())
+        return o
+
+
+def _check_item_vectors(B, image_idx, snr_fac, seed, item_id):
+    for t, d in ((image_idx, torch.int32), (snr_fac, torch.float64), (seed, torch.int64), (item_id, torch.int64)):
+        assert t.dtype == d and tuple(t.shape) == (B,)
+
+
+def pr_generate(images, image_idx, snr_fac, seed, item_id, M):
+    """pnp_pr_generate: B phase-retrieval problems with M measurements each generated on the device from the counter-based
+    stream of include/pnp_hip.h.  images: [n, H, W] (normalised; its dtype is the problems'); per item device vectors as in
+    DeblurPlan.generate.  Returns a dict of device tensors: A [B, M, H*W], xrec [B, H, W], Y [B, M], sigma [B] (float64)."""
+    require_gpu()
+    B, dt, dev = image_idx.shape[0], images.dtype, images.device
+    assert images.dim() == 3 and images.is_contiguous()
+    _check_item_vectors(B, image_idx, snr_fac, seed, item_id)
+    H, W = int(images.shape[1]), int(images.shape[2])
+    if int(M) * H * W > 2 ** 32:
+        raise ValueError(f'M * N = {int(M) * H * W} > 2^32: the matrix stream has a 32-bit pair index')
+    o = dict(A=torch.empty((B, int(M), H * W), dtype=dt, device=dev), xrec=torch.empty((B, H, W), dtype=dt, device=dev),
+             Y=torch.empty((B, int(M)), dtype=dt, device=dev), sigma=torch.empty(B, dtype=torch.float64, device=dev))
+    N.call('pnp_pr_generate', _p(images), images.shape[0], _p(image_idx), _p(snr_fac), _p(seed), _p(item_id), H, W, int(M), B,
+           _DT[dt], _p(o['A']), _p(o['xrec']), _p(o['Y']), _p(o['sigma']), _stream())
+    return o
+
+
+def pr_spectral_init_batch(A, Y, xrec, max_iters=1000, check_every=8):
+    """pnp_pr_spectral_init_batch: PhaseRetrieval.spec_init + min-max normalisation (PR.py:50-63, :38) of B problems at once,
+    the stopping rule evaluated per item on the device; one host synchronisation per `check_every` steps.  A [B, M, N],
+    Y [B, M], xrec [B, ...] of one dtype.  Returns (xinit like xrec, iters int32 [B], active int32 [B]): `active` is nonzero
+    for an item that had not met its rule after `max_iters` steps."""
+    require_gpu()
+    B, M, Nn = A.shape
+    assert Y.dtype == A.dtype and xrec.dtype == A.dtype and tuple(Y.shape) == (B, M) and xrec.numel() == B * Nn
+    ws = torch.empty(N.lib().pnp_pr_spectral_workspace_bytes(M, Nn, B) // 8, dtype=torch.float64, device=A.device)
+    xinit = torch.empty_like(xrec)
+    iters = torch.empty(B, dtype=torch.int32, device=A.device)
+    active = torch.empty(B, dtype=torch.int32, device=A.device)
+    N.call('pnp_pr_spectral_init_batch', _p(A), _p(Y), _p(xrec), M, Nn, B, _DT[A.dtype], int(max_iters), int(check_every), _p(ws),
+           _p(xinit), _p(iters), _p(active), _stream())
+    return xinit, iters, active
+
 
 def pr_grad(A, w, y, rows=None, scale=1.0, workspace=None, out=None):
     """scale * A_sel^T(((|A_sel w| - y_sel)/|A_sel w|) o A_sel w); A [M,N], rows int32 [nsel] or None."""

@@ -303,6 +303,19 @@ def _bilinear_taps(iava, dims):
     return idx.astype(np.int32), wts, a_rowptr, a_col, a_val
 
 
+def _deblur_taps(H, W, scale_percent, eps=1e-10):
+    """The down-sampler of a Deblur problem (DeblurSR.py:39-40, 95-108): None for scale_percent == 100 (identity), else the
+    bilinear taps on the reference's sampling grid."""
+    if scale_percent == 100:
+        return None
+    lrH, lrW = int(H * scale_percent / 100), int(W * scale_percent / 100)
+    ptsH = np.linspace(eps, H - (1 + eps), lrH)
+    ptsW = np.linspace(eps, W - (1 + eps), lrW)
+    meshW, meshH = np.meshgrid(ptsH, ptsW)                            # (sic) as DeblurSR.py:102
+    iava = np.vstack([meshH.ravel(), meshW.ravel()])
+    return _bilinear_taps(iava, (H, W))
+
+
 class Deblur(Problem):
     """reference problems/DeblurSR.py:16-147 with forward model and gradients on the MI355X."""
     eps = 1e-10
@@ -351,13 +364,7 @@ class Deblur(Problem):
         self.B = np.asarray(self.B).ravel() / self.N
 
     def _generate_bop(self):
-        taps = None
-        if self.scale_percent != 100:
-            ptsH = np.linspace(self.eps, self.H - (1 + self.eps), self.lrH)
-            ptsW = np.linspace(self.eps, self.W - (1 + self.eps), self.lrW)
-            meshW, meshH = np.meshgrid(ptsH, ptsW)                    # (sic) as DeblurSR.py:102
-            iava = np.vstack([meshH.ravel(), meshW.ravel()])
-            taps = _bilinear_taps(iava, (self.H, self.W))
+        taps = _deblur_taps(self.H, self.W, self.scale_percent, self.eps)
         self.Bop = taps                                               # forward taps + CSR adjoint (None = Identity)
         self.plan = ops.DeblurPlan(self.H, self.W, 1, self.dtype, self.B, bilinear=taps)
 

@@ -162,9 +162,14 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
     1/M0 and minibatch thresholds); Deblur / PR items are grouped by alpha, which fixes the operator's shape (scale_percent =
     100 alpha; num_meas = alpha H W).
     seeding='generator': per-item data from a Generator stream keyed by the item, built on the host, minibatches drawn on the device;
-    seeding='device'   : (problem='csmri') per-item data generated ON THE DEVICE from the counter-based stream of include/pnp_hip.h
-                         (engine.CsmriBatch.generate; the normalised image set is uploaded once per runner), minibatches drawn on
-                         the device and graph replay as with 'generator'; a third stream: not the data of the other two modes;
+    seeding='counter'  : per-item data generated ON THE DEVICE from the counter-based stream of include/pnp_hip.h, for all three
+                         problems (engine.CsmriBatch.generate / DeblurBatch.generate / PrBatch.generate; the normalised image set
+                         is uploaded once per runner): Deblur items with scale_percent = deblur_scale_percent(alpha), values other
+                         than 100 (super-resolution) included; PR items with A generated in HBM and the spectral initialisation
+                         batched on the device.  Minibatches drawn on the device and graph replay as with 'generator'; a third
+                         stream: not the data of the other two modes;
+    seeding='device'   : the older, CSMRI-only spelling of 'counter' (the same code path and the same data, bit for bit); any other
+                         problem raises ValueError;
     seeding='legacy'   : per item exactly the reference's RNG use -- np.random.seed(item seed), the problem constructor's draws
                          in its order, np.random.seed(run_seed), then the loop's draws in ITS order (one select_mb per inner
                          iteration; pnp_saga: one select_mb for the table, then select_mb + np.random.choice(hist_size, 1) per
@@ -181,7 +186,7 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
     if seeding == 'device' and problem != 'csmri':
         raise ValueError(f"seeding='device' is supported for problem='csmri' only (got {problem!r}); use 'generator' or 'legacy'")
     mb, dkw = mini_batch_size, dict(denoiser_kwargs or {})
-    dev_images = []                                              # seeding='device': the image set in HBM, uploaded on first use
+    dev_images = []                                              # seeding='counter' / 'device': the image set in HBM, uploaded on first use
 
     def group_key(it):
         return None if problem == 'csmri' else it['alpha']
@@ -224,6 +229,14 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
             xs.append(x); As.append(A); Ys.append(Y); xi.append((x0 - x0.min()) / (x0.max() - x0.min()))
         return E.PrBatch(np.stack(xs), np.stack(As), np.stack(Ys), np.stack(xi), dtype=dtype)
 
+    def build_counter(dev_imgs, chunk):
+        a = chunk[0]['alpha']
+        if problem == 'csmri':
+            return E.CsmriBatch.generate(dev_imgs, chunk, H, W, dtype)
+        if problem == 'deblur':
+            return E.DeblurBatch.generate(dev_imgs, chunk, H, W, dtype, kernel=kernel, scale_percent=deblur_scale_percent(a))
+        return E.PrBatch.generate(dev_imgs, chunk, H, W, pr_num_meas(a, H, W), dtype)
+
     def build_legacy(chunk):
         """-> (batch, draws): per item the reference's constructor on its seed, then the loop's RNG draws on run_seed."""
         probs, draws = [], []
@@ -258,10 +271,10 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
                 self.batch, draws = build_legacy(chunk)
                 self.idx_d = torch.from_numpy(np.stack([d[0] for d in draws], axis=1)).to(self.batch.device) if algorithm != 'gd' else None
                 self.rs = np.stack([d[1] for d in draws], axis=1)                  # [n_inner][B]
-            elif seeding == 'device':
+            elif seeding in ('device', 'counter'):
                 if not dev_images:
                     dev_images.append(E.CsmriBatch.upload_images(images, H, W, dtype))
-                self.batch, self.idx_d, self.rs = E.CsmriBatch.generate(dev_images[0], chunk, H, W, dtype), None, None
+                self.batch, self.idx_d, self.rs = build_counter(dev_images[0], chunk), None, None
             else:
                 self.batch, self.idx_d, self.rs = build_generator(chunk), None, None
             kw = dict(seed=chunk[0]['id'] + 1)
