@@ -169,6 +169,58 @@ int pnp_csmri_svrg_outer_iteration(pnp_csmri_plan* plan, void* z, void* w, void*
                                    double sigma_modifier, double fallback_sigma, const void* xrec, double* sse_log,
                                    int log_row0, int n_log, void* sigma_out, void* stream);
 
+/* ------------------------------------------------------------------ per-problem hyper-parameters: the _pp forms
+ * A hyper-parameter grid runs as ONE batch when every problem of the batch carries its own step size, minibatch size and
+ * denoiser strength (sweep.grid_search(batch_trials=True)).  ONE naming scheme: an entry point `name_pp` is `name` with,
+ * behind each scalar that has a per-problem form, a nullable DEVICE array of [batch] values -- `x_pp` (double) or `mb_vec`
+ * (int32).  NULL means "the scalar holds for every problem"; with every such array NULL a _pp call computes what the plain
+ * call computes.  The kernels read the arrays with plain loads of wave-uniform values (one workgroup owns one problem) and
+ * convert each value exactly as the host converts the scalar of the plain call -- the same order of the 1/N scale, the cast to
+ * `dtype` and the product with alpha_vec[b] -- so problem b of a _pp call equals, bit for bit, problem b of the plain call made
+ * with that problem's scalars.  The plain entry points and their kernels are unchanged.
+ *
+ * Draws: problem b takes its own mb_vec[b] smallest keys (at or above its number of candidates: all of them), and its stream
+ * absorbs draw_id[b] in place of the batch index b: state = mix64(mix64(mix64(seed) + step) + draw_id[b]).  draw_id == NULL:
+ * the batch index.  Keys, fast path and radix fallback are those of the plain draw.  mb_vec is required; the call does not
+ * synchronise, so it cannot read mb_vec: entries must be >= 1 (the Python front end checks its host copy and raises; an entry
+ * below 1 that reaches the kernel draws as 1, never out of bounds).                                              */
+int pnp_csmri_draw_thresholds_pp(pnp_csmri_plan* plan, const uint32_t* bitsT, const int32_t* mb_vec, const uint32_t* draw_id,
+                                 uint64_t seed, uint32_t step0, int nsteps, const uint32_t* step_dev, void* mbd,
+                                 uint32_t* selbits, void* stream);
+int pnp_draw_thresholds_pp(int M, int batch, const int32_t* mb_vec, const uint32_t* draw_id, uint64_t seed, uint32_t step0,
+                           int nsteps, const uint32_t* step_dev, void* mbd, void* stream);
+/* pnp_csmri_grad_sel with per-problem alpha and gamma: problem b uses (alpha_pp ? alpha_pp[b] : alpha) * alpha_vec[b] and
+ * (gamma_pp ? gamma_pp[b] : gamma).  On the one-kernel route (f32 256 x 256 bits form, large batches) a per-problem gamma
+ * needs c1 beside c2 (PNP_ERR_ARG otherwise).                                                                     */
+int pnp_csmri_grad_sel_pp(pnp_csmri_plan* plan, const void* a, const void* b, const uint8_t* selT, const uint32_t* bitsT,
+                          const void* yh, const void* YT, double alpha, const double* alpha_pp, const void* alpha_vec,
+                          double beta, const void* c1, double gamma, const double* gamma_pp, const void* c2, void* out,
+                          void* stream);
+/* The three one-kernel calls.  svrg_step: alpha_pp, gamma_pp, sigma_modifier_pp.  svrg_outer_step: lr_pp (the step uses
+ * -lr_pp[b]), sigma_modifier_pp.  svrg_outer_iteration: lr_pp, mb_vec (the inner iterations use -lr_pp[b] / mb_vec[b], the
+ * quotient taken in double as the plain call takes it on the host), sigma_modifier_pp.                               */
+int pnp_csmri_svrg_step_pp(pnp_csmri_plan* plan, const void* a, const void* b, const uint32_t* bitsT, double alpha,
+                           const double* alpha_pp, const void* alpha_vec, double beta, const void* c1, double gamma,
+                           const double* gamma_pp, const void* c2, void* out, int denoise, double sigma_modifier,
+                           const double* sigma_modifier_pp, double fallback_sigma, const void* xrec, double* sse_out,
+                           void* sigma_out, void* stream);
+int pnp_csmri_svrg_outer_step_pp(pnp_csmri_plan* plan, const void* z, const uint32_t* mask_bitsT, const void* yh,
+                                 const void* alpha_vec, double lr, const double* lr_pp, void* w_out, void* mu_out, void* out,
+                                 int denoise, double sigma_modifier, const double* sigma_modifier_pp, double fallback_sigma,
+                                 const void* xrec, double* sse_out, void* sigma_out, void* stream);
+int pnp_csmri_svrg_outer_iteration_pp(pnp_csmri_plan* plan, void* z, void* w, void* mu, const uint32_t* mask_bitsT, const void* yh,
+                                      const void* alpha_vec, const uint32_t* selbits, int T2, double lr, const double* lr_pp,
+                                      int mini_batch_size, const int32_t* mb_vec, double sigma_modifier,
+                                      const double* sigma_modifier_pp, double fallback_sigma, const void* xrec, double* sse_log,
+                                      int log_row0, int n_log, void* sigma_out, void* stream);
+/* pnp_prox_tv / pnp_prox_wavelet2d with sigma used = sigma_est * (sigma_modifier_pp ? sigma_modifier_pp[b] : sigma_modifier). */
+int pnp_prox_tv_pp(const void* z_in, void* z_out, int H, int W, int batch, int dtype, const void* sigma_in,
+                   double sigma_modifier, const double* sigma_modifier_pp, double fallback_sigma, const void* xrec,
+                   double* sse_out, void* sigma_out, void* stream);
+int pnp_prox_wavelet2d_pp(const void* z_in, void* z_out, int H, int W, int batch, int dtype, const void* sigma_in,
+                          double sigma_modifier, const double* sigma_modifier_pp, double fallback_sigma, const void* xrec,
+                          double* sse_out, void* sigma_out, void* stream);
+
 /* ------------------------------------------------------------------ Deblur / super-resolution
  * Replaces problems/DeblurSR.py:119-147: 1-D circular blur of the raveled image via a length-H*W FFT
  * (spectrum of the kernel computed once at plan creation), optional 4-tap bilinear down-sampler

@@ -76,6 +76,16 @@ SIGNATURES = {
     'pnp_indicator_from_indices': (_i, [_vp, _i, _i, _i, _vp, _vp]),
     'pnp_saga_table_update': (_i, [_vp, _vp, _vp, _vp, _vp, _d, _d, _sz, _i, _vp]),
     'pnp_axpbypcz': (_i, [_d, _vp, _d, _vp, _d, _vp, _vp, _sz, _i, _vp]),
+    # per-problem (_pp) forms: a nullable [batch] device array behind each scalar that has one
+    'pnp_csmri_draw_thresholds_pp': (_i, [_vp, _vp, _vp, _vp, ctypes.c_uint64, ctypes.c_uint32, _i, _vp, _vp, _vp, _vp]),
+    'pnp_draw_thresholds_pp': (_i, [_i, _i, _vp, _vp, ctypes.c_uint64, ctypes.c_uint32, _i, _vp, _vp, _vp]),
+    'pnp_csmri_grad_sel_pp': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _vp, _vp, _d, _vp, _d, _vp, _vp, _vp, _vp]),
+    'pnp_csmri_svrg_step_pp': (_i, [_vp, _vp, _vp, _vp, _d, _vp, _vp, _d, _vp, _d, _vp, _vp, _vp, _i, _d, _vp, _d, _vp, _vp, _vp, _vp]),
+    'pnp_csmri_svrg_outer_step_pp': (_i, [_vp, _vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp, _i, _d, _vp, _d, _vp, _vp, _vp, _vp]),
+    'pnp_csmri_svrg_outer_iteration_pp': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _d, _vp, _i, _vp, _d, _vp, _d, _vp, _vp, _i,
+                                               _i, _vp, _vp]),
+    'pnp_prox_tv_pp': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _d, _vp, _d, _vp, _vp, _vp, _vp]),
+    'pnp_prox_wavelet2d_pp': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _d, _vp, _d, _vp, _vp, _vp, _vp]),
     'pnp_legacy_choice': (_i, [_vp, ctypes.POINTER(ctypes.c_int), _vp, _i, _i, _vp, _vp]),
 }
 

@@ -279,6 +279,17 @@ extern "C" int pnp_csmri_draw_thresholds(pnp_csmri_plan* p, const uint32_t* bits
     return PNP_OK;
 }
 
+extern "C" int pnp_csmri_draw_thresholds_pp(pnp_csmri_plan* p, const uint32_t* bitsT, const int32_t* mb_vec, const uint32_t* draw_id,
+                                            uint64_t seed, uint32_t step0, int nsteps, const uint32_t* step_dev, void* mbd,
+                                            uint32_t* selbits, void* stream) {
+    PNP_CHECK_ARG(p && bitsT && mb_vec && mbd, "null argument");
+    PNP_CHECK_ARG(nsteps >= 1 && nsteps <= 65535, "need 1 <= nsteps <= 65535");
+    k_draw_thr_pp<true><<<dim3(p->batch, nsteps), 256, 0, (hipStream_t)stream>>>(bitsT, p->H, p->W, mb_vec, draw_id, seed, step0, step_dev,
+                                                                                (MbDesc*)mbd, selbits, draw_fast_path());
+    PNP_CHECK_LAUNCH();
+    return PNP_OK;
+}
+
 extern "C" int pnp_csmri_sel_from_thresholds(pnp_csmri_plan* p, const uint32_t* bitsT, const void* mbd, uint8_t* selT,
                                              void* stream) {
     PNP_CHECK_ARG(p && bitsT && mbd && selT, "null argument");
@@ -319,18 +330,20 @@ namespace pnp {
 int csmri_fused_launch(int batch, const void* twtab, const void* a, const void* b, const uint32_t* bitsT, const void* yh,
                        double alpha, const void* alpha_vec, double beta, const void* c1, double gamma, const void* c2, void* out,
                        int mode, double sigma_modifier, double fallback_sigma, const void* xrec, double* sse_out, void* sigma_out,
-                       void* stream, void* w_out = nullptr, void* mu_out = nullptr);
+                       void* stream, void* w_out = nullptr, void* mu_out = nullptr, const double* alpha_pp = nullptr,
+                       const double* gamma_pp = nullptr, const double* sm_pp = nullptr);
 int csmri_fused_outer_launch(int batch, const void* twtab, void* z, void* w, void* mu, const uint32_t* mask_bits, const void* yh,
                              const void* alpha_vec, const uint32_t* selbits, int T2, double lr, int mini_batch_size,
                              double sigma_modifier, double fallback_sigma, const void* xrec, double* sse_log, int log_row0, int n_log,
-                             void* sigma_out, void* stream);
+                             void* sigma_out, void* stream, const double* lr_pp = nullptr, const int32_t* mb_vec = nullptr,
+                             const double* sm_pp = nullptr);
 }
 
 namespace {
 template <typename T, int RA, int LA>
 int run_grad(pnp_csmri_plan* p, const void* a, const void* b, const uint8_t* selT, const uint32_t* bitsT,
              const void* yh, const void* YT, double alpha, const void* alpha_vec, double beta, const void* c1, double gamma, const void* c2,
-             void* out, hipStream_t s) {
+             void* out, hipStream_t s, const double* alpha_pp, const double* gamma_pp) {
     constexpr int G = FftSmem<T, RA, LA>::G;
     const int H = p->H, W = p->W;
     cx<T>* work = (cx<T>*)p->work;
@@ -344,16 +357,21 @@ int run_grad(pnp_csmri_plan* p, const void* a, const void* b, const uint8_t* sel
     else
         k_cols<T, RA, LA, SEL_BITS><<<cg, 256, 0, s>>>(work, nullptr, bitsT, (const cx<T>*)yh, (const cx<T>*)YT, tw, W);
     PNP_CHECK_LAUNCH();
-    k_rows_inv<T, RA, LA><<<dim3(H / (2 * G), p->batch), 256, 0, s>>>(work, tw, H, scale, (const T*)alpha_vec, (T)beta,
-                                                                 (const T*)c1, (T)gamma, (const T*)c2, (T*)out);
+    if (alpha_pp != nullptr || gamma_pp != nullptr)
+        k_rows_inv_pp<T, RA, LA><<<dim3(H / (2 * G), p->batch), 256, 0, s>>>(work, tw, H, scale, alpha_pp, 1.0 / ((double)H * (double)W),
+                                                                        (const T*)alpha_vec, (T)beta, (const T*)c1, (T)gamma, gamma_pp,
+                                                                        (const T*)c2, (T*)out);
+    else
+        k_rows_inv<T, RA, LA><<<dim3(H / (2 * G), p->batch), 256, 0, s>>>(work, tw, H, scale, (const T*)alpha_vec, (T)beta,
+                                                                     (const T*)c1, (T)gamma, (const T*)c2, (T*)out);
     PNP_CHECK_LAUNCH();
     return PNP_OK;
 }
 }  // namespace
 
-extern "C" int pnp_csmri_grad_sel(pnp_csmri_plan* p, const void* a, const void* b, const uint8_t* selT, const uint32_t* bitsT,
-                                  const void* yh, const void* YT, double alpha, const void* alpha_vec,
-                                  double beta, const void* c1, double gamma, const void* c2, void* out, void* stream) {
+static int grad_sel_impl(pnp_csmri_plan* p, const void* a, const void* b, const uint8_t* selT, const uint32_t* bitsT,
+                         const void* yh, const void* YT, double alpha, const double* alpha_pp, const void* alpha_vec,
+                         double beta, const void* c1, double gamma, const double* gamma_pp, const void* c2, void* out, void* stream) {
     PNP_CHECK_ARG(p && a && out, "null argument");
     PNP_CHECK_ARG(!(yh != nullptr && YT != nullptr), "pass the packed data term (yh) or the raw data (YT), not both");
     PNP_CHECK_ARG((selT != nullptr) != (bitsT != nullptr), "pass either an explicit selector (selT) or mask bits (bitsT)");
@@ -361,9 +379,9 @@ extern "C" int pnp_csmri_grad_sel(pnp_csmri_plan* p, const void* a, const void* 
     // (csmri_fused.hip; one workgroup per image, so it needs about a workgroup per CU to pay off)
     if (p->dtype == PNP_F32 && p->H == 256 && bitsT != nullptr && YT == nullptr && p->batch >= p->fused_min_batch)
         return csmri_fused_launch(p->batch, p->twtab, a, b, bitsT, yh, alpha, alpha_vec, beta, c1, gamma, c2, out, 2, 1.0, 0.0,
-                                  nullptr, nullptr, nullptr, stream);
+                                  nullptr, nullptr, nullptr, stream, nullptr, nullptr, alpha_pp, gamma_pp, nullptr);
     hipStream_t s = (hipStream_t)stream;
-#define PNP_CS_ARGS p, a, b, selT, bitsT, yh, YT, alpha, alpha_vec, beta, c1, gamma, c2, out, s
+#define PNP_CS_ARGS p, a, b, selT, bitsT, yh, YT, alpha, alpha_vec, beta, c1, gamma, c2, out, s, alpha_pp, gamma_pp
     if (p->dtype == PNP_F32) {
         if (p->NL == 16) return run_grad<float, 16, 16>(PNP_CS_ARGS);
         if (p->NL == 12) return run_grad<float, 8, 16>(PNP_CS_ARGS);
@@ -373,6 +391,19 @@ extern "C" int pnp_csmri_grad_sel(pnp_csmri_plan* p, const void* a, const void* 
     if (p->NL == 12) return run_grad<double, 8, 16>(PNP_CS_ARGS);
     return run_grad<double, 8, 8>(PNP_CS_ARGS);
 #undef PNP_CS_ARGS
+}
+
+extern "C" int pnp_csmri_grad_sel(pnp_csmri_plan* p, const void* a, const void* b, const uint8_t* selT, const uint32_t* bitsT,
+                                  const void* yh, const void* YT, double alpha, const void* alpha_vec,
+                                  double beta, const void* c1, double gamma, const void* c2, void* out, void* stream) {
+    return grad_sel_impl(p, a, b, selT, bitsT, yh, YT, alpha, nullptr, alpha_vec, beta, c1, gamma, nullptr, c2, out, stream);
+}
+
+extern "C" int pnp_csmri_grad_sel_pp(pnp_csmri_plan* p, const void* a, const void* b, const uint8_t* selT, const uint32_t* bitsT,
+                                     const void* yh, const void* YT, double alpha, const double* alpha_pp, const void* alpha_vec,
+                                     double beta, const void* c1, double gamma, const double* gamma_pp, const void* c2, void* out,
+                                     void* stream) {
+    return grad_sel_impl(p, a, b, selT, bitsT, yh, YT, alpha, alpha_pp, alpha_vec, beta, c1, gamma, gamma_pp, c2, out, stream);
 }
 
 extern "C" int pnp_csmri_grad(pnp_csmri_plan* p, const void* a, const void* b, const uint8_t* selT, const void* yh,
@@ -392,6 +423,19 @@ extern "C" int pnp_csmri_svrg_step(pnp_csmri_plan* p, const void* a, const void*
     PNP_CHECK_ARG(!(sse_out && !xrec), "sse_out needs xrec");
     return csmri_fused_launch(p->batch, p->twtab, a, b, bitsT, nullptr, alpha, alpha_vec, beta, c1, gamma, c2, out, denoise ? 0 : 1,
                               sigma_modifier, fallback_sigma, xrec, sse_out, sigma_out, stream);
+}
+
+extern "C" int pnp_csmri_svrg_step_pp(pnp_csmri_plan* p, const void* a, const void* b, const uint32_t* bitsT, double alpha,
+                                      const double* alpha_pp, const void* alpha_vec, double beta, const void* c1, double gamma,
+                                      const double* gamma_pp, const void* c2, void* out, int denoise, double sigma_modifier,
+                                      const double* sigma_modifier_pp, double fallback_sigma, const void* xrec, double* sse_out,
+                                      void* sigma_out, void* stream) {
+    PNP_CHECK_ARG(p && a && bitsT && out, "null argument");
+    PNP_CHECK_ARG(p->dtype == PNP_F32 && p->H == 256 && p->W == 256, "the one-kernel iteration exists for f32 plans of 256 x 256");
+    PNP_CHECK_ARG(!(sse_out && !xrec), "sse_out needs xrec");
+    return csmri_fused_launch(p->batch, p->twtab, a, b, bitsT, nullptr, alpha, alpha_vec, beta, c1, gamma, c2, out, denoise ? 0 : 1,
+                              sigma_modifier, fallback_sigma, xrec, sse_out, sigma_out, stream, nullptr, nullptr, alpha_pp, gamma_pp,
+                              sigma_modifier_pp);
 }
 
 // ---- the same with the outer-loop refresh folded in (first inner iteration of an outer iteration)
@@ -418,4 +462,33 @@ extern "C" int pnp_csmri_svrg_outer_iteration(pnp_csmri_plan* p, void* z, void* 
     PNP_CHECK_ARG(z != w && z != mu && w != mu, "z, w and mu must be buffers of their own");
     return csmri_fused_outer_launch(p->batch, p->twtab, z, w, mu, mask_bitsT, yh, alpha_vec, selbits, T2, lr, mini_batch_size,
                                     sigma_modifier, fallback_sigma, xrec, sse_log, log_row0, n_log, sigma_out, stream);
+}
+
+// ---- the per-problem forms of the two calls above (lr_pp, sigma_modifier_pp: double [batch]; mb_vec: int32 [batch]; NULL = the scalar)
+extern "C" int pnp_csmri_svrg_outer_step_pp(pnp_csmri_plan* p, const void* z, const uint32_t* mask_bitsT, const void* yh,
+                                            const void* alpha_vec, double lr, const double* lr_pp, void* w_out, void* mu_out, void* out,
+                                            int denoise, double sigma_modifier, const double* sigma_modifier_pp, double fallback_sigma,
+                                            const void* xrec, double* sse_out, void* sigma_out, void* stream) {
+    PNP_CHECK_ARG(p && z && mask_bitsT && yh && w_out && mu_out && out, "null argument");
+    PNP_CHECK_ARG(p->dtype == PNP_F32 && p->H == 256 && p->W == 256, "the one-kernel iteration exists for f32 plans of 256 x 256");
+    PNP_CHECK_ARG(!(sse_out && !xrec), "sse_out needs xrec");
+    PNP_CHECK_ARG(w_out != z && mu_out != z && w_out != mu_out && w_out != out && mu_out != out, "w_out and mu_out must be buffers of their own");
+    return csmri_fused_launch(p->batch, p->twtab, z, nullptr, mask_bitsT, yh, 1.0, alpha_vec, 1.0, z, -lr, nullptr, out,
+                              denoise ? 0 : 1, sigma_modifier, fallback_sigma, xrec, sse_out, sigma_out, stream, w_out, mu_out, nullptr,
+                              lr_pp, sigma_modifier_pp);
+}
+
+extern "C" int pnp_csmri_svrg_outer_iteration_pp(pnp_csmri_plan* p, void* z, void* w, void* mu, const uint32_t* mask_bitsT, const void* yh,
+                                                 const void* alpha_vec, const uint32_t* selbits, int T2, double lr, const double* lr_pp,
+                                                 int mini_batch_size, const int32_t* mb_vec, double sigma_modifier,
+                                                 const double* sigma_modifier_pp, double fallback_sigma, const void* xrec,
+                                                 double* sse_log, int log_row0, int n_log, void* sigma_out, void* stream) {
+    PNP_CHECK_ARG(p && z && w && mu && mask_bitsT && yh && alpha_vec && xrec && sse_log && sigma_out, "null argument");
+    PNP_CHECK_ARG(p->dtype == PNP_F32 && p->H == 256 && p->W == 256, "the one-kernel iteration exists for f32 plans of 256 x 256");
+    PNP_CHECK_ARG(T2 >= 1 && (T2 == 1 || selbits != nullptr) && (mb_vec != nullptr || mini_batch_size >= 1) && n_log >= 1 && log_row0 >= 0,
+                  "bad T2 / selbits / mini_batch_size / log");
+    PNP_CHECK_ARG(z != w && z != mu && w != mu, "z, w and mu must be buffers of their own");
+    return csmri_fused_outer_launch(p->batch, p->twtab, z, w, mu, mask_bitsT, yh, alpha_vec, selbits, T2, lr, mini_batch_size,
+                                    sigma_modifier, fallback_sigma, xrec, sse_log, log_row0, n_log, sigma_out, stream, lr_pp, mb_vec,
+                                    sigma_modifier_pp);
 }

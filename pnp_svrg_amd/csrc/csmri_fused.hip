@@ -764,6 +764,38 @@ __global__ __launch_bounds__(FT) void k_svrg_iter(const float* a, const float* b
                                       OUTER ? w_out + img : nullptr, OUTER ? mu_out + img : nullptr);
 }
 
+// Per-problem coefficients (the _pp entry points): alpha_pp, gamma_pp, sm_pp are DOUBLE [batch] arrays, each may be NULL (the
+// scalar argument then holds for every problem).  Plain loads of wave-uniform values, converted here exactly as the host converts
+// the scalars of k_svrg_iter: scale = (float)(alpha / N) (N = 2^16, so the product with 2^-16 is that quotient), then the
+// product with alpha_vec[b]; gamma and sigma_modifier by one cast.  OUTER: gamma_pp holds lr, the coefficient is -lr.
+template <int MODE, bool OUTER = false, int NOPS = 2>
+__global__ __launch_bounds__(FT) void k_svrg_iter_pp(const float* a, const float* b,
+                                                     const uint32_t* __restrict__ bitsT, const cx<float>* __restrict__ yh,
+                                                     const cx<float>* __restrict__ twtab,
+                                                     float scale, const float* __restrict__ alpha_vec, float beta, const float* c1,
+                                                     float gamma, const float* c2, float* out,
+                                                     float sigma_modifier, float fallback_sigma, const float* __restrict__ xrec,
+                                                     double* __restrict__ sse_out, float* __restrict__ sigma_out,
+                                                     float* w_out, float* mu_out, int stagger_n, int stagger_groups, int stagger_units,
+                                                     const double* __restrict__ alpha_pp, const double* __restrict__ gamma_pp,
+                                                     const double* __restrict__ sm_pp) {
+    startup_stagger(stagger_n, stagger_groups, stagger_units);
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    __shared__ FusedShared sh;
+    const int prob = blockIdx.x;
+    const size_t img = (size_t)prob * FN * FN;
+    if (alpha_pp != nullptr) scale = (float)(alpha_pp[prob] * (1.0 / ((double)FN * (double)FN)));
+    if (alpha_vec != nullptr) scale *= alpha_vec[prob];
+    if (gamma_pp != nullptr) gamma = OUTER ? (float)(-gamma_pp[prob]) : (float)gamma_pp[prob];
+    if (sm_pp != nullptr) sigma_modifier = (float)sm_pp[prob];
+    svrg_iter_body<MODE, OUTER, NOPS>(lds_raw, sh, a + img, b != nullptr ? b + img : nullptr, bitsT + (size_t)prob * FN * 8,
+                                      yh != nullptr ? yh + (size_t)prob * (FN / 2) * FN : nullptr, twtab, scale, beta,
+                                      c1 != nullptr ? c1 + img : nullptr, gamma, c2 != nullptr ? c2 + img : nullptr, out + img,
+                                      sigma_modifier, fallback_sigma, xrec != nullptr ? xrec + img : nullptr,
+                                      sse_out != nullptr ? sse_out + prob : nullptr, sigma_out != nullptr ? sigma_out + prob : nullptr,
+                                      OUTER ? w_out + img : nullptr, OUTER ? mu_out + img : nullptr);
+}
+
 // A whole OUTER iteration of pnp_svrg with the TV prox in one launch (algorithms/pnp_svrg.py:32-95 for T2 inner iterations): the
 // workgroup that owns an image runs the folded refresh + first inner iteration and then the T2 - 1 plain inner iterations of
 // THAT image back to back.  Inner iterations of different images never meet, so there is nothing to synchronise across
@@ -792,6 +824,46 @@ __global__ __launch_bounds__(FT) void k_svrg_outer(float* z, float* w, float* mu
 #pragma unroll 1
     for (int j = 1; j < T2; ++j) {
         // this iteration reads what the last one wrote (same lanes, same addresses): stores done, no stale line in the L1
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        __syncthreads();
+        svrg_iter_body<FUSED_FULL, false, 2>(lds_raw, sh, zi, w + img, selbits + ((size_t)j * batch + prob) * FN * 8, nullptr, twtab,
+                                             scale_inner, 1.0f, zi, gamma, mu + img, zi, sigma_modifier,
+                                             fallback_sigma, xrec + img, sse_log + (size_t)((log_row0 + j) % n_log) * batch + prob,
+                                             sigma_out + prob, nullptr, nullptr);
+    }
+}
+
+// Per-problem lr, mini_batch_size and sigma_modifier (pnp_csmri_svrg_outer_iteration_pp): lr_pp, sm_pp DOUBLE [batch], mb_vec
+// int32 [batch], each may be NULL (the scalar then holds).  The two coefficients are formed as csmri_fused_outer_launch forms
+// them on the host: alpha = -lr / (double)mb in double (IEEE division), scale_inner = (float)(alpha / N) (N = 2^16: the
+// product with 2^-16 is that quotient), gamma = (float)(-lr).
+__global__ __launch_bounds__(FT) void k_svrg_outer_pp(float* z, float* w, float* mu, const uint32_t* __restrict__ mask_bits,
+                                                      const cx<float>* __restrict__ yh, const float* __restrict__ alpha_vec,
+                                                      const uint32_t* __restrict__ selbits, int T2, double lr, const double* __restrict__ lr_pp,
+                                                      int mini_batch_size, const int32_t* __restrict__ mb_vec,
+                                                      const cx<float>* __restrict__ twtab, float sigma_modifier,
+                                                      const double* __restrict__ sm_pp, float fallback_sigma,
+                                                      const float* __restrict__ xrec, double* __restrict__ sse_log, int log_row0, int n_log,
+                                                      float* __restrict__ sigma_out) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    __shared__ FusedShared sh;
+    const int prob = blockIdx.x;
+    if (lr_pp != nullptr) lr = lr_pp[prob];
+    if (mb_vec != nullptr) mini_batch_size = mb_vec[prob];
+    if (sm_pp != nullptr) sigma_modifier = (float)sm_pp[prob];
+    const double alpha = -lr / (double)mini_batch_size;
+    const float scale_inner = (float)(alpha * (1.0 / ((double)FN * (double)FN))), gamma = (float)(-lr);
+    // from here on k_svrg_outer, statement for statement (a body shared with it changed its register allocation)
+    const int batch = gridDim.x;
+    const size_t img = (size_t)prob * FN * FN;
+    const float inv_n = 1.0f / ((float)FN * (float)FN);
+    float* zi = z + img;
+    svrg_iter_body<FUSED_FULL, true, 0>(lds_raw, sh, zi, nullptr, mask_bits + (size_t)prob * FN * 8, yh + (size_t)prob * (FN / 2) * FN, twtab,
+                                        inv_n * alpha_vec[prob], 1.0f, zi, gamma, nullptr, zi, sigma_modifier, fallback_sigma, xrec + img,
+                                        sse_log + (size_t)(log_row0 % n_log) * batch + prob, sigma_out + prob, w + img, mu + img);
+#pragma unroll 1
+    for (int j = 1; j < T2; ++j) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
         __syncthreads();
@@ -833,7 +905,14 @@ static int fused_lds_optin() {
         PNP_FUSED_ATTR(2, false, 0); PNP_FUSED_ATTR(2, false, 1); PNP_FUSED_ATTR(2, false, 2);
         PNP_FUSED_ATTR(0, true, 0); PNP_FUSED_ATTR(1, true, 0);
 #undef PNP_FUSED_ATTR
+#define PNP_FUSED_ATTR(...) PNP_CHECK_HIP(hipFuncSetAttribute((const void*)k_svrg_iter_pp<__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F_LDS_BYTES))
+        PNP_FUSED_ATTR(0, false, 0); PNP_FUSED_ATTR(0, false, 1); PNP_FUSED_ATTR(0, false, 2);
+        PNP_FUSED_ATTR(1, false, 0); PNP_FUSED_ATTR(1, false, 1); PNP_FUSED_ATTR(1, false, 2);
+        PNP_FUSED_ATTR(2, false, 0); PNP_FUSED_ATTR(2, false, 1); PNP_FUSED_ATTR(2, false, 2);
+        PNP_FUSED_ATTR(0, true, 0); PNP_FUSED_ATTR(1, true, 0);
+#undef PNP_FUSED_ATTR
         PNP_CHECK_HIP(hipFuncSetAttribute((const void*)k_svrg_outer, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F_LDS_BYTES));
+        PNP_CHECK_HIP(hipFuncSetAttribute((const void*)k_svrg_outer_pp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F_LDS_BYTES));
         attr_done |= 1ull << (dev & 63);
     }
     return PNP_OK;
@@ -843,10 +922,19 @@ static int fused_lds_optin() {
 int csmri_fused_outer_launch(int batch, const void* twtab, void* z, void* w, void* mu, const uint32_t* mask_bits, const void* yh,
                              const void* alpha_vec, const uint32_t* selbits, int T2, double lr, int mini_batch_size,
                              double sigma_modifier, double fallback_sigma, const void* xrec, double* sse_log, int log_row0, int n_log,
-                             void* sigma_out, void* stream) {
+                             void* sigma_out, void* stream, const double* lr_pp, const int32_t* mb_vec, const double* sm_pp) {
     int num_cu = 0, st_groups = 0, st_units = 0;
     { const int rc = stagger_config(&num_cu, &st_groups, &st_units); if (rc != PNP_OK) return rc; }
     { const int rc = fused_lds_optin(); if (rc != PNP_OK) return rc; }
+    if (lr_pp != nullptr || mb_vec != nullptr || sm_pp != nullptr) {    // per-problem form: the coefficients are made in the kernel
+        k_svrg_outer_pp<<<batch, FT, F_LDS_BYTES, (hipStream_t)stream>>>((float*)z, (float*)w, (float*)mu, mask_bits, (const cx<float>*)yh,
+                                                                        (const float*)alpha_vec, selbits, T2, lr, lr_pp, mini_batch_size,
+                                                                        mb_vec, (const cx<float>*)twtab, (float)sigma_modifier, sm_pp,
+                                                                        (float)fallback_sigma, (const float*)xrec, sse_log, log_row0,
+                                                                        n_log, (float*)sigma_out);
+        PNP_CHECK_LAUNCH();
+        return PNP_OK;
+    }
     const double alpha = -lr / (double)mini_batch_size;
     const float scale_inner = (float)(alpha / ((double)FN * (double)FN));
     k_svrg_outer<<<batch, FT, F_LDS_BYTES, (hipStream_t)stream>>>((float*)z, (float*)w, (float*)mu, mask_bits, (const cx<float>*)yh,
@@ -863,8 +951,11 @@ int csmri_fused_outer_launch(int batch, const void* twtab, void* z, void* w, voi
 int csmri_fused_launch(int batch, const void* twtab, const void* a, const void* b, const uint32_t* bitsT, const void* yh,
                        double alpha, const void* alpha_vec, double beta, const void* c1, double gamma, const void* c2, void* out,
                        int mode, double sigma_modifier, double fallback_sigma, const void* xrec, double* sse_out, void* sigma_out,
-                       void* stream, void* w_out, void* mu_out) {
+                       void* stream, void* w_out, void* mu_out, const double* alpha_pp, const double* gamma_pp, const double* sm_pp) {
     const float scale = (float)(alpha / ((double)FN * (double)FN));
+    const bool pp = alpha_pp != nullptr || gamma_pp != nullptr || sm_pp != nullptr;
+    // (a lone c2 moves to the first operand slot below and its coefficient becomes beta, which has no per-problem form)
+    PNP_CHECK_ARG(!(gamma_pp != nullptr && c1 == nullptr && c2 != nullptr), "per-problem gamma needs c1 beside c2 in the one-kernel form");
     hipStream_t s = (hipStream_t)stream;
     int num_cu = 0, st_groups = 0, st_units = 0;
     { const int rc = stagger_config(&num_cu, &st_groups, &st_units); if (rc != PNP_OK) return rc; }
@@ -874,13 +965,13 @@ int csmri_fused_launch(int batch, const void* twtab, const void* a, const void* 
     int nops = (c1 != nullptr ? 1 : 0) + (c2 != nullptr ? 1 : 0);
     if (c1 == nullptr && c2 != nullptr) { c1 = c2; beta = gamma; c2 = nullptr; }
     const bool outer = w_out != nullptr;
+#define PNP_FUSED_ARGS (const float*)a, (const float*)b, bitsT, (const cx<float>*)yh, (const cx<float>*)twtab, scale,                \
+                       (const float*)alpha_vec, (float)beta, (const float*)c1, (float)gamma, (const float*)c2, (float*)out,         \
+                       (float)sigma_modifier, (float)fallback_sigma, (const float*)xrec, sse_out, (float*)sigma_out, (float*)w_out, \
+                       (float*)mu_out, num_cu, st_groups, stagger_units
 #define PNP_FUSED_LAUNCH(...)                                                                                             \
-    k_svrg_iter<__VA_ARGS__><<<batch, FT, F_LDS_BYTES, s>>>((const float*)a, (const float*)b, bitsT, (const cx<float>*)yh,    \
-                                                       (const cx<float>*)twtab, scale, (const float*)alpha_vec, (float)beta,    \
-                                                       (const float*)c1, (float)gamma, (const float*)c2, (float*)out,         \
-                                                       (float)sigma_modifier, (float)fallback_sigma, (const float*)xrec,      \
-                                                       sse_out, (float*)sigma_out, (float*)w_out, (float*)mu_out, num_cu,      \
-                                                       st_groups, stagger_units)
+    do { if (pp) k_svrg_iter_pp<__VA_ARGS__><<<batch, FT, F_LDS_BYTES, s>>>(PNP_FUSED_ARGS, alpha_pp, gamma_pp, sm_pp);     \
+         else k_svrg_iter<__VA_ARGS__><<<batch, FT, F_LDS_BYTES, s>>>(PNP_FUSED_ARGS); } while (0)
 #define PNP_FUSED_BY_NOPS(MD)                                                     \
     do { if (nops == 0) PNP_FUSED_LAUNCH(MD, false, 0); else if (nops == 1) PNP_FUSED_LAUNCH(MD, false, 1); else PNP_FUSED_LAUNCH(MD, false, 2); } while (0)
     if (outer) {                                                // the outer refresh folded into the first inner iteration
@@ -891,6 +982,7 @@ int csmri_fused_launch(int batch, const void* twtab, const void* a, const void* 
     else PNP_FUSED_BY_NOPS(1);
 #undef PNP_FUSED_BY_NOPS
 #undef PNP_FUSED_LAUNCH
+#undef PNP_FUSED_ARGS
     PNP_CHECK_LAUNCH();
     return PNP_OK;
 }

@@ -80,50 +80,21 @@ template <typename T, int RA, int LA, bool MAG = false>
 __global__ __launch_bounds__(256) void k_rows_inv(const cx<T>* __restrict__ S1T, const cx<T>* __restrict__ twtab, int H,
                                                   T alpha, const T* __restrict__ alpha_vec, T beta, const T* c1, T gamma,
                                                   const T* c2, T* out) {
-    using S = FftSmem<T, RA, LA>;
-    constexpr int N = S::N, G = S::G, LG = S::LG;
-    __shared__ cx<T> smem[S::ELEMS];
-    const int t = threadIdx.x, g = t / LG, lane = t % LG;
-    const int prob = blockIdx.y, h0 = blockIdx.x * 2 * G;
-    if (alpha_vec != nullptr) alpha *= alpha_vec[prob];        // per-problem 1/M0 of a mixed-mask batch
+#include "rows_inv_body.h"
+}
 
-    const int p = t % G;
-    cx<T>* zp = smem + p * (N + 1);
-    for (int kx = t / G; kx < N / 2; kx += 256 / G) {
-        const vec4<T> q = *reinterpret_cast<const vec4<T>*>(S1T + ((size_t)prob * (N / 2) + kx) * H + h0 + 2 * p);
-        if (kx == 0) {
-            zp[0] = {q.a, q.c};
-            zp[N / 2] = {q.b, q.d};
-        } else {
-            zp[kx] = {q.a - q.d, q.b + q.c};                 // A + iB
-            zp[N - kx] = {q.a + q.d, q.c - q.b};             // conj(A) + i conj(B)
-        }
-    }
-    __syncthreads();
-    cx<T> v[LG], tw[LG];
-    load_twiddles_gen<T, LG>(tw, twtab, lane, N);
-#pragma unroll
-    for (int r = 0; r < LA; ++r) v[r] = smem[g * (N + 1) + (lane < RA ? lane : 0) + RA * r];
-    fft_gen<T, LA, RA, true>(v, tw, smem + g * LG * (LG + 1), lane);
-
-    const size_t ra = (size_t)prob * H * N + (size_t)(h0 + 2 * g) * N, rb = ra + N;
-    if (lane < LA) {
-#pragma unroll
-        for (int r = 0; r < RA; ++r) {
-            const int w = lane + LA * r;
-            T oa = alpha * v[r].x, ob = alpha * v[r].y;
-            if constexpr (MAG) {
-                const T pa = c1[ra + w], pb = c1[rb + w];
-                oa = sqrt(fma_(oa, oa, pa * pa));
-                ob = sqrt(fma_(ob, ob, pb * pb));
-            } else {
-                if (c1 != nullptr) { oa += beta * c1[ra + w]; ob += beta * c1[rb + w]; }
-                if (c2 != nullptr) { oa += gamma * c2[ra + w]; ob += gamma * c2[rb + w]; }
-            }
-            out[ra + w] = oa;
-            out[rb + w] = ob;
-        }
-    }
+// Per-problem coefficients (pnp_csmri_grad_sel_pp): alpha_pp / gamma_pp are DOUBLE [batch] arrays (NULL: the scalar), converted
+// here exactly as the host converts the scalars of k_rows_inv: alpha -> (T)(alpha * 1/(H W)) (inv_n is a power of two: the
+// product is the host's quotient), then the product with alpha_vec[b]; gamma -> (T)gamma.
+template <typename T, int RA, int LA>
+__global__ __launch_bounds__(256) void k_rows_inv_pp(const cx<T>* __restrict__ S1T, const cx<T>* __restrict__ twtab, int H,
+                                                     T alpha, const double* __restrict__ alpha_pp, double inv_n,
+                                                     const T* __restrict__ alpha_vec, T beta, const T* c1, T gamma,
+                                                     const double* __restrict__ gamma_pp, const T* c2, T* out) {
+    constexpr bool MAG = false;
+    if (alpha_pp != nullptr) alpha = (T)(alpha_pp[blockIdx.y] * inv_n);
+    if (gamma_pp != nullptr) gamma = (T)gamma_pp[blockIdx.y];
+#include "rows_inv_body.h"
 }
 
 }  // namespace pnp

@@ -43,6 +43,27 @@ __global__ __launch_bounds__(1024) void k_prox_tv(const T* zin, T* zout, int W,
                                 DENOISE ? zout : nullptr, sse_out, sigma_out, red, &sig_sh);
 }
 
+// sigma_modifier per problem (pnp_prox_tv_pp): sm_pp is a DOUBLE [batch] array, cast to T as the host casts the scalar
+template <typename T, int H, bool DENOISE>
+__global__ __launch_bounds__(1024) void k_prox_tv_pp(const T* zin, T* zout, int W, const T* __restrict__ sigma_in,
+                                                     const double* __restrict__ sm_pp, T fallback_sigma,
+                                                     const T* __restrict__ xrec, double* __restrict__ sse_out,
+                                                     T* __restrict__ sigma_out) {
+    constexpr int RPC = H / 4;
+    __shared__ double red[16];
+    __shared__ T sig_sh;
+    const int prob = blockIdx.x;
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63, cl = lane & 15, q = lane >> 4;
+    const int nwaves = blockDim.x >> 6;
+    const size_t base = (size_t)prob * H * W + (size_t)(q * RPC) * W + wv * 16 + cl;
+
+    T x[RPC];
+#pragma unroll
+    for (int i = 0; i < RPC; ++i) x[i] = zin[base + (size_t)i * W];
+    prox_tv_regs<T, H, DENOISE>(x, prob, W, base, wv, lane, q, nwaves, sigma_in, (T)sm_pp[prob], fallback_sigma, xrec,
+                                DENOISE ? zout : nullptr, sse_out, sigma_out, red, &sig_sh);
+}
+
 // ------------------------------------------------------------------------------- small batches: one wave per 16 columns
 // k_prox_tv gives an image to ONE workgroup, i.e. one CU: at B = 1 (the drop-in loops) the whole chip waits for it.  For
 // small batches the same pipeline runs as two launches of W/16 single-wave workgroups per image -- (1) per-column noise
@@ -66,49 +87,18 @@ __global__ __launch_bounds__(64) void k_shrink_cols(const T* zin, T* zout, int W
                                                     const T* __restrict__ xrec, double* __restrict__ sse_out,
                                                     T* __restrict__ sigma_out, double* __restrict__ partial,
                                                     unsigned* __restrict__ counter) {
-    constexpr int RPC = H / 4;
-    const int prob = blockIdx.y, wv = blockIdx.x, lane = threadIdx.x, cl = lane & 15, q = lane >> 4;
-    const int nwaves = W / 16;
-    T sigma_est;
-    if (sigma_in != nullptr) {
-        sigma_est = sigma_in[prob];
-    } else {
-        double s = 0;
-        for (int v = 0; v < nwaves; ++v) {                      // k_prox_tv: wave_sum over a wave's 16 columns, waves in order
-            double part = lane < 16 ? (double)sig_cols[(size_t)prob * W + v * 16 + lane] : 0.0;
-            s += wave_sum(part);
-        }
-        sigma_est = (T)(s / (double)W);
-    }
-    if (sigma_out != nullptr && wv == 0 && lane == 0) sigma_out[prob] = sigma_est;
-    if (!DENOISE) return;
-    const size_t base = (size_t)prob * H * W + (size_t)(q * RPC) * W + wv * 16 + cl;
-    T x[RPC];
-#pragma unroll
-    for (int i = 0; i < RPC; ++i) x[i] = zin[base + (size_t)i * W];
-    const T sigma = sigma_est > (T)0 ? sigma_est * sigma_modifier : fallback_sigma;
-    haar_bayes_shrink<T, H>(x, sigma * sigma);
-    double err = 0.0;
-    if (xrec != nullptr) err = (double)column_sq_err<T, RPC>(x, xrec + base, W);
-#pragma unroll
-    for (int i = 0; i < RPC; ++i) zout[base + (size_t)i * W] = x[i];
-    if (sse_out != nullptr) {
-        err = wave_sum(err);
-        __shared__ bool last;
-        if (lane == 0) {
-            partial[(size_t)prob * 16 + wv] = err;
-            __threadfence();
-            last = atomicAdd(&counter[prob], 1u) == (unsigned)(nwaves - 1);
-        }
-        __syncthreads();
-        if (last && lane == 0) {
-            __threadfence();
-            double s = 0;
-            for (int i = 0; i < nwaves; ++i) s += partial[(size_t)prob * 16 + i];
-            sse_out[prob] = s;
-            counter[prob] = 0;                                  // ready for the next call
-        }
-    }
+#include "shrink_cols_body.h"
+}
+
+template <typename T, int H>
+__global__ __launch_bounds__(64) void k_shrink_cols_pp(const T* zin, T* zout, int W, const T* __restrict__ sig_cols,
+                                                       const T* __restrict__ sigma_in, const double* __restrict__ sm_pp, T fallback_sigma,
+                                                       const T* __restrict__ xrec, double* __restrict__ sse_out,
+                                                       T* __restrict__ sigma_out, double* __restrict__ partial,
+                                                       unsigned* __restrict__ counter) {
+    constexpr bool DENOISE = true;
+    const T sigma_modifier = (T)sm_pp[blockIdx.y];
+#include "shrink_cols_body.h"
 }
 
 constexpr int kSmallBatch = 32;                                // up to this many images take the split form
@@ -197,7 +187,7 @@ __global__ void k_axpbypcz(T a, const T* x, T b, const T* y, T c, const T* w, T*
 
 template <typename T, int H, bool DENOISE>
 int launch_prox(const void* zin, void* zout, int W, int batch, const void* sigma_in, double mod, double fb,
-                const void* xrec, double* sse, void* sigma_out, hipStream_t s) {
+                const void* xrec, double* sse, void* sigma_out, hipStream_t s, const double* sm_pp = nullptr) {
     if (batch <= kSmallBatch && getenv("PNP_PROX_NO_SPLIT") == nullptr) {
         SmallProxScratch* sc = nullptr;
         const int rc = small_prox_scratch(&sc, s);
@@ -207,9 +197,19 @@ int launch_prox(const void* zin, void* zout, int W, int batch, const void* sigma
             k_sigma_cols<T, H><<<grid, 64, 0, s>>>((const T*)zin, W, (T*)sc->sig_cols);
             PNP_CHECK_LAUNCH();
         }
-        k_shrink_cols<T, H, DENOISE><<<DENOISE ? grid : dim3(1, batch), 64, 0, s>>>(
-            (const T*)zin, (T*)zout, W, (const T*)sc->sig_cols, (const T*)sigma_in, (T)mod, (T)fb, (const T*)xrec, sse,
-            (T*)sigma_out, sc->partial, sc->counter);
+        if (DENOISE && sm_pp != nullptr)
+            k_shrink_cols_pp<T, H><<<grid, 64, 0, s>>>((const T*)zin, (T*)zout, W, (const T*)sc->sig_cols, (const T*)sigma_in, sm_pp,
+                                                      (T)fb, (const T*)xrec, sse, (T*)sigma_out, sc->partial, sc->counter);
+        else
+            k_shrink_cols<T, H, DENOISE><<<DENOISE ? grid : dim3(1, batch), 64, 0, s>>>(
+                (const T*)zin, (T*)zout, W, (const T*)sc->sig_cols, (const T*)sigma_in, (T)mod, (T)fb, (const T*)xrec, sse,
+                (T*)sigma_out, sc->partial, sc->counter);
+        PNP_CHECK_LAUNCH();
+        return PNP_OK;
+    }
+    if (DENOISE && sm_pp != nullptr) {
+        k_prox_tv_pp<T, H, DENOISE><<<batch, (W / 16) * 64, 0, s>>>((const T*)zin, (T*)zout, W, (const T*)sigma_in, sm_pp, (T)fb,
+                                                                 (const T*)xrec, sse, (T*)sigma_out);
         PNP_CHECK_LAUNCH();
         return PNP_OK;
     }
@@ -221,12 +221,12 @@ int launch_prox(const void* zin, void* zout, int W, int batch, const void* sigma
 
 template <bool DENOISE>
 int dispatch_prox(const void* zin, void* zout, int H, int W, int batch, int dtype, const void* sigma_in, double mod,
-                  double fb, const void* xrec, double* sse, void* sigma_out, hipStream_t s) {
+                  double fb, const void* xrec, double* sse, void* sigma_out, hipStream_t s, const double* sm_pp = nullptr) {
     PNP_CHECK_ARG(zin != nullptr && batch >= 1, "null input / empty batch");
     PNP_CHECK_ARG(H == 16 || H == 32 || H == 64 || H == 128 || H == 256, "H must be 16, 32, 64, 128 or 256");
     PNP_CHECK_ARG(W % 16 == 0 && W >= 16 && W <= 256, "W must be a multiple of 16 in [16, 256]");
     PNP_CHECK_ARG(dtype == PNP_F32 || dtype == PNP_F64, "bad dtype");
-#define PNP_PROX_CASE(TT, HH) return launch_prox<TT, HH, DENOISE>(zin, zout, W, batch, sigma_in, mod, fb, xrec, sse, sigma_out, s)
+#define PNP_PROX_CASE(TT, HH) return launch_prox<TT, HH, DENOISE>(zin, zout, W, batch, sigma_in, mod, fb, xrec, sse, sigma_out, s, sm_pp)
     if (dtype == PNP_F32) {
         if (H == 256) PNP_PROX_CASE(float, 256);
         if (H == 128) PNP_PROX_CASE(float, 128);
@@ -258,6 +258,14 @@ extern "C" int pnp_prox_tv(const void* z_in, void* z_out, int H, int W, int batc
     PNP_CHECK_ARG(z_out != nullptr, "null output");
     return dispatch_prox<true>(z_in, z_out, H, W, batch, dtype, sigma_in, sigma_modifier, fallback_sigma, xrec, sse_out,
                                sigma_out, (hipStream_t)stream);
+}
+
+extern "C" int pnp_prox_tv_pp(const void* z_in, void* z_out, int H, int W, int batch, int dtype, const void* sigma_in,
+                              double sigma_modifier, const double* sigma_modifier_pp, double fallback_sigma, const void* xrec,
+                              double* sse_out, void* sigma_out, void* stream) {
+    PNP_CHECK_ARG(z_out != nullptr, "null output");
+    return dispatch_prox<true>(z_in, z_out, H, W, batch, dtype, sigma_in, sigma_modifier, fallback_sigma, xrec, sse_out,
+                               sigma_out, (hipStream_t)stream, sigma_modifier_pp);
 }
 
 extern "C" int pnp_sse(const void* z, const void* xrec, int n, int batch, int dtype, double* sse_out, void* stream) {

@@ -142,132 +142,32 @@ __global__ __launch_bounds__(kW2dThreads) void k_prox_wavelet2d(const T* zin, T*
                                                                 const T* __restrict__ sigma_in, T sigma_modifier, T fallback_sigma,
                                                                 const T* __restrict__ xrec, double* __restrict__ sse_out,
                                                                 T* __restrict__ sigma_out) {
-    __shared__ double red[16];
-    __shared__ T sig_sh;
-    __shared__ T band_sh[kW2dWaves][kW2dBands];
-    __shared__ T thr_sh[kW2dBands];
-    const int prob = blockIdx.x;
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const T* img_in = zin + (size_t)prob * H * W;
+#include "prox_wavelet2d_body.h"
+}
 
-    // ---------------- sigma_est = mean over columns of the per-column MAD estimate: prox_tv_regs' sum, wave for wave
-    T sigma_est;
-    if (sigma_in != nullptr) {
-        sigma_est = sigma_in[prob];
-    } else {
-        constexpr int RPC = H / 4;
-        const int cl = lane & 15, q = lane >> 4, ngroups = W / 16;
-#pragma unroll 1
-        for (int g = wv; g < ngroups; g += kW2dWaves) {
-            const T* col = img_in + (size_t)(q * RPC) * W + g * 16 + cl;
-            T x[RPC];
-#pragma unroll
-            for (int i = 0; i < RPC; ++i) x[i] = col[(size_t)i * W];
-            const T sc = column_sigma<T, RPC>(x, q);
-            double part = q == 0 ? (double)sc : 0.0;
-            part = wave_sum(part);
-            if (lane == 0) red[g] = part;
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            double s = 0;
-            for (int i = 0; i < ngroups; ++i) s += red[i];
-            sig_sh = (T)(s / (double)W);
-        }
-        __syncthreads();
-        sigma_est = sig_sh;
-    }
-    if (sigma_out != nullptr && threadIdx.x == 0) sigma_out[prob] = sigma_est;
-    const T sigma = sigma_est > (T)0 ? sigma_est * sigma_modifier : fallback_sigma;
-    const T var = sigma * sigma;
-
-    const int lx = lane & 7, ly = lane >> 3;
-    const int rcols = (W + 31) / 32, nregions = ((H + 31) / 32) * rcols;
-
-    // ---------------- pass 1: sums of squares of every detail sub-band
-    T acc[kW2dBands];
-#pragma unroll
-    for (int k = 0; k < kW2dBands; ++k) acc[k] = (T)0;
-#pragma unroll 1
-    for (int r = wv; r < nregions; r += kW2dWaves) {
-        const int row0 = (r / rcols) * 32 + ly * 4, col0 = (r % rcols) * 32 + lx * 4;
-        const bool inside = row0 < H && col0 < W;      // H, W are multiples of 16: a 4 x 4 block is wholly in or out
-        W2dCoef<T> c;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) c.v[i][j] = inside ? img_in[(size_t)(row0 + i) * W + col0 + j] : (T)0;
-        w2d_analysis(c, L, lx, ly);
-        w2d_accumulate(c, L, lx, ly, inside, acc);
-    }
-#pragma unroll
-    for (int k = 0; k < kW2dBands; ++k) {
-        const T s = wave_sum(acc[k]);
-        if (lane == 0) band_sh[wv][k] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < 3 * L) {
-        const int k = threadIdx.x, l = k / 3 + 1;
-        T ss = band_sh[0][k];
-        for (int w = 1; w < kW2dWaves; ++w) ss += band_sh[w][k];
-        const T dvar = ss / (T)((H >> l) * (W >> l));
-        T den = dvar - var;
-        den = (den > (T)2.220446049250313e-16 || den != den) ? den : (T)2.220446049250313e-16;   // max(NaN, eps) is NaN
-        thr_sh[k] = var / sqrt(den);
-    }
-    __syncthreads();
-    T thr[kW2dBands];
-#pragma unroll
-    for (int k = 0; k < kW2dBands; ++k) thr[k] = k < 3 * L ? thr_sh[k] : (T)0;
-
-    // ---------------- pass 2: analysis again, shrink, synthesis, store + squared error against the ground truth
-    double err = 0.0;
-#pragma unroll 1
-    for (int r = wv; r < nregions; r += kW2dWaves) {
-        const int row0 = (r / rcols) * 32 + ly * 4, col0 = (r % rcols) * 32 + lx * 4;
-        const bool inside = row0 < H && col0 < W;
-        const size_t off = (size_t)prob * H * W + (size_t)row0 * W + col0;
-        W2dCoef<T> c;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) c.v[i][j] = inside ? zin[off + (size_t)i * W + j] : (T)0;
-        w2d_analysis(c, L, lx, ly);
-        w2d_shrink_synthesis(c, L, lx, ly, thr);
-        if (inside) {
-            if (xrec != nullptr) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const double df = (double)xrec[off + (size_t)i * W + j] - (double)c.v[i][j];
-                        err += df * df;
-                    }
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) zout[off + (size_t)i * W + j] = c.v[i][j];
-        }
-    }
-    if (sse_out != nullptr) {
-        err = wave_sum(err);
-        __syncthreads();                               // red[] may still be read by the sigma sum of a slower wave
-        if (lane == 0) red[wv] = err;
-        __syncthreads();
-        if (threadIdx.x == 0) sse_out[prob] = ((red[0] + red[1]) + red[2]) + red[3];
-    }
+// sigma_modifier per problem (pnp_prox_wavelet2d_pp): sm_pp is a DOUBLE [batch] array, cast to T as the host casts the scalar
+template <typename T, int H>
+__global__ __launch_bounds__(kW2dThreads) void k_prox_wavelet2d_pp(const T* zin, T* zout, int W, int L,
+                                                                   const T* __restrict__ sigma_in, const double* __restrict__ sm_pp,
+                                                                   T fallback_sigma, const T* __restrict__ xrec,
+                                                                   double* __restrict__ sse_out, T* __restrict__ sigma_out) {
+    const T sigma_modifier = (T)sm_pp[blockIdx.x];
+#include "prox_wavelet2d_body.h"
 }
 
 template <typename T, int H>
 int launch_prox_wavelet2d(const void* zin, void* zout, int W, int batch, const void* sigma_in, double mod, double fb,
-                          const void* xrec, double* sse, void* sigma_out, hipStream_t s) {
+                          const void* xrec, double* sse, void* sigma_out, hipStream_t s, const double* sm_pp) {
     int lw = 0;
     while ((2 << lw) <= W) ++lw;                       // floor(log2 W)
     const int lh = HaarLevels<H>::value + 3;           // log2 H
     const int L = (lh < lw ? lh : lw) - 3 > 1 ? (lh < lw ? lh : lw) - 3 : 1;
-    k_prox_wavelet2d<T, H><<<batch, kW2dThreads, 0, s>>>((const T*)zin, (T*)zout, W, L, (const T*)sigma_in, (T)mod, (T)fb,
-                                                        (const T*)xrec, sse, (T*)sigma_out);
+    if (sm_pp != nullptr)
+        k_prox_wavelet2d_pp<T, H><<<batch, kW2dThreads, 0, s>>>((const T*)zin, (T*)zout, W, L, (const T*)sigma_in, sm_pp, (T)fb,
+                                                               (const T*)xrec, sse, (T*)sigma_out);
+    else
+        k_prox_wavelet2d<T, H><<<batch, kW2dThreads, 0, s>>>((const T*)zin, (T*)zout, W, L, (const T*)sigma_in, (T)mod, (T)fb,
+                                                            (const T*)xrec, sse, (T*)sigma_out);
     PNP_CHECK_LAUNCH();
     return PNP_OK;
 }
@@ -285,7 +185,32 @@ extern "C" int pnp_prox_wavelet2d(const void* z_in, void* z_out, int H, int W, i
     PNP_CHECK_ARG(W % 16 == 0 && W >= 16 && W <= 256, "W must be a multiple of 16 in [16, 256]");
     PNP_CHECK_ARG(dtype == PNP_F32 || dtype == PNP_F64, "bad dtype");
 #define PNP_W2D_CASE(TT, HH) \
-    return launch_prox_wavelet2d<TT, HH>(z_in, z_out, W, batch, sigma_in, sigma_modifier, fallback_sigma, xrec, sse_out, sigma_out, (hipStream_t)stream)
+    return launch_prox_wavelet2d<TT, HH>(z_in, z_out, W, batch, sigma_in, sigma_modifier, fallback_sigma, xrec, sse_out, sigma_out, (hipStream_t)stream, nullptr)
+    if (dtype == PNP_F32) {
+        if (H == 256) PNP_W2D_CASE(float, 256);
+        if (H == 128) PNP_W2D_CASE(float, 128);
+        if (H == 64) PNP_W2D_CASE(float, 64);
+        if (H == 32) PNP_W2D_CASE(float, 32);
+        PNP_W2D_CASE(float, 16);
+    }
+    if (H == 256) PNP_W2D_CASE(double, 256);
+    if (H == 128) PNP_W2D_CASE(double, 128);
+    if (H == 64) PNP_W2D_CASE(double, 64);
+    if (H == 32) PNP_W2D_CASE(double, 32);
+    PNP_W2D_CASE(double, 16);
+#undef PNP_W2D_CASE
+}
+
+extern "C" int pnp_prox_wavelet2d_pp(const void* z_in, void* z_out, int H, int W, int batch, int dtype, const void* sigma_in,
+                                  double sigma_modifier, const double* sigma_modifier_pp, double fallback_sigma, const void* xrec,
+                                  double* sse_out, void* sigma_out, void* stream) {
+    PNP_CHECK_ARG(z_out != nullptr, "null output");
+    PNP_CHECK_ARG(z_in != nullptr && batch >= 1, "null input / empty batch");
+    PNP_CHECK_ARG(H == 16 || H == 32 || H == 64 || H == 128 || H == 256, "H must be 16, 32, 64, 128 or 256");
+    PNP_CHECK_ARG(W % 16 == 0 && W >= 16 && W <= 256, "W must be a multiple of 16 in [16, 256]");
+    PNP_CHECK_ARG(dtype == PNP_F32 || dtype == PNP_F64, "bad dtype");
+#define PNP_W2D_CASE(TT, HH) \
+    return launch_prox_wavelet2d<TT, HH>(z_in, z_out, W, batch, sigma_in, sigma_modifier, fallback_sigma, xrec, sse_out, sigma_out, (hipStream_t)stream, sigma_modifier_pp)
     if (dtype == PNP_F32) {
         if (H == 256) PNP_W2D_CASE(float, 256);
         if (H == 128) PNP_W2D_CASE(float, 128);

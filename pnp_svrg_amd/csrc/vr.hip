@@ -72,6 +72,16 @@ extern "C" int pnp_draw_thresholds(int M, int batch, int mb, uint64_t seed, uint
     return PNP_OK;
 }
 
+extern "C" int pnp_draw_thresholds_pp(int M, int batch, const int32_t* mb_vec, const uint32_t* draw_id, uint64_t seed, uint32_t step0,
+                                      int nsteps, const uint32_t* step_dev, void* mbd, void* stream) {
+    PNP_CHECK_ARG(mbd != nullptr && mb_vec != nullptr, "null argument");
+    PNP_CHECK_ARG(M >= 1 && batch >= 1 && nsteps >= 1 && nsteps <= 65535, "need M, batch >= 1 and 1 <= nsteps <= 65535");
+    k_draw_thr_pp<false><<<dim3(batch, nsteps), 256, 0, (hipStream_t)stream>>>(nullptr, 1, M, mb_vec, draw_id, seed, step0, step_dev,
+                                                                              (MbDesc*)mbd, nullptr, draw_fast_path());
+    PNP_CHECK_LAUNCH();
+    return PNP_OK;
+}
+
 extern "C" int pnp_indicator_from_thresholds(int M, int batch, const void* mbd, uint8_t* sel, void* stream) {
     PNP_CHECK_ARG(mbd && sel && M >= 1 && batch >= 1, "bad argument");
     k_indicator_from_thr<<<dim3((M + 255) / 256, batch), 256, 0, (hipStream_t)stream>>>((const MbDesc*)mbd, sel, M);

@@ -16,6 +16,12 @@ A *batch problem* (CsmriBatch, DeblurBatch, PrBatch) holds the device-resident d
 Minibatches are drawn on the device by default (counter-based keys + a threshold per (problem, step): csrc/draw.h;
 the selection itself is re-derived inside the gradient kernels and never stored); for reference-identical runs pass
 index lists drawn from the legacy `np.random` stream (`step(idx)`).
+
+Per-problem hyper-parameters (a hyper-parameter grid as one batch): GdEngine, SgdEngine and SvrgEngine take `eta` and
+`mini_batch_size`, and TVProx takes `sigma_modifier`, as a scalar or as a [B] array.  A scalar takes exactly the plain calls; an
+array goes to the `_pp` entry points as float64 / int32 device vectors made once on the host (`-lr`, `-lr / mb`: remade when
+lr_decay != 1 changes them), and problem b then walks, bit for bit, the trajectory a scalar engine with b's values walks.
+`draw_id` ([B] ints) replaces the batch index in the minibatch stream, and `CsmriBatch.tile(n)` repeats a batch's data n times.
 """
 import numpy as np
 import torch
@@ -40,6 +46,17 @@ class _BatchBase:
         return Minibatches(n, self.B, self.device)
 
     def _check_mb(self, mb):
+        if np.ndim(mb) != 0:                                    # per problem: every entry against its own problem's population
+            mb = np.asarray(mb)
+            cap = np.broadcast_to(np.asarray(getattr(self, 'M0', self.max_mb)), (self.B,))
+            if mb.shape != (self.B,) or not np.issubdtype(mb.dtype, np.integer):
+                raise ValueError(f'per-problem mini_batch_size: {self.B} integers, got shape {mb.shape} of {mb.dtype}')
+            bad = np.flatnonzero((mb < 1) | (mb > cap))
+            if bad.size:
+                b = int(bad[0])
+                raise ValueError(f"Cannot take a larger sample than population when 'replace=False' (problem {b}: mini_batch_size "
+                                 f'{int(mb[b])}, population {int(cap[b])}; sizes must be >= 1)')
+            return
         if mb > self.max_mb:
             # np.random.choice(..., replace=False) raises the same way (problems/problem.py:110-117, CSMRI.py:66-74)
             raise ValueError(f"Cannot take a larger sample than population when 'replace=False' (mini_batch_size {mb} > {self.max_mb})")
@@ -174,6 +191,23 @@ class CsmriBatch(_BatchBase):
         self._mask_np = None
         return self
 
+    def tile(self, n):
+        """A batch of n * B problems whose data is this batch's repeated n times along B (problem t * B + i = this batch's
+        problem i): device copies only, no regeneration and no host round trip -- what a trial-batched grid runs on."""
+        n = int(n)
+        if n < 1:
+            raise ValueError('tile(n) needs n >= 1')
+        t = type(self).__new__(type(self))
+        t.B, t.H, t.W, t.N, t.dtype, t.device = self.B * n, self.H, self.W, self.N, self.dtype, self.device
+        t.plan = ops.CsmriPlan(self.H, self.W, t.B, self.dtype)
+        for name in ('xrec', 'xinit', 'maskT', 'bits', 'YT', 'yh_full', 'inv_m0', 'sigma'):
+            v = getattr(self, name, None)
+            if v is not None:
+                setattr(t, name, v.repeat((n,) + (1,) * (v.dim() - 1)).contiguous())
+        t.M0, t.max_mb = np.tile(self.M0, n), self.max_mb
+        t._mask_np = None if self._mask_np is None else np.tile(self._mask_np, (n, 1, 1))
+        return t
+
     @classmethod
     def from_problems(cls, probs, dtype=torch.float32, device='cuda'):
         """From reference-style problem objects (anything with Xrec, mask, Y, Xinit: problems.CSMRI, the oracle's)."""
@@ -196,10 +230,16 @@ class CsmriBatch(_BatchBase):
     def minibatches(self, n):
         return Minibatches(n, self.B, self.device, bits_shape=(self.W, self.H // 32))
 
-    def draw(self, mbs, mb, seed, step0, nsteps=1, step_dev=None):
-        self._check_mb(mb)
+    def draw(self, mbs, mb, seed, step0, nsteps=1, step_dev=None, draw_id=None):
+        """mb: an int, or per problem: [B] integers on the host (checked against each problem's population, then uploaded) or an
+        int32 [B] device tensor (taken as checked: the engines check their host copy once).  draw_id: int32 [B] device tensor,
+        the ids the minibatch streams absorb in place of the batch index."""
+        if not isinstance(mb, torch.Tensor):
+            self._check_mb(mb)
+            if np.ndim(mb) != 0:
+                mb = torch.from_numpy(np.ascontiguousarray(mb, np.int32)).to(self.device)
         self.plan.draw_thresholds(self.bits, mb, seed, step0, nsteps, out=mbs.mbd[:nsteps], step_dev=step_dev,
-                                  selbits=mbs.selbits[:nsteps])
+                                  selbits=mbs.selbits[:nsteps], draw_id=draw_id)
         for j in range(nsteps):
             mbs.host[j] = None
 
@@ -474,6 +514,11 @@ class TVProx:
 
     def bind(self, batch):
         self.sig = torch.empty(batch.B, dtype=batch.dtype, device=batch.xrec.device)
+        if not isinstance(self.sigma_modifier, torch.Tensor) and np.ndim(self.sigma_modifier) != 0:
+            sm = np.ascontiguousarray(self.sigma_modifier, np.float64)      # per problem: a float64 [B] device vector, uploaded once
+            if sm.shape != (batch.B,):
+                raise ValueError(f'per-problem sigma_modifier: {batch.B} values, got shape {sm.shape}')
+            self.sigma_modifier = torch.from_numpy(sm).to(batch.xrec.device)
 
     def __call__(self, z, xrec, sse_out):
         self.t += 1
@@ -574,6 +619,11 @@ class LoopEngine:
 
     def __init__(self, batch, prox, eta, lr_decay=1.0, n_log=4096, seed=0):
         self.b, self.prox, self.eta, self.lr_decay, self.seed = batch, prox, eta, lr_decay, seed
+        if np.ndim(eta) != 0:                                   # per-problem step sizes
+            self.eta = np.ascontiguousarray(eta, np.float64)
+            if self.eta.shape != (batch.B,) or batch.kind != 'csmri':
+                raise ValueError(f'per-problem eta: {batch.B} values on a CsmriBatch, got shape {self.eta.shape} on {batch.kind!r}')
+        self._coef = {}
         dev = batch.xrec.device
         self.z = batch.xinit.clone()
         self.sse_log = torch.zeros((n_log, batch.B), dtype=torch.float64, device=dev)
@@ -588,6 +638,17 @@ class LoopEngine:
         self.s = self.n_prox = 0
         if hasattr(self.prox, 't'):
             self.prox.t = 0
+
+    def _c(self, name, k, v):
+        """A coefficient as the kernels take it: a scalar stays the Python float of the plain calls; a per-problem array (float64,
+        made on the host) is uploaded -- once when lr_decay == 1, else whenever the decay exponent k changes."""
+        if np.ndim(v) == 0:
+            return v
+        key = k if self.lr_decay != 1.0 else 0
+        hit = self._coef.get(name)
+        if hit is None or hit[0] != key:
+            hit = self._coef[name] = (key, torch.from_numpy(np.ascontiguousarray(v, np.float64)).to(self.z.device))
+        return hit[1]
 
     def _prox(self, z):
         out = self.prox(z, self.b.xrec, self.sse_log[self.n_prox % self.n_log])
@@ -611,7 +672,7 @@ class GdEngine(LoopEngine):
 
     def step(self):
         lr = self.eta * self.lr_decay ** self.s
-        self.b.grad_full(self.z, out=self.z, alpha=-lr, beta=1.0, c1=self.z)
+        self.b.grad_full(self.z, out=self.z, alpha=self._c('-lr', self.s, -lr), beta=1.0, c1=self.z)
         self.z = self._prox(self.z)
         self.s += 1
 
@@ -622,10 +683,23 @@ class _StochEngine(LoopEngine):
     # (seed, step, problem) only, so a window of steps drawn together holds the very same selections.
     AHEAD = 16
 
-    def __init__(self, batch, prox, eta, mini_batch_size, lr_decay=1.0, n_log=4096, seed=0, n_slots=None):
+    def __init__(self, batch, prox, eta, mini_batch_size, lr_decay=1.0, n_log=4096, seed=0, n_slots=None, draw_id=None):
         super().__init__(batch, prox, eta, lr_decay, n_log, seed)
         batch._check_mb(mini_batch_size)
-        self.mb = mini_batch_size
+        self.mb = self._mb_draw = mini_batch_size               # (host value for the coefficients, what the draws take)
+        self._draw_kw = {}
+        if np.ndim(mini_batch_size) != 0 or draw_id is not None:
+            if batch.kind != 'csmri':
+                raise ValueError(f'per-problem mini_batch_size / draw_id need a CsmriBatch (got {batch.kind!r})')
+            dev = batch.xrec.device
+            if np.ndim(mini_batch_size) != 0:
+                self.mb = np.ascontiguousarray(mini_batch_size, np.int32)
+                self._mb_draw = torch.from_numpy(self.mb).to(dev)
+            if draw_id is not None:                             # the 32-bit ids the minibatch streams absorb
+                ids = np.array([int(v) & 0xFFFFFFFF for v in np.ravel(draw_id)], np.uint32)
+                if ids.shape != (batch.B,):
+                    raise ValueError(f'draw_id: {batch.B} values, got {ids.shape}')
+                self._draw_kw = dict(draw_id=torch.from_numpy(ids.view(np.int32)).to(dev))
         self._window = n_slots is None                          # one draw launch per AHEAD steps (else: the subclass draws)
         self.mbs = batch.minibatches(self.AHEAD if n_slots is None else n_slots)
         self._drawn_base = None                                 # first step of the window the slots currently hold
@@ -637,12 +711,12 @@ class _StochEngine(LoopEngine):
             self._drawn_base = None
             return 0
         if not self._window or step_id >= 0xFFFFFFF0:          # (0xFFFFFFFF: the table-filling draw of pnp_saga)
-            self.b.draw(self.mbs, self.mb, self.seed, step_id, 1)
+            self.b.draw(self.mbs, self._mb_draw, self.seed, step_id, 1, **self._draw_kw)
             self._drawn_base = None
             return 0
         base = step_id - step_id % self.AHEAD
         if self._drawn_base != base:
-            self.b.draw(self.mbs, self.mb, self.seed, base, self.AHEAD)
+            self.b.draw(self.mbs, self._mb_draw, self.seed, base, self.AHEAD, **self._draw_kw)
             self._drawn_base = base
         return step_id - base
 
@@ -650,7 +724,7 @@ class _StochEngine(LoopEngine):
         one = Minibatches.__new__(Minibatches)
         one.n, one.mbd, one.host = 1, self.mbs.mbd[slot:slot + 1], [None]
         one.selbits = self.mbs.selbits[slot:slot + 1] if self.mbs.selbits is not None else None
-        self.b.draw(one, self.mb, self.seed, step_id, 1)
+        self.b.draw(one, self._mb_draw, self.seed, step_id, 1, **self._draw_kw)
         self.mbs.host[slot] = None
 
 
@@ -660,7 +734,7 @@ class SgdEngine(_StochEngine):
     def step(self, idx_s=None):
         j = self._minibatch(idx_s, self.s)
         lr = self.eta * self.lr_decay ** self.s
-        self.b.grad_stoch(self.z, self.mbs, j, out=self.z, alpha=-lr / self.mb, beta=1.0, c1=self.z)
+        self.b.grad_stoch(self.z, self.mbs, j, out=self.z, alpha=self._c('-lr/mb', self.s, -lr / self.mb), beta=1.0, c1=self.z)
         self.z = self._prox(self.z)
         self.s += 1
 
@@ -673,8 +747,8 @@ class SvrgEngine(_StochEngine):
     FUSED_MIN_BATCH = 192
 
     def __init__(self, batch, prox, eta, T2, mini_batch_size, lr_decay=1.0, variant='svrg', n_log=4096, seed=0, fused=None,
-                 fold_outer=True):
-        super().__init__(batch, prox, eta, mini_batch_size, lr_decay, n_log, seed, n_slots=T2)
+                 fold_outer=True, draw_id=None):
+        super().__init__(batch, prox, eta, mini_batch_size, lr_decay, n_log, seed, n_slots=T2, draw_id=draw_id)
         self.T2, self.variant = T2, variant
         # the one-kernel inner iteration (csrc/csmri_fused.hip): CSMRI, f32, 256 x 256, true SVRG direction, a prox that
         # can follow it (TV inside the kernel, DnCNN after it)
@@ -709,13 +783,13 @@ class SvrgEngine(_StochEngine):
         lr = self.eta * self.lr_decay ** (s // self.T2)
         if j == 0:                                              # outer: mu = grad_full(z); w = z
             if self.variant == 'svrg' and idx_s is None:
-                b.draw(self.mbs, self.mb, self.seed, s, self.T2)
+                b.draw(self.mbs, self._mb_draw, self.seed, s, self.T2, **self._draw_kw)
             if self.fused and self.fold_outer:
                 # ... folded into the first inner iteration: at j = 0 the SVRG difference gs(z) - gs(w) is exactly zero
                 # (w == z), so that iteration is z <- prox(z - lr * mu); ONE kernel forms mu, stores it and w, and goes on
                 if idx_s is not None:                           # (the minibatch of this step is drawn but cannot matter)
                     b.set_host(self.mbs, j, idx_s)
-                self._fused_outer(lr, self.sse_log[self.n_prox % self.n_log])
+                self._fused_outer(lr, self.sse_log[self.n_prox % self.n_log], s // self.T2)
                 self.n_prox += 1
                 self.s += 1
                 return
@@ -727,25 +801,35 @@ class SvrgEngine(_StochEngine):
             elif self.mbs.host[j] is not None:                  # a host-fed outer iteration continued with device draws
                 self._draw_slot(j, s)
             if self.fused:
-                self._fused_inner(j, lr, self.sse_log[self.n_prox % self.n_log])
+                self._fused_inner(j, lr, self.sse_log[self.n_prox % self.n_log], s // self.T2)
                 self.n_prox += 1
                 self.s += 1
                 return
-            b.grad_stoch_diff(self.z, self.w, self.mbs, j, out=self.z, alpha=-lr / self.mb, beta=1.0, c1=self.z,
-                              gamma=-lr, c2=self.mu)
+            k = s // self.T2
+            b.grad_stoch_diff(self.z, self.w, self.mbs, j, out=self.z, alpha=self._c('-lr/mb', k, -lr / self.mb), beta=1.0, c1=self.z,
+                              gamma=self._c('-lr', k, -lr), c2=self.mu)
         else:
-            ops.axpbypcz(1.0, self.z, -lr, self.mu, out=self.z)
+            self._step_along_mu(lr)
         self.z = self._prox(self.z)
         self.s += 1                                             # eager steps keep the index on the host (no counter launch)
 
-    def _fused_outer(self, lr, sse_out):
+    def _step_along_mu(self, lr):
+        """variant='reference': z <- z - lr * mu.  pnp_axpbypcz has scalar coefficients: per-problem step sizes take one launch
+        per problem (this variant documents what v1 executes; it is not a throughput path)."""
+        if np.ndim(lr) == 0:
+            ops.axpbypcz(1.0, self.z, -lr, self.mu, out=self.z)
+        else:
+            for i in range(self.b.B):
+                ops.axpbypcz(1.0, self.z[i], -float(lr[i]), self.mu[i], out=self.z[i])
+
+    def _fused_outer(self, lr, sse_out, k=0):
         """outer refresh (mu = grad_full(z), w = z) + inner iteration 0 in one kernel (pnp_csmri_svrg_outer_step)."""
         b, px = self.b, self.prox
-        b.plan.svrg_outer_step(self.z, b.bits, b.yh_full, b.inv_m0, lr, self.w, self.mu, out=self.z, denoise=px.fused_denoise,
-                               xrec=b.xrec, sse=sse_out if px.fused_denoise else None, **px.fused_args())
+        b.plan.svrg_outer_step(self.z, b.bits, b.yh_full, b.inv_m0, self._c('lr', k, lr), self.w, self.mu, out=self.z,
+                               denoise=px.fused_denoise, xrec=b.xrec, sse=sse_out if px.fused_denoise else None, **px.fused_args())
         px.after_fused(self.z, b.xrec, sse_out)
 
-    def _fused_inner(self, j, lr, sse_out):
+    def _fused_inner(self, j, lr, sse_out, k=0):
         """step + estimate_sigma + prox + error of inner iteration j in one kernel (TV), or in one kernel + the network."""
         b, px = self.b, self.prox
         if self.mbs.host[j] is not None:                        # host-drawn selector: pack it to bits (a 5 us launch)
@@ -753,8 +837,8 @@ class SvrgEngine(_StochEngine):
             bits = self._hostbits
         else:
             bits = self.mbs.selbits[j]
-        b.plan.svrg_step(self.z, self.w, bits, alpha=-lr / self.mb, beta=1.0, c1=self.z, gamma=-lr, c2=self.mu, out=self.z,
-                         denoise=px.fused_denoise, xrec=b.xrec, sse=sse_out if px.fused_denoise else None, **px.fused_args())
+        b.plan.svrg_step(self.z, self.w, bits, alpha=self._c('-lr/mb', k, -lr / self.mb), beta=1.0, c1=self.z,
+                         gamma=self._c('-lr', k, -lr), c2=self.mu, out=self.z, denoise=px.fused_denoise, xrec=b.xrec, sse=sse_out if px.fused_denoise else None, **px.fused_args())
         px.after_fused(self.z, b.xrec, sse_out)
 
     # ---- hipGraph form: one OUTER iteration (full-gradient refresh + T2 inner iterations) = one graph launch
@@ -766,7 +850,7 @@ class SvrgEngine(_StochEngine):
             self.w.copy_(self.z)
         lr = self.eta
         if self.variant == 'svrg':
-            b.draw(self.mbs, self.mb, self.seed, 0, self.T2, step_dev=self.step_dev)
+            b.draw(self.mbs, self._mb_draw, self.seed, 0, self.T2, step_dev=self.step_dev, **self._draw_kw)
         for j in range(self.T2):
             if fold and j == 0:
                 self._fused_outer(lr, self.sse_tmp)
@@ -774,10 +858,10 @@ class SvrgEngine(_StochEngine):
                 self._fused_inner(j, lr, self.sse_tmp)
             else:
                 if self.variant == 'svrg':
-                    b.grad_stoch_diff(self.z, self.w, self.mbs, j, out=self.z, alpha=-lr / self.mb, beta=1.0, c1=self.z,
-                                      gamma=-lr, c2=self.mu)
+                    b.grad_stoch_diff(self.z, self.w, self.mbs, j, out=self.z, alpha=self._c('-lr/mb', 0, -lr / self.mb), beta=1.0,
+                                      c1=self.z, gamma=self._c('-lr', 0, -lr), c2=self.mu)
                 else:
-                    ops.axpbypcz(1.0, self.z, -lr, self.mu, out=self.z)
+                    self._step_along_mu(lr)
                 out = self.prox(self.z, b.xrec, self.sse_tmp)
                 if out is not self.z:
                     raise ValueError('graph capture needs an in-place prox')
@@ -847,10 +931,10 @@ class SvrgEngine(_StochEngine):
                                  'refresh, device-drawn minibatches and a step count that is a multiple of T2')
             b, px = self.b, self.prox
             for _ in range(n_outer):
-                b.draw(self.mbs, self.mb, self.seed, self.s, self.T2)
+                b.draw(self.mbs, self._mb_draw, self.seed, self.s, self.T2, **self._draw_kw)
                 lr = self.eta * self.lr_decay ** (self.s // self.T2)
-                b.plan.svrg_outer_iteration(self.z, self.w, self.mu, b.bits, b.yh_full, b.inv_m0, self.mbs.selbits, self.T2, lr, self.mb,
-                                            b.xrec, self.sse_log, self.n_prox % self.n_log, px.sig, sigma_modifier=px.sigma_modifier)
+                b.plan.svrg_outer_iteration(self.z, self.w, self.mu, b.bits, b.yh_full, b.inv_m0, self.mbs.selbits, self.T2,
+                                            self._c('lr', self.s // self.T2, lr), self._mb_draw, b.xrec, self.sse_log, self.n_prox % self.n_log, px.sig, sigma_modifier=px.sigma_modifier)
                 self.s += self.T2
                 self.n_prox += self.T2
                 px.t += self.T2
@@ -954,5 +1038,6 @@ def make_engine(batch, prox, eta, T2, mini_batch_size, lr_decay=1.0, variant='sv
         return SagaEngine(batch, prox, eta, mini_batch_size, hist_size=hist_size, lr_decay=lr_decay, **kw)
     if algorithm == 'gd':
         kw.pop('seed', None)
+        kw.pop('draw_id', None)
         return GdEngine(batch, prox, eta, lr_decay=lr_decay, **kw)
     raise ValueError(f'unknown algorithm {algorithm!r}')

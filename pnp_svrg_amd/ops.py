@@ -25,6 +25,15 @@ def _p(t):
     return ctypes.c_void_p(t.data_ptr())
 
 
+def _pp(v, B, dtype=torch.float64):
+    """A hyper-parameter that may be per problem -> (scalar, device array or None): a tensor ([B], float64 -- int32 for minibatch
+    sizes) goes to the `_pp` entry point's array argument, anything else is the scalar of the plain call."""
+    if isinstance(v, torch.Tensor):
+        assert v.dtype == dtype and tuple(v.shape) == (B,), f'per-problem values: a [{B}] {dtype} device tensor'
+        return (0 if dtype == torch.int32 else 0.0), v
+    return (int(v) if dtype == torch.int32 else float(v)), None
+
+
 def require_gpu():
     if not torch.cuda.is_available():
         raise N.NativeError('no MI355X visible (torch.cuda.is_available() is False); the hot path has no CPU fallback')
@@ -63,14 +72,24 @@ class CsmriPlan:
         N.call('pnp_csmri_pack_mask', self._h, _p(selT), _p(out), _stream())
         return out
 
-    def draw_thresholds(self, bits, mb, seed, step0, nsteps=1, out=None, step_dev=None, selbits=None):
+    def draw_thresholds(self, bits, mb, seed, step0, nsteps=1, out=None, step_dev=None, selbits=None, draw_id=None):
         """Device-side minibatch draws for steps step0 .. step0+nsteps-1 of every problem: threshold descriptors
         (int64 [nsteps, B, 2] = 16 bytes per (step, problem)) and, when `selbits` (int32 [nsteps, B, W, H/32]) is given,
-        mask o minibatch as bit-packed selectors -- `grad(bits=selbits[j])` consumes a step's row."""
+        mask o minibatch as bit-packed selectors -- `grad(bits=selbits[j])` consumes a step's row.
+        mb: an int, or an int32 [B] device tensor (problem b draws mb[b]); draw_id: int32 [B] device tensor holding the 32-bit
+        ids the streams absorb in place of the batch index (pnp_csmri_draw_thresholds_pp)."""
         assert bits.dtype == torch.int32 and tuple(bits.shape) == (self.B, self.W, self.H // 32)
         out = out if out is not None else torch.empty((nsteps, self.B, 2), dtype=torch.int64, device=bits.device)
         assert out.dtype == torch.int64 and tuple(out.shape) == (nsteps, self.B, 2)
         assert selbits is None or (selbits.dtype == torch.int32 and tuple(selbits.shape) == (nsteps, self.B, self.W, self.H // 32))
+        if isinstance(mb, torch.Tensor) or draw_id is not None:
+            if not isinstance(mb, torch.Tensor):
+                mb = torch.full((self.B,), int(mb), dtype=torch.int32, device=bits.device)
+            assert mb.dtype == torch.int32 and tuple(mb.shape) == (self.B,)
+            assert draw_id is None or (draw_id.dtype == torch.int32 and tuple(draw_id.shape) == (self.B,))
+            N.call('pnp_csmri_draw_thresholds_pp', self._h, _p(bits), _p(mb), _p(draw_id), int(seed) & (2 ** 64 - 1),
+                   int(step0) & 0xFFFFFFFF, int(nsteps), _p(step_dev), _p(out), _p(selbits), _stream())
+            return out
         N.call('pnp_csmri_draw_thresholds', self._h, _p(bits), int(mb), int(seed) & (2 ** 64 - 1), int(step0) & 0xFFFFFFFF,
                int(nsteps), _p(step_dev), _p(out), _p(selbits), _stream())
         return out
@@ -116,6 +135,11 @@ class CsmriPlan:
         assert alpha_vec is None or (alpha_vec.dtype == self.dtype and alpha_vec.numel() == self.B)
         out = out if out is not None else torch.empty_like(a)
         assert YT is None or (YT.dtype == _CDT[self.dtype] and tuple(YT.shape) == (self.B, self.W, self.H))
+        if isinstance(alpha, torch.Tensor) or isinstance(gamma, torch.Tensor):       # float64 [B]: per-problem coefficients
+            (al, al_pp), (ga, ga_pp) = _pp(alpha, self.B), _pp(gamma, self.B)
+            N.call('pnp_csmri_grad_sel_pp', self._h, _p(a), _p(b), _p(selT), _p(bits), _p(yh), _p(YT), al, _p(al_pp), _p(alpha_vec),
+                   float(beta), _p(c1), ga, _p(ga_pp), _p(c2), _p(out), _stream())
+            return out
         N.call('pnp_csmri_grad_sel', self._h, _p(a), _p(b), _p(selT), _p(bits), _p(yh), _p(YT), float(alpha), _p(alpha_vec),
                float(beta), _p(c1), float(gamma), _p(c2), _p(out), _stream())
         return out
@@ -153,6 +177,12 @@ class CsmriPlan:
         assert bits.dtype == torch.int32 and tuple(bits.shape) == (self.B, self.W, self.H // 32)
         out = out if out is not None else torch.empty_like(a)
         sigma_out = sigma_out if sigma_out is not None else torch.empty(self.B, dtype=a.dtype, device=a.device)
+        if any(isinstance(v, torch.Tensor) for v in (alpha, gamma, sigma_modifier)):
+            (al, al_pp), (ga, ga_pp), (sm, sm_pp) = _pp(alpha, self.B), _pp(gamma, self.B), _pp(sigma_modifier, self.B)
+            N.call('pnp_csmri_svrg_step_pp', self._h, _p(a), _p(b), _p(bits), al, _p(al_pp), _p(alpha_vec), float(beta), _p(c1), ga,
+                   _p(ga_pp), _p(c2), _p(out), 1 if denoise else 0, sm, _p(sm_pp), float(fallback_sigma), _p(xrec), _p(sse),
+                   _p(sigma_out), _stream())
+            return out, sse, sigma_out
         N.call('pnp_csmri_svrg_step', self._h, _p(a), _p(b), _p(bits), float(alpha), _p(alpha_vec), float(beta), _p(c1),
                float(gamma), _p(c2), _p(out), 1 if denoise else 0, float(sigma_modifier), float(fallback_sigma), _p(xrec),
                _p(sse), _p(sigma_out), _stream())
@@ -169,6 +199,12 @@ class CsmriPlan:
             assert t is None or (t.dtype == self.dtype and t.numel() == self.B * self.H * self.W)
         out = out if out is not None else torch.empty_like(z)
         sigma_out = sigma_out if sigma_out is not None else torch.empty(self.B, dtype=z.dtype, device=z.device)
+        if isinstance(lr, torch.Tensor) or isinstance(sigma_modifier, torch.Tensor):
+            (l, l_pp), (sm, sm_pp) = _pp(lr, self.B), _pp(sigma_modifier, self.B)
+            N.call('pnp_csmri_svrg_outer_step_pp', self._h, _p(z), _p(mask_bits), _p(yh), _p(alpha_vec), l, _p(l_pp), _p(w_out),
+                   _p(mu_out), _p(out), 1 if denoise else 0, sm, _p(sm_pp), float(fallback_sigma), _p(xrec), _p(sse), _p(sigma_out),
+                   _stream())
+            return out, sse, sigma_out
         N.call('pnp_csmri_svrg_outer_step', self._h, _p(z), _p(mask_bits), _p(yh), _p(alpha_vec), float(lr), _p(w_out), _p(mu_out),
                _p(out), 1 if denoise else 0, float(sigma_modifier), float(fallback_sigma), _p(xrec), _p(sse), _p(sigma_out), _stream())
         return out, sse, sigma_out
@@ -182,6 +218,12 @@ class CsmriPlan:
             assert t.dtype == self.dtype and t.numel() == self.B * self.H * self.W
         assert selbits.dtype == torch.int32 and tuple(selbits.shape) == (T2, self.B, self.W, self.H // 32)
         assert sse_log.dtype == torch.float64 and sse_log.dim() == 2 and sse_log.shape[1] == self.B and sse_log.is_contiguous()
+        if any(isinstance(v, torch.Tensor) for v in (lr, mini_batch_size, sigma_modifier)):
+            (l, l_pp), (m, m_vec), (sm, sm_pp) = _pp(lr, self.B), _pp(mini_batch_size, self.B, torch.int32), _pp(sigma_modifier, self.B)
+            N.call('pnp_csmri_svrg_outer_iteration_pp', self._h, _p(z), _p(w), _p(mu), _p(mask_bits), _p(yh), _p(alpha_vec), _p(selbits),
+                   int(T2), l, _p(l_pp), m, _p(m_vec), sm, _p(sm_pp), float(fallback_sigma), _p(xrec), _p(sse_log), int(log_row0),
+                   int(sse_log.shape[0]), _p(sigma_out), _stream())
+            return
         N.call('pnp_csmri_svrg_outer_iteration', self._h, _p(z), _p(w), _p(mu), _p(mask_bits), _p(yh), _p(alpha_vec), _p(selbits), int(T2),
                float(lr), int(mini_batch_size), float(sigma_modifier), float(fallback_sigma), _p(xrec), _p(sse_log), int(log_row0),
                int(sse_log.shape[0]), _p(sigma_out), _stream())
@@ -319,6 +361,10 @@ def prox_tv(z, sigma_in=None, sigma_modifier=1.0, fallback_sigma=0.0, xrec=None,
     if xrec is not None and sse is None:
         sse = torch.empty(B, dtype=torch.float64, device=z.device)
     sigma_out = sigma_out if sigma_out is not None else torch.empty(B, dtype=z.dtype, device=z.device)
+    if isinstance(sigma_modifier, torch.Tensor):                # float64 [B]: per-problem strength
+        N.call('pnp_prox_tv_pp', _p(z), _p(out), H, W, B, _DT[z.dtype], _p(sigma_in), 0.0, _p(_pp(sigma_modifier, B)[1]),
+               float(fallback_sigma), _p(xrec), _p(sse), _p(sigma_out), _stream())
+        return out, sse, sigma_out
     N.call('pnp_prox_tv', _p(z), _p(out), H, W, B, _DT[z.dtype], _p(sigma_in), float(sigma_modifier),
            float(fallback_sigma), _p(xrec), _p(sse), _p(sigma_out), _stream())
     return out, sse, sigma_out
@@ -333,6 +379,10 @@ def prox_wavelet2d(z, sigma_in=None, sigma_modifier=1.0, fallback_sigma=0.0, xre
     if xrec is not None and sse is None:
         sse = torch.empty(B, dtype=torch.float64, device=z.device)
     sigma_out = sigma_out if sigma_out is not None else torch.empty(B, dtype=z.dtype, device=z.device)
+    if isinstance(sigma_modifier, torch.Tensor):                # float64 [B]: per-problem strength
+        N.call('pnp_prox_wavelet2d_pp', _p(z), _p(out), H, W, B, _DT[z.dtype], _p(sigma_in), 0.0, _p(_pp(sigma_modifier, B)[1]),
+               float(fallback_sigma), _p(xrec), _p(sse), _p(sigma_out), _stream())
+        return out, sse, sigma_out
     N.call('pnp_prox_wavelet2d', _p(z), _p(out), H, W, B, _DT[z.dtype], _p(sigma_in), float(sigma_modifier),
            float(fallback_sigma), _p(xrec), _p(sse), _p(sigma_out), _stream())
     return out, sse, sigma_out
@@ -522,10 +572,19 @@ def pr_grad_batch(A, w, y, rows=None, scale=1.0, workspace=None, out=None):
     return out
 
 
-def draw_thresholds(M, B, mb, seed, step0, nsteps=1, out=None, step_dev=None, device='cuda'):
-    """Device-side draws of `mb` of M measurements for B problems and `nsteps` steps -> descriptors int64 [nsteps, B, 2]."""
+def draw_thresholds(M, B, mb, seed, step0, nsteps=1, out=None, step_dev=None, device='cuda', draw_id=None):
+    """Device-side draws of `mb` of M measurements for B problems and `nsteps` steps -> descriptors int64 [nsteps, B, 2].
+    mb: an int, or an int32 [B] device tensor; draw_id: int32 [B] ids absorbed in place of the batch index (pnp_draw_thresholds_pp)."""
     require_gpu()
     out = out if out is not None else torch.empty((nsteps, B, 2), dtype=torch.int64, device=device)
+    if isinstance(mb, torch.Tensor) or draw_id is not None:
+        if not isinstance(mb, torch.Tensor):
+            mb = torch.full((B,), int(mb), dtype=torch.int32, device=out.device)
+        assert mb.dtype == torch.int32 and tuple(mb.shape) == (B,)
+        assert draw_id is None or (draw_id.dtype == torch.int32 and tuple(draw_id.shape) == (B,))
+        N.call('pnp_draw_thresholds_pp', int(M), int(B), _p(mb), _p(draw_id), int(seed) & (2 ** 64 - 1), int(step0) & 0xFFFFFFFF,
+               int(nsteps), _p(step_dev), _p(out), _stream())
+        return out
     N.call('pnp_draw_thresholds', int(M), int(B), int(mb), int(seed) & (2 ** 64 - 1), int(step0) & 0xFFFFFFFF, int(nsteps),
            _p(step_dev), _p(out), _stream())
     return out

@@ -152,7 +152,7 @@ def make_prox(denoiser, **kw):
 
 def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta, n_inner, mini_batch_size=None, T2=None,
                 hist_size=50, H=256, W=256, dtype=torch.float32, max_batch=128, seeding='generator', variant='svrg', run_seed=1,
-                keep_trace=False, graph=True, kernel='Minimal', lr_decay=1.0, denoiser_kwargs=None):
+                keep_trace=False, graph=True, kernel='Minimal', lr_decay=1.0, denoiser_kwargs=None, sigma_modifier=None):
     """Runner for `run_sweep` / `grid_search` over any cell of the reference's sweep (script_diff_sampratio_set12.py:23-25,
     41-51, 64-131): problem in {'csmri', 'deblur', 'pr'} x algorithm in {'gd', 'sgd', 'svrg', 'saga', 'sarah'} x denoiser in
     {'tv', 'nlm', factory}; `n_inner` inner iterations (prox evaluations of the stepped iterate) per item, hyper-parameters
@@ -174,7 +174,12 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
                          in its order, np.random.seed(run_seed), then the loop's draws in ITS order (one select_mb per inner
                          iteration; pnp_saga: one select_mb for the table, then select_mb + np.random.choice(hist_size, 1) per
                          iteration, algorithms/pnp_saga.py:25-29,43-47) -- so an item's trajectory equals the reference loop's
-                         (and the oracle's) on the same seeds."""
+                         (and the oracle's) on the same seeds.
+    sigma_modifier: shorthand for denoiser_kwargs={'sigma_modifier': ...}, so that a search grid can name it as a key.
+    Beside `run(items)` the runner offers the pieces of a trial-batched grid (`grid_search(batch_trials=True)`):
+    `run.prepare_data(items)` builds a rank's batches WITHOUT engines, `run.run_trials(data, trials, max_batch_trials)` runs a list
+    of trials ({'eta', 'mini_batch_size', 'sigma_modifier'} overrides) on them as tiled batches, `run.data_key` says which runners
+    may share prepared data."""
     from . import engine as E
     from . import problems as P
     if problem not in PROBLEMS or algorithm not in ALGORITHMS:
@@ -186,6 +191,8 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
     if seeding == 'device' and problem != 'csmri':
         raise ValueError(f"seeding='device' is supported for problem='csmri' only (got {problem!r}); use 'generator' or 'legacy'")
     mb, dkw = mini_batch_size, dict(denoiser_kwargs or {})
+    if sigma_modifier is not None:
+        dkw['sigma_modifier'] = sigma_modifier
     dev_images = []                                              # seeding='counter' / 'device': the image set in HBM, uploaded on first use
 
     def group_key(it):
@@ -265,7 +272,7 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
     class _Chunk:
         """One batch of a rank's items on its engine: built (data in HBM) by `prepare`, advanced by `advance`."""
 
-        def __init__(self, chunk):
+        def __init__(self, chunk, with_engine=True):
             self.items = chunk
             if seeding == 'legacy':
                 self.batch, draws = build_legacy(chunk)
@@ -277,6 +284,10 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
                 self.batch, self.idx_d, self.rs = build_counter(dev_images[0], chunk), None, None
             else:
                 self.batch, self.idx_d, self.rs = build_generator(chunk), None, None
+            self.done = 0
+            if not with_engine:                                 # data only: trial slabs put their engines on tiles of it
+                self.tiles = {}
+                return
             kw = dict(seed=chunk[0]['id'] + 1)
             if algorithm == 'saga' and self.idx_d is not None:
                 kw['idx0'] = self.idx_d[0]
@@ -317,12 +328,68 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
                 out.append(r)
             return out
 
-    def prepare(items):
-        """Build this rank's batches (problem data resident in HBM, engines constructed): everything before the iterations."""
+    class _TrialSlab(_Chunk):
+        """Some trials of a grid on ONE engine: the data of a prepared chunk tiled once per trial (problem t * n + i = trial t
+        of item i), per-problem eta / mini_batch_size / sigma_modifier, and the chunk's own seed and item-keyed minibatch
+        streams (draw_id = i) -- so item i walks in every trial the trajectory the per-trial runner gives it."""
+
+        def __init__(self, base, trials):
+            n, nt = len(base.items), len(trials)
+            self.items, self.idx_d, self.rs, self.done = base.items * nt, None, None, 0
+            if nt not in base.tiles:
+                base.tiles = {nt: base.batch.tile(nt)}           # (one tiled copy at a time: slabs of one size reuse it)
+            self.batch = base.tiles[nt]
+            lay = trial_layout(n, trials, {'eta': eta, 'mini_batch_size': mb, 'sigma_modifier': dkw.get('sigma_modifier', 1.0)})
+            pkw = dict(dkw)
+            if any('sigma_modifier' in tr for tr in trials):
+                pkw['sigma_modifier'] = lay['sigma_modifier']
+            self.eng = E.make_engine(self.batch, make_prox(denoiser, **pkw), lay['eta'], T2,
+                                     None if algorithm == 'gd' else lay['mini_batch_size'], lr_decay=lr_decay, variant=variant,
+                                     algorithm=algorithm, hist_size=hist_size, seed=base.items[0]['id'] + 1, draw_id=lay['draw_id'])
+
+    def _group_chunks(items):
         groups = {}
         for it in items:
             groups.setdefault(group_key(it), []).append(it)
-        return [_Chunk(g[s0:s0 + max_batch]) for g in groups.values() for s0 in range(0, len(g), max_batch)]
+        return [g[s0:s0 + max_batch] for g in groups.values() for s0 in range(0, len(g), max_batch)]
+
+    def prepare(items):
+        """Build this rank's batches (problem data resident in HBM, engines constructed): everything before the iterations."""
+        return [_Chunk(c) for c in _group_chunks(items)]
+
+    def check_trials(trials):
+        """What a trial-batched run supports, each refusal naming the offender."""
+        if problem != 'csmri':
+            raise ValueError(f"batch_trials: problem {problem!r} is not supported (only 'csmri')")
+        if algorithm not in ('gd', 'sgd', 'svrg'):
+            raise ValueError(f"batch_trials: algorithm {algorithm!r} is not supported (only 'gd', 'sgd', 'svrg')")
+        if denoiser == 'nlm':
+            raise ValueError("batch_trials: denoiser 'nlm' is not supported (NLMProx has no per-problem form)")
+        if seeding == 'legacy':
+            raise ValueError("batch_trials: seeding 'legacy' is not supported (host index lists; use 'counter' or 'generator')")
+        for tr in trials:
+            bad = [k for k in tr if k not in PER_PROBLEM_KEYS]
+            if bad or (callable(denoiser) and 'sigma_modifier' in tr):
+                raise ValueError(f'batch_trials: trial key {(bad or ["sigma_modifier"])[0]!r} has no per-problem form here '
+                                 f'(per-problem keys: {PER_PROBLEM_KEYS}; a prox factory takes no sigma_modifier)')
+
+    def prepare_data(items):
+        """This rank's batches as `prepare` chunks them (the same groups, order and max_batch), data only."""
+        return [_Chunk(c, with_engine=False) for c in _group_chunks(items)]
+
+    def run_trials(data, trials, max_batch_trials=1024):
+        """trials: dicts of per-problem overrides -> [results of run(items) per trial], on `data` = prepare_data(items): every
+        chunk runs its trials in slabs of at most max_batch_trials problems (at least one trial)."""
+        check_trials(trials)
+        out = [[] for _ in trials]
+        for base in data:
+            n = len(base.items)
+            for t0, t1 in trial_slabs(len(trials), n, max_batch_trials):
+                slab = _TrialSlab(base, trials[t0:t1])
+                slab.advance(n_inner)
+                for j, r in enumerate(slab.results()):
+                    out[t0 + j // n].append(r)
+        return [sorted(rs, key=lambda r: r['id']) for rs in out]
 
     def advance(state, n):
         for c in state:
@@ -345,6 +412,8 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
         return collect(state)
 
     run.prepare, run.advance, run.collect, run.warm = prepare, advance, collect, warm
+    run.prepare_data, run.run_trials, run.check_trials = prepare_data, run_trials, check_trials
+    run.data_key = (id(images), problem, seeding, H, W, dtype, max_batch, kernel)
     run.names = (_REF_NAMES[problem], 'CNN' if callable(denoiser) else _REF_NAMES.get(denoiser, str(denoiser)), 'pnp_' + algorithm)
     return run
 
@@ -392,20 +461,72 @@ def best_over_trials(per_trial):
     return [best[k] for k in sorted(best)]
 
 
-def grid_search(items, make_runner, grid, group=None):
+PER_PROBLEM_KEYS = ('eta', 'mini_batch_size', 'sigma_modifier')
+
+
+def group_trials(trials):
+    """Trials (dicts, grid order) -> [(structural params, [trial indices])]: trials that agree in every key that is not per
+    problem (T2 included: it changes the schedule) form a group, groups and members in order of first appearance."""
+    groups = {}
+    for t, tr in enumerate(trials):
+        key = tuple((k, tr[k]) for k in tr if k not in PER_PROBLEM_KEYS)
+        groups.setdefault(key, []).append(t)
+    return [(dict(key), idx) for key, idx in groups.items()]
+
+
+def trial_slabs(n_trials, n_items, max_batch_trials):
+    """[t0, t1) trial ranges of the slabs: as many whole trials as fit into max_batch_trials problems, at least one."""
+    per = max(1, int(max_batch_trials) // max(1, int(n_items)))
+    return [(t0, min(t0 + per, n_trials)) for t0 in range(0, n_trials, per)]
+
+
+def trial_layout(n_items, trials, defaults):
+    """Per-problem vectors of a slab of len(trials) trials over n_items items: problem b = t * n_items + i carries trial t's
+    value of every per-problem key (`defaults` where the trial names none) and draw_id[b] = i."""
+    nt = len(trials)
+    lay = {'draw_id': np.tile(np.arange(n_items, dtype=np.int64), nt)}
+    for k in PER_PROBLEM_KEYS:
+        if defaults.get(k) is None and not any(k in tr for tr in trials):
+            lay[k] = None
+            continue
+        vals = np.repeat(np.array([tr.get(k, defaults.get(k)) for tr in trials]), n_items)
+        lay[k] = vals.astype(np.int32 if k == 'mini_batch_size' else np.float64)
+    return lay
+
+
+def grid_search(items, make_runner, grid, group=None, *, batch_trials=False, max_batch_trials=1024):
     """The sweep the reference scripts run (process_img, script_diff_sampratio_set12.py:103-131): for every work item
     search the hyper-parameters and keep the best trial.  `make_runner(**params)` returns a runner as `run_sweep`
     takes; each rank runs every trial on ITS shard of the items (one batched engine per trial), the reduction over
-    trials is local and the single gather at the end carries one small row per item."""
+    trials is local and the single gather at the end carries one small row per item.
+    batch_trials=True (CSMRI; gd, sgd, svrg; not NLM; not legacy seeding -- ValueError otherwise): the trials of a rank run as
+    ONE batch per chunk instead of one after the other.  Keys 'eta', 'mini_batch_size', 'sigma_modifier' become
+    per-problem vectors; trials are grouped by every other key (T2 included), the problem data of a chunk is prepared once and
+    shared by all groups, and a group runs on the chunk tiled once per trial in slabs of at most max_batch_trials problems.
+    The rows returned are those of batch_trials=False."""
     if dist.is_available() and dist.is_initialized():
         rank, world = dist.get_rank(group), dist.get_world_size(group)
     else:
         rank, world = 0, 1
     mine = shard(items, rank, world)
+    trials = grid_points(grid)
     per_trial = []
-    for params in grid_points(grid):
-        res = make_runner(**params)(mine) if mine else []
-        per_trial.append((params, [{k: v for k, v in r.items() if k != 'z'} for r in res]))
+    if batch_trials:
+        per_trial, data = [None] * len(trials), {}
+        for _, idx in group_trials(trials):
+            run = make_runner(**trials[idx[0]])
+            if not hasattr(run, 'run_trials'):
+                raise ValueError('batch_trials needs runners of sweep.make_runner (run.prepare_data / run.run_trials)')
+            sub = [{k: v for k, v in trials[t].items() if k in PER_PROBLEM_KEYS} for t in idx]
+            run.check_trials(sub)
+            if run.data_key not in data:
+                data[run.data_key] = run.prepare_data(mine)
+            for t, res in zip(idx, run.run_trials(data[run.data_key], sub, max_batch_trials)):
+                per_trial[t] = (trials[t], [{k: v for k, v in r.items() if k != 'z'} for r in res])
+    else:
+        for params in trials:
+            res = make_runner(**params)(mine) if mine else []
+            per_trial.append((params, [{k: v for k, v in r.items() if k != 'z'} for r in res]))
     return gather_results(best_over_trials(per_trial), 0, group)
 
 

@@ -6,7 +6,9 @@ static checks (check_w44_isa.py, check_w44_gaps.py, check_w44b_isa.py, check_fus
 
 --against is the check of a kernel refactor: REV's pnp_svrg_amd/csrc and include trees are taken from `git archive` into a
 temporary directory, both files are compiled, and the listings must be equal (exit code 0) -- apart from the one symbol hipcc
-derives from a hash of the source text, `__hip_cuid_<hash>`, which is masked."""
+derives from a hash of the source text, `__hip_cuid_<hash>`, which is masked.
+    python tools/hip_listing.py csmri_fused.hip --against REV --per-kernel   ... kernel by kernel: for a change that ADDS kernels to a
+                                                                              file and must leave the existing ones as they are"""
 import argparse
 import os
 import re
@@ -44,15 +46,37 @@ def masked(text):
     return re.sub(r'__hip_cuid_[0-9a-f]+', '__hip_cuid_', text)
 
 
+def kernels(text):
+    """{kernel symbol: its code and its .amdhsa_kernel descriptor block} of a listing, with the per-file numbering of local labels
+    (.LBB<function>_<block>, .Lfunc_end<function>) masked: adding a kernel to a file renumbers the others without changing them."""
+    text = re.sub(r'BB\d+_', 'BB_', re.sub(r'\.Lfunc_(begin|end)\d+', r'.Lfunc_\1', masked(text)))
+    text = re.sub(r'[ \t]*;.*$', '', text, flags=re.M)          # comments (their column depends on the width of a label number)
+    out = {}
+    for m in re.finditer(r'^\t\.amdhsa_kernel (\S+)\n(.*?)^\t\.end_amdhsa_kernel', text, re.M | re.S):
+        name = m.group(1)
+        body = re.search(r'^' + re.escape(name) + r':.*?^\.Lfunc_end:', text, re.M | re.S)
+        out[name] = (body.group(0) if body else '') + '\n' + m.group(2)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('name', help='file name under pnp_svrg_amd/csrc')
     ap.add_argument('-D', dest='defines', action='append', default=[], help='extra define (NAME or NAME=VALUE)')
     ap.add_argument('-o', dest='out', help='write the listing here (default: standard output)')
     ap.add_argument('--against', metavar='REV', help='compare with the listing of the file as of this git revision')
+    ap.add_argument('--per-kernel', action='store_true', help='with --against: compare kernel by kernel -- every kernel REV has must '
+                    'exist and be equal (code and descriptor); kernels REV does not have are listed as new')
     a = ap.parse_args()
     defines = ['-D' + d for d in a.defines]
     text = listing(a.name, defines)
+    if a.against and a.per_kernel:
+        old, new = kernels(listing_at(a.against, a.name, defines)), kernels(text)
+        bad = [k for k in old if old[k] != new.get(k)]
+        added = [k for k in new if k not in old]
+        print(f'{a.name}: {len(old)} kernels of {a.against}: ' + (f'{len(bad)} DIFFER or are missing: {bad}' if bad else 'all equal')
+              + f'; {len(added)} new')
+        return 1 if bad or not old else 0
     if a.against:
         old = masked(listing_at(a.against, a.name, defines)).split('\n')
         new = masked(text).split('\n')
