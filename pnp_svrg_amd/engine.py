@@ -7,15 +7,8 @@ where many reconstructions (image x sampling ratio x SNR x trial) are independen
 iteration: squared errors (for PSNR) accumulate in a device log.  The drop-in loops of `algorithms.py` (golden-pinned)
 are the specification: every engine is tested to walk the same trajectory as B drop-in loops fed the same minibatches.
 
-A *batch problem* (CsmriBatch, DeblurBatch, PrBatch) holds the device-resident data of B problems and offers
-    grad_full(z, out, alpha, beta, c1)                         alpha * grad_full(z) + beta * c1
-    grad_stoch(z, mbs, j, out, alpha, beta, c1)                alpha * grad_stoch(z, minibatch j) + beta * c1
-    grad_stoch_diff(z, w, mbs, j, out, alpha, beta, c1, gamma, c2)
-                                                               alpha * (gs(z) - gs(w)) + beta * c1 + gamma * c2
-    minibatches(n) / draw(mbs, mb, seed, step0, nsteps) / set_host(mbs, j, idx)
-Minibatches are drawn on the device by default (counter-based keys + a threshold per (problem, step): csrc/draw.h;
-the selection itself is re-derived inside the gradient kernels and never stored); for reference-identical runs pass
-index lists drawn from the legacy `np.random` stream (`step(idx)`).
+The batch problems (CsmriBatch, DeblurBatch, PrBatch: the data of B problems and their gradients) are in `batches.py`, the prox
+adapters (TVProx, DnCNNProx, NLMProx) in `prox.py`; both are re-exported here.
 
 Per-problem hyper-parameters (a hyper-parameter grid as one batch): GdEngine, SgdEngine and SvrgEngine take `eta` and
 `mini_batch_size`, and TVProx takes `sigma_modifier`, as a scalar or as a [B] array.  A scalar takes exactly the plain calls; an
@@ -27,592 +20,10 @@ import numpy as np
 import torch
 
 from . import ops
+from .batches import Minibatches, _BatchBase, CsmriBatch, DeblurBatch, PrBatch  # noqa: F401  (re-exported)
+from .prox import TVProx, DnCNNProx, NLMProx  # noqa: F401  (re-exported)
 
 
-class Minibatches:
-    """n slots of per-problem minibatch selections: threshold descriptors of device draws (int64 [n, B, 2]) or
-    host-provided selections (slot -> whatever the batch problem's kernels take)."""
-
-    def __init__(self, n, B, device, bits_shape=None):
-        self.n = n
-        self.mbd = torch.zeros((n, B, 2), dtype=torch.int64, device=device)
-        # CSMRI: the device-drawn selections themselves, bit-packed (what the column pass reads)
-        self.selbits = torch.zeros((n, B) + tuple(bits_shape), dtype=torch.int32, device=device) if bits_shape else None
-        self.host = [None] * n
-
-
-class _BatchBase:
-    def minibatches(self, n):
-        return Minibatches(n, self.B, self.device)
-
-    def _check_mb(self, mb):
-        if np.ndim(mb) != 0:                                    # per problem: every entry against its own problem's population
-            mb = np.asarray(mb)
-            cap = np.broadcast_to(np.asarray(getattr(self, 'M0', self.max_mb)), (self.B,))
-            if mb.shape != (self.B,) or not np.issubdtype(mb.dtype, np.integer):
-                raise ValueError(f'per-problem mini_batch_size: {self.B} integers, got shape {mb.shape} of {mb.dtype}')
-            bad = np.flatnonzero((mb < 1) | (mb > cap))
-            if bad.size:
-                b = int(bad[0])
-                raise ValueError(f"Cannot take a larger sample than population when 'replace=False' (problem {b}: mini_batch_size "
-                                 f'{int(mb[b])}, population {int(cap[b])}; sizes must be >= 1)')
-            return
-        if mb > self.max_mb:
-            # np.random.choice(..., replace=False) raises the same way (problems/problem.py:110-117, CSMRI.py:66-74)
-            raise ValueError(f"Cannot take a larger sample than population when 'replace=False' (mini_batch_size {mb} > {self.max_mb})")
-
-    @staticmethod
-    def upload_images(images, H=256, W=256, dtype=torch.float32, device='cuda'):
-        """The image set of `generate`, each image min-max normalised in float64 (sweep._norm01), as one [n, H, W] device tensor."""
-        xs = []
-        for img in images:
-            x = np.asarray(img, np.float64)
-            if x.shape != (H, W):
-                raise ValueError(f'image of shape {x.shape}: generate needs {H} x {W} images')
-            xs.append((x - x.min()) / (x.max() - x.min()))
-        return torch.from_numpy(np.stack(xs)).to(device, dtype).contiguous()
-
-    @classmethod
-    def _generate_inputs(cls, images, items, H, W, dtype, device):
-        """What every `generate` starts from: the image set on the device and the per-item [B] parameter vectors of the
-        counter-based stream (image_idx int32, snr_fac float64, seed, id as int64 holding the 64-bit values)."""
-        ops.require_gpu()
-        if not isinstance(images, torch.Tensor):
-            images = cls.upload_images(images, H, W, dtype, device)
-        if images.dtype != dtype or tuple(images.shape[1:]) != (H, W):
-            raise ValueError(f'image set of dtype {images.dtype}, shape {tuple(images.shape)}: generate needs [n, {H}, {W}] {dtype}')
-        if len(items) < 1 or any(not 0 <= it['image'] < images.shape[0] for it in items):
-            raise ValueError('generate needs at least one item and image indices inside the image set')
-        u64 = lambda v: np.array([int(x) & (2 ** 64 - 1) for x in v], np.uint64).view(np.int64)
-        par = [np.array([it['image'] for it in items], np.int32),
-               np.array([10.0 ** (-np.float64(it['snr']) / 10) for it in items], np.float64),
-               u64([it['seed'] for it in items]), u64([it['id'] for it in items])]
-        return images, [torch.from_numpy(a).to(images.device) for a in par]
-
-    def psnr_init(self):
-        """rounded PSNR of Xinit per problem (problems/problem.py:33-35)."""
-        sse = ops.sse(self.xinit, self.xrec).cpu().numpy()
-        with np.errstate(divide='ignore'):
-            return np.around(10 * np.log10(1.0 / (sse / self.N)), 2)
-
-
-class CsmriBatch(_BatchBase):
-    """Device-resident data of B CSMRI problems (reference problems/CSMRI.py:12-41 per problem).  Masks may have
-    different numbers of sampled locations (the reference draws Bernoulli masks, CSMRI.py:43-45): grad_full's 1/M0
-    is a per-problem device vector."""
-    kind = 'csmri'
-
-    def __init__(self, xrec, mask, Y, xinit, dtype=torch.float32, device='cuda'):
-        ops.require_gpu()
-        B, H, W = xrec.shape
-        self.B, self.H, self.W, self.N, self.dtype = B, H, W, H * W, dtype
-        self.device = torch.device(device)
-        cdt = torch.complex64 if dtype == torch.float32 else torch.complex128
-        self.plan = ops.CsmriPlan(H, W, B, dtype)
-        self.xrec = torch.from_numpy(np.ascontiguousarray(xrec, np.float64)).to(device, dtype)
-        self.xinit = torch.from_numpy(np.ascontiguousarray(xinit, np.float64)).to(device, dtype).reshape(B, H, W)
-        self.mask_np = np.ascontiguousarray(mask, np.uint8).reshape(B, H, W)
-        self.M0 = self.mask_np.reshape(B, -1).sum(1).astype(np.int64)
-        self.max_mb = int(self.M0.min())
-        self.inv_m0 = torch.from_numpy(1.0 / self.M0.astype(np.float64)).to(device, dtype)
-        self.maskT = self.plan.sel_from_dense(torch.from_numpy(self.mask_np).to(device))
-        self.bits = self.plan.pack_mask(self.maskT)
-        self.YT = torch.from_numpy(np.ascontiguousarray(np.swapaxes(Y, 1, 2))).to(device, cdt).contiguous()
-        self.yh_full = self.plan.pack_y(self.YT, self.maskT)
-
-    @classmethod
-    def synthetic(cls, B, H=256, W=256, sample_prob=0.2, snr=20.0, seed=0, dtype=torch.float32, bernoulli=True):
-        """B synthetic problems: smoothed-noise images, complex data with real noise on the support.
-        bernoulli=True draws each mask entry with probability p like the reference (CSMRI.py:43-45; the number of
-        sampled points then differs per problem), False draws exactly round(p*N) points."""
-        rng = np.random.default_rng(seed)
-        N = H * W
-        xrec = np.empty((B, H, W))
-        mask = np.zeros((B, N), np.uint8)
-        Y = np.empty((B, H, W), np.complex128)
-        xinit = np.empty((B, N))
-        for b in range(B):
-            x = rng.random((H, W))
-            p = np.pad(x, 2, mode='wrap')
-            y = sum(p[i:i + H, j:j + W] for i in range(5) for j in range(5)) / 25.0
-            y = (y - y.min()) / (y.max() - y.min())
-            xrec[b] = np.round(y * 255) / 255.0
-            xrec[b] = (xrec[b] - xrec[b].min()) / (xrec[b].max() - xrec[b].min())
-            if bernoulli:
-                mask[b] = rng.random(N) < sample_prob
-            else:
-                mask[b, rng.choice(N, int(round(sample_prob * N)), replace=False)] = 1
-            mk = mask[b].reshape(H, W)
-            Y0 = mk * np.fft.fft2(xrec[b])
-            sigma = np.sqrt(np.linalg.norm(Y0.ravel()) / 10 ** (snr / 10) / H / W)     # problem.py:58-61
-            Y[b] = Y0 + mk * rng.normal(0, sigma, (H, W))
-            xi = np.absolute(np.fft.ifft2(Y[b])).ravel()
-            xinit[b] = (xi - xi.min()) / (xi.max() - xi.min())
-        return cls(xrec, mask.reshape(B, H, W), Y, xinit, dtype=dtype)
-
-    @property
-    def mask_np(self):
-        """[B, H, W] uint8 sampling masks on the host; a generated batch reads them back on first use."""
-        if self._mask_np is None:
-            self._mask_np = np.ascontiguousarray(self.maskT.cpu().numpy().swapaxes(1, 2))
-        return self._mask_np
-
-    @mask_np.setter
-    def mask_np(self, m):
-        self._mask_np = m
-
-    @classmethod
-    def generate(cls, images, items, H=256, W=256, dtype=torch.float32, device='cuda'):
-        """The problems of `items` (dicts of sweep.make_items: id, image, alpha, snr, seed) generated ON THE DEVICE from the
-        counter-based stream of include/pnp_hip.h (pnp_csmri_generate): Bernoulli mask, masked spectrum, real noise on the
-        support, Xinit -- problems/CSMRI.py:12-59 per item, NOT NumPy's streams.  images: a list of H x W arrays, or the
-        tensor `upload_images` made of them (upload once, generate many batches).  Host work: the [B] parameter vectors and
-        one read-back of M0."""
-        ops.require_gpu()
-        if not isinstance(images, torch.Tensor):
-            images = cls.upload_images(images, H, W, dtype, device)
-        B = len(items)
-        if B < 1 or any(not 0 <= it['image'] < images.shape[0] for it in items):
-            raise ValueError('generate needs at least one item and image indices inside the image set')
-        self = cls.__new__(cls)
-        self.B, self.H, self.W, self.N, self.dtype = B, H, W, H * W, dtype
-        self.device = images.device
-        self.plan = ops.CsmriPlan(H, W, B, dtype)
-        u64 = lambda v: np.array([int(x) & (2 ** 64 - 1) for x in v], np.uint64).view(np.int64)
-        thr = [min(max(int(np.floor(np.float64(it['alpha']) * 2.0 ** 32)), 0), 2 ** 32) for it in items]
-        par = [np.array([it['image'] for it in items], np.int32), np.array(thr, np.int64),
-               np.array([10.0 ** (-np.float64(it['snr']) / 10) for it in items], np.float64),
-               u64([it['seed'] for it in items]), u64([it['id'] for it in items])]
-        o = self.plan.generate(images, *[torch.from_numpy(a).to(self.device) for a in par])
-        self.xrec, self.xinit, self.maskT, self.bits = o['xrec'], o['xinit'], o['maskT'], o['bits']
-        self.YT, self.yh_full, self.inv_m0, self.sigma = o['YT'], o['yh_full'], o['inv_m0'], o['sigma']
-        self.M0 = o['M0'].cpu().numpy().astype(np.int64)
-        self.max_mb = int(self.M0.min())
-        self._mask_np = None
-        return self
-
-    def tile(self, n):
-        """A batch of n * B problems whose data is this batch's repeated n times along B (problem t * B + i = this batch's
-        problem i): device copies only, no regeneration and no host round trip -- what a trial-batched grid runs on."""
-        n = int(n)
-        if n < 1:
-            raise ValueError('tile(n) needs n >= 1')
-        t = type(self).__new__(type(self))
-        t.B, t.H, t.W, t.N, t.dtype, t.device = self.B * n, self.H, self.W, self.N, self.dtype, self.device
-        t.plan = ops.CsmriPlan(self.H, self.W, t.B, self.dtype)
-        for name in ('xrec', 'xinit', 'maskT', 'bits', 'YT', 'yh_full', 'inv_m0', 'sigma'):
-            v = getattr(self, name, None)
-            if v is not None:
-                setattr(t, name, v.repeat((n,) + (1,) * (v.dim() - 1)).contiguous())
-        t.M0, t.max_mb = np.tile(self.M0, n), self.max_mb
-        t._mask_np = None if self._mask_np is None else np.tile(self._mask_np, (n, 1, 1))
-        return t
-
-    @classmethod
-    def from_problems(cls, probs, dtype=torch.float32, device='cuda'):
-        """From reference-style problem objects (anything with Xrec, mask, Y, Xinit: problems.CSMRI, the oracle's)."""
-        return cls(np.stack([p.Xrec for p in probs]), np.stack([p.mask for p in probs]), np.stack([p.Y for p in probs]),
-                   np.stack([p.Xinit for p in probs]), dtype=dtype, device=device)
-
-    def draw_minibatches(self, n_steps, mb, seed=1):
-        """[n_steps][B][mb] int32 flat k-space indices, each row a uniform draw without replacement
-        from that problem's mask support (CSMRI.py:66-74 semantics, fast Generator stream)."""
-        self._check_mb(mb)
-        rng = np.random.default_rng(seed)
-        out = np.empty((n_steps, self.B, mb), np.int32)
-        for b in range(self.B):
-            locs = np.flatnonzero(self.mask_np[b]).astype(np.int32)
-            for s in range(n_steps):
-                out[s, b] = rng.choice(locs, mb, replace=False)
-        return torch.from_numpy(out).to(self.device)
-
-    # ---- minibatch slots
-    def minibatches(self, n):
-        return Minibatches(n, self.B, self.device, bits_shape=(self.W, self.H // 32))
-
-    def draw(self, mbs, mb, seed, step0, nsteps=1, step_dev=None, draw_id=None):
-        """mb: an int, or per problem: [B] integers on the host (checked against each problem's population, then uploaded) or an
-        int32 [B] device tensor (taken as checked: the engines check their host copy once).  draw_id: int32 [B] device tensor,
-        the ids the minibatch streams absorb in place of the batch index."""
-        if not isinstance(mb, torch.Tensor):
-            self._check_mb(mb)
-            if np.ndim(mb) != 0:
-                mb = torch.from_numpy(np.ascontiguousarray(mb, np.int32)).to(self.device)
-        self.plan.draw_thresholds(self.bits, mb, seed, step0, nsteps, out=mbs.mbd[:nsteps], step_dev=step_dev,
-                                  selbits=mbs.selbits[:nsteps], draw_id=draw_id)
-        for j in range(nsteps):
-            mbs.host[j] = None
-
-    def set_host(self, mbs, j, idx):
-        """idx: int32 [B, mb] flat row-major k-space positions (np.flatnonzero(mask o minibatch))."""
-        mbs.host[j] = self.plan.sel_from_indices(idx, out=mbs.host[j] if isinstance(mbs.host[j], torch.Tensor) else None)
-
-    def _sel(self, mbs, j):
-        if mbs.host[j] is not None:
-            return dict(selT=mbs.host[j])
-        return dict(bits=mbs.selbits[j])
-
-    # ---- gradients
-    def grad_full(self, z, out, alpha=1.0, beta=0.0, c1=None):
-        return self.plan.grad(z, bits=self.bits, yh=self.yh_full, alpha=alpha, alpha_vec=self.inv_m0, beta=beta, c1=c1, out=out)
-
-    def grad_stoch(self, z, mbs, j, out, alpha=1.0, beta=0.0, c1=None):
-        return self.plan.grad(z, YT=self.YT, alpha=alpha, beta=beta, c1=c1, out=out, **self._sel(mbs, j))
-
-    def grad_stoch_diff(self, z, w, mbs, j, out, alpha=1.0, beta=0.0, c1=None, gamma=0.0, c2=None):
-        # one FFT pair: the data terms cancel (SURVEY F13)
-        return self.plan.grad(z, b=w, alpha=alpha, beta=beta, c1=c1, gamma=gamma, c2=c2, out=out, **self._sel(mbs, j))
-
-
-class DeblurBatch(_BatchBase):
-    """B Deblur / super-resolution problems sharing one blur kernel and one down-sampler (reference
-    problems/DeblurSR.py:17-147 per problem; the sweeps vary image, noise and seed, not the operator)."""
-    kind = 'deblur'
-
-    def __init__(self, xrec, Bk, Y, xinit, dtype=torch.float32, device='cuda', bilinear=None):
-        ops.require_gpu()
-        B, H, W = xrec.shape
-        self.B, self.H, self.W, self.N, self.dtype = B, H, W, H * W, dtype
-        self.device = torch.device(device)
-        self.plan = ops.DeblurPlan(H, W, B, dtype, Bk, bilinear=bilinear)
-        self.M = self.plan.M
-        self.max_mb = self.M
-        self.xrec = torch.from_numpy(np.ascontiguousarray(xrec, np.float64)).to(device, dtype)
-        self.xinit = torch.from_numpy(np.ascontiguousarray(xinit, np.float64)).to(device, dtype).reshape(B, H, W)
-        self.Y = torch.from_numpy(np.ascontiguousarray(Y, np.float64)).to(device, dtype).reshape(B, self.M)
-        self._tmp = None
-
-    @classmethod
-    def generate(cls, images, items, H=256, W=256, dtype=torch.float32, kernel='Minimal', scale_percent=100, device='cuda'):
-        """The problems of `items` (dicts of sweep.make_items; their alpha is NOT read: the operator comes from `kernel` and
-        `scale_percent`) generated ON THE DEVICE from the counter-based stream of include/pnp_hip.h (pnp_deblur_generate):
-        Y = S B x + noise, Xinit uniform in [0, 1) -- problems/DeblurSR.py:38-57 per item, NOT NumPy's streams.  images: a list of
-        H x W arrays, or the tensor `upload_images` made of them.  Also sets `sigma` ([B] float64, device)."""
-        from .problems import _deblur_taps
-        from .sweep import _minimal_kernel
-        images, par = cls._generate_inputs(images, items, H, W, dtype, device)
-        self = cls.__new__(cls)
-        self.B, self.H, self.W, self.N, self.dtype = len(items), H, W, H * W, dtype
-        self.device = images.device
-        self.plan = ops.DeblurPlan(H, W, self.B, dtype, _minimal_kernel(H, W, kernel), bilinear=_deblur_taps(H, W, scale_percent))
-        self.M = self.max_mb = self.plan.M
-        o = self.plan.generate(images, *par)
-        self.xrec, self.xinit, self.Y, self.sigma = o['xrec'], o['xinit'], o['Y'], o['sigma']
-        self._tmp = None
-        return self
-
-    @classmethod
-    def from_problems(cls, probs, dtype=torch.float32, device='cuda'):
-        p0 = probs[0]
-        return cls(np.stack([p.Xrec for p in probs]), p0.B, np.stack([p.Y for p in probs]),
-                   np.stack([p.Xinit for p in probs]), dtype=dtype, device=device,
-                   bilinear=getattr(p0, 'Bop', None) if isinstance(getattr(p0, 'Bop', None), tuple) else None)
-
-    @classmethod
-    def synthetic(cls, B, H=256, W=256, kernel='Minimal', snr=20.0, seed=0, dtype=torch.float32):
-        """B synthetic Deblur problems (scale_percent = 100): smoothed-noise images, the reference's "Minimal" or
-        "Identity" kernel (DeblurSR.py:80-89), noise and U(0,1) initialisation from a Generator stream."""
-        rng = np.random.default_rng(seed)
-        N = H * W
-        if kernel == 'Minimal':
-            Bk = np.zeros((H, W))
-            Bk[0, 0] = Bk[H // 2, H // 2] = Bk[H // 2, H // 3] = Bk[H // 2, H // 4] = 0.25
-        else:
-            Bk = np.zeros((H, W))
-            Bk[0, 0] = 1
-        Bk = Bk.ravel() / N
-        FB = np.fft.fft(Bk)
-        xrec = np.empty((B, H, W))
-        Y = np.empty((B, N))
-        for b in range(B):
-            x = rng.random((H, W))
-            p = np.pad(x, 2, mode='wrap')
-            y = sum(p[i:i + H, j:j + W] for i in range(5) for j in range(5)) / 25.0
-            xrec[b] = (y - y.min()) / (y.max() - y.min())
-            Y0 = np.real(np.fft.ifft(np.fft.fft(xrec[b].ravel()) * FB)) * np.sqrt(N)       # DeblurSR.py:119-120
-            sigma = np.sqrt(np.linalg.norm(Y0) / 10 ** (snr / 10) / H / W)
-            Y[b] = Y0 + rng.normal(0, sigma, N)
-        return cls(xrec, Bk, Y, rng.uniform(0.0, 1.0, (B, N)), dtype=dtype)
-
-    def draw_minibatches(self, n_steps, mb, seed=1):
-        self._check_mb(mb)
-        rng = np.random.default_rng(seed)
-        out = np.stack([[rng.choice(self.M, mb, replace=False) for _ in range(self.B)] for _ in range(n_steps)]).astype(np.int32)
-        return torch.from_numpy(out).to(self.device)
-
-    def draw(self, mbs, mb, seed, step0, nsteps=1, step_dev=None):
-        self._check_mb(mb)
-        ops.draw_thresholds(self.M, self.B, mb, seed, step0, nsteps, out=mbs.mbd[:nsteps], step_dev=step_dev)
-        for j in range(nsteps):
-            mbs.host[j] = None
-
-    def set_host(self, mbs, j, idx):
-        """idx: int32 [B, mb] measurement indices (np.flatnonzero of Problem.select_mb's indicator)."""
-        mbs.host[j] = ops.indicator_from_indices(idx, self.M, out=mbs.host[j] if isinstance(mbs.host[j], torch.Tensor) else None)
-
-    def _sel(self, mbs, j):
-        if mbs.host[j] is not None:
-            return dict(sel=mbs.host[j])
-        return dict(mbd=mbs.mbd[j])
-
-    def _axpby(self, g, alpha_applied, out, beta, c1, gamma=0.0, c2=None):
-        if c1 is None and c2 is None:
-            return g
-        return ops.axpbypcz(1.0, g, beta, c1, gamma, c2, out=out)
-
-    def _scratch(self, z):
-        if self._tmp is None:
-            self._tmp = torch.empty_like(z)
-        return self._tmp
-
-    def grad_full(self, z, out, alpha=1.0, beta=0.0, c1=None):
-        if c1 is None:
-            return self.plan.grad(z, self.Y, scale=alpha / self.M, out=out)
-        g = self.plan.grad(z, self.Y, scale=alpha / self.M, out=self._scratch(z))
-        return ops.axpbypcz(1.0, g, beta, c1, out=out)
-
-    def grad_stoch(self, z, mbs, j, out, alpha=1.0, beta=0.0, c1=None):
-        if c1 is None:
-            return self.plan.grad(z, self.Y, scale=alpha, out=out, **self._sel(mbs, j))
-        g = self.plan.grad(z, self.Y, scale=alpha, out=self._scratch(z), **self._sel(mbs, j))
-        return ops.axpbypcz(1.0, g, beta, c1, out=out)
-
-    def grad_stoch_diff(self, z, w, mbs, j, out, alpha=1.0, beta=0.0, c1=None, gamma=0.0, c2=None):
-        # gs(z) - gs(w) = B^T S^T sel (S B (z - w)) + (terms in y cancel): two gradients, one combine
-        t = self._scratch(z)
-        g1 = self.plan.grad(z, self.Y, scale=alpha, out=torch.empty_like(z), **self._sel(mbs, j))
-        g2 = self.plan.grad(w, self.Y, scale=alpha, out=t, **self._sel(mbs, j))
-        d = ops.axpbypcz(1.0, g1, -1.0, g2, out=g1)
-        if c1 is None and c2 is None:
-            return out.copy_(d) if out is not d else d
-        return ops.axpbypcz(1.0, d, beta, c1, gamma, c2, out=out)
-
-
-class PrBatch(_BatchBase):
-    """B phase-retrieval problems (reference problems/PR.py:13-87 per problem), each with its own dense M x N matrix."""
-    kind = 'pr'
-
-    def __init__(self, xrec, A, Y, xinit, dtype=torch.float32, device='cuda'):
-        ops.require_gpu()
-        B, H, W = xrec.shape
-        self.B, self.H, self.W, self.N, self.dtype = B, H, W, H * W, dtype
-        self.device = torch.device(device)
-        self.M = A.shape[1]
-        self.max_mb = self.M
-        self.xrec = torch.from_numpy(np.ascontiguousarray(xrec, np.float64)).to(device, dtype)
-        self.xinit = torch.from_numpy(np.ascontiguousarray(xinit, np.float64)).to(device, dtype).reshape(B, H, W)
-        self.A = torch.from_numpy(np.ascontiguousarray(A, np.float64)).to(device, dtype).contiguous()
-        self.Y = torch.from_numpy(np.ascontiguousarray(Y, np.float64)).to(device, dtype).reshape(B, self.M)
-        from . import _native as N
-        self._ws = torch.empty(B * N.lib().pnp_pr_workspace_elems(self.M, self.N), dtype=dtype, device=device)
-        self._tmp = None
-        self._mb = None
-
-    @classmethod
-    def generate(cls, images, items, H, W, M, dtype=torch.float32, max_iters=1000, check_every=8, device='cuda'):
-        """The problems of `items` (dicts of sweep.make_items; their alpha is NOT read: `M` is the number of measurements)
-        generated ON THE DEVICE from the counter-based stream of include/pnp_hip.h: the Gaussian A in HBM, Y = |A x| + noise
-        (pnp_pr_generate) and the spectral initialisation of all items at once with the stopping rule evaluated per item on the
-        device (pnp_pr_spectral_init_batch; one host synchronisation per `check_every` steps) -- problems/PR.py:26-63 per item,
-        NOT NumPy's streams.  Also sets `sigma` ([B] float64, device) and `spec_iters` ([B] int array: power-iteration steps per
-        item).  Raises ValueError naming the items that have not met the rule after `max_iters` steps."""
-        from . import _native as N
-        images, par = cls._generate_inputs(images, items, H, W, dtype, device)
-        self = cls.__new__(cls)
-        self.B, self.H, self.W, self.N, self.dtype = len(items), H, W, H * W, dtype
-        self.device = images.device
-        self.M = self.max_mb = int(M)
-        o = ops.pr_generate(images, *par, self.M)
-        self.xrec, self.A, self.Y, self.sigma = o['xrec'], o['A'], o['Y'], o['sigma']
-        self.xinit, iters, active = ops.pr_spectral_init_batch(self.A, self.Y, self.xrec, max_iters, check_every)
-        self.spec_iters = iters.cpu().numpy().astype(np.int64)
-        late = np.flatnonzero(active.cpu().numpy())
-        if late.size:
-            raise ValueError(f'spectral initialisation: items {[items[j]["id"] for j in late]} (batch positions {late.tolist()}) '
-                             f'still active after max_iters = {max_iters} steps')
-        self._ws = torch.empty(self.B * N.lib().pnp_pr_workspace_elems(self.M, self.N), dtype=dtype, device=self.device)
-        self._tmp = None
-        self._mb = None
-        return self
-
-    @classmethod
-    def from_problems(cls, probs, dtype=torch.float32, device='cuda'):
-        return cls(np.stack([p.Xrec for p in probs]), np.stack([p.A for p in probs]), np.stack([p.Y for p in probs]),
-                   np.stack([p.Xinit for p in probs]), dtype=dtype, device=device)
-
-    def draw_minibatches(self, n_steps, mb, seed=1):
-        self._check_mb(mb)
-        rng = np.random.default_rng(seed)
-        out = np.stack([[np.sort(rng.choice(self.M, mb, replace=False)) for _ in range(self.B)] for _ in range(n_steps)]).astype(np.int32)
-        return torch.from_numpy(out).to(self.device)
-
-    def draw(self, mbs, mb, seed, step0, nsteps=1, step_dev=None):
-        self._check_mb(mb)
-        self._mb = mb
-        ops.draw_thresholds(self.M, self.B, mb, seed, step0, nsteps, out=mbs.mbd[:nsteps], step_dev=step_dev)
-        for j in range(nsteps):
-            mbs.host[j] = None
-
-    def set_host(self, mbs, j, idx):
-        """idx: int32 [B, mb] row ids (np.flatnonzero of the indicator: ascending, like A[idx] in PR.py:82-83)."""
-        mbs.host[j] = idx.contiguous()
-
-    def _rows(self, mbs, j):
-        if mbs.host[j] is not None:
-            return mbs.host[j]
-        key = ('rows', j)
-        buf = getattr(mbs, '_rows', None)
-        if buf is None:
-            buf = mbs._rows = {}
-        if key not in buf:
-            buf[key] = torch.empty((self.B, self._mb), dtype=torch.int32, device=self.device)
-        return ops.rows_from_thresholds(self.M, self._mb, mbs.mbd[j], out=buf[key])
-
-    def _scratch(self, z):
-        if self._tmp is None:
-            self._tmp = torch.empty((self.B, self.N), dtype=self.dtype, device=self.device)
-        return self._tmp
-
-    def _g(self, z, rows, scale, out):
-        return ops.pr_grad_batch(self.A, z.reshape(self.B, self.N), self.Y, rows=rows, scale=scale, workspace=self._ws,
-                                 out=out.reshape(self.B, self.N)).reshape(out.shape)
-
-    def grad_full(self, z, out, alpha=1.0, beta=0.0, c1=None):
-        if c1 is None:
-            return self._g(z, None, alpha / self.M, out)
-        g = self._g(z, None, alpha / self.M, self._scratch(z))
-        return ops.axpbypcz(1.0, g.reshape(z.shape), beta, c1, out=out)
-
-    def grad_stoch(self, z, mbs, j, out, alpha=1.0, beta=0.0, c1=None):
-        rows = self._rows(mbs, j)
-        if c1 is None:
-            return self._g(z, rows, alpha, out)
-        g = self._g(z, rows, alpha, self._scratch(z))
-        return ops.axpbypcz(1.0, g.reshape(z.shape), beta, c1, out=out)
-
-    def grad_stoch_diff(self, z, w, mbs, j, out, alpha=1.0, beta=0.0, c1=None, gamma=0.0, c2=None):
-        rows = self._rows(mbs, j)
-        g1 = self._g(z, rows, alpha, torch.empty_like(z))
-        g2 = self._g(w, rows, alpha, self._scratch(z)).reshape(z.shape)
-        d = ops.axpbypcz(1.0, g1, -1.0, g2, out=g1)
-        if c1 is None and c2 is None:
-            return out.copy_(d) if out is not d else d
-        return ops.axpbypcz(1.0, d, beta, c1, gamma, c2, out=out)
-
-
-# ---------------------------------------------------------------------------------------------------------- prox
-class TVProx:
-    """denoisers/TV.py semantics for the engines (fused estimate_sigma + BayesShrink + error sum).
-    multi=True: the per-column 1-D prox (pnp_prox_tv), which the one-kernel iteration holds inside the gradient kernel.
-    multi=False: the 2-D wavelet prox (pnp_prox_wavelet2d): a kernel of its own after the gradient kernel, which in the
-    one-kernel iteration makes step + noise estimate (the DnCNNProx pattern) -- the engine then steps per iteration."""
-
-    def __init__(self, sigma_modifier=1.0, decay=1.0, denoise_strength=0.0, multi=True):
-        self.sigma_modifier, self.decay, self.denoise_strength, self.t = sigma_modifier, decay, denoise_strength, 0
-        self.multi = multi
-        self.fused_denoise = bool(multi)                        # one-kernel iteration: only the 1-D prox runs inside it
-
-    def bind(self, batch):
-        self.sig = torch.empty(batch.B, dtype=batch.dtype, device=batch.xrec.device)
-        if not isinstance(self.sigma_modifier, torch.Tensor) and np.ndim(self.sigma_modifier) != 0:
-            sm = np.ascontiguousarray(self.sigma_modifier, np.float64)      # per problem: a float64 [B] device vector, uploaded once
-            if sm.shape != (batch.B,):
-                raise ValueError(f'per-problem sigma_modifier: {batch.B} values, got shape {sm.shape}')
-            self.sigma_modifier = torch.from_numpy(sm).to(batch.xrec.device)
-
-    def __call__(self, z, xrec, sse_out):
-        self.t += 1
-        prox = ops.prox_tv if self.multi else ops.prox_wavelet2d
-        prox(z, sigma_modifier=self.sigma_modifier, fallback_sigma=self.denoise_strength * self.decay ** self.t,
-             xrec=xrec, out=z, sse=sse_out, sigma_out=self.sig)
-        return z
-
-    inplace = True                                              # writes its result into the iterate it was given
-
-    # one-kernel iteration (pnp_csmri_svrg_step): the 1-D prox runs inside the gradient kernel (fused_denoise); for the
-    # 2-D prox that kernel stops after the noise estimate and after_fused shrinks with it
-    def fused_args(self):
-        if not self.multi:
-            return dict(sigma_out=self.sig)
-        self.t += 1
-        return dict(sigma_modifier=self.sigma_modifier, fallback_sigma=self.denoise_strength * self.decay ** self.t, sigma_out=self.sig)
-
-    def after_fused(self, z, xrec, sse_out):
-        if not self.multi:
-            self.t += 1
-            ops.prox_wavelet2d(z, sigma_in=self.sig, sigma_modifier=self.sigma_modifier,
-                               fallback_sigma=self.denoise_strength * self.decay ** self.t, xrec=xrec, out=z, sse=sse_out,
-                               sigma_out=self.sig)
-        return z
-
-
-class DnCNNProx:
-    """denoisers/RealSN_DnCNN.py semantics for the engines.  The loop's estimate_sigma is still
-    evaluated (the reference computes it every iteration and this denoiser ignores it, F12)."""
-
-    def __init__(self, weights, sigma):
-        self.weights, self.sigma = weights, sigma
-
-    def bind(self, batch):
-        self.plan = ops.DncnnPlan(self.weights, batch.H, batch.W, batch.B)
-        self.sig = torch.empty(batch.B, dtype=batch.dtype, device=batch.xrec.device)
-        self.batch = batch
-
-    def __call__(self, z, xrec, sse_out):
-        from . import _native as N
-        import ctypes
-        b = self.batch
-        N.call('pnp_sigma_est', ctypes.c_void_p(z.data_ptr()), b.H, b.W, b.B, 0 if b.dtype == torch.float32 else 1,
-               ctypes.c_void_p(self.sig.data_ptr()), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-        self.plan.denoise(z, self.sigma, xrec=xrec, out=z, sse=sse_out)
-        return z
-
-    inplace = True
-    # one-kernel iteration: the gradient kernel makes the (ignored, F12) noise estimate; the network follows
-    fused_denoise = False
-
-    def fused_args(self):
-        return dict(sigma_out=self.sig)
-
-    def after_fused(self, z, xrec, sse_out):
-        self.plan.denoise(z, self.sigma, xrec=xrec, out=z, sse=sse_out)
-        return z
-
-
-class NLMProx:
-    """denoisers/NLM.py:22-27 semantics for the engines: h = sigma = estimate_sigma * sigma_modifier when
-    `self.sigma > 0` (the attribute the reference reads; default 1.0 here), else the decaying fixed strength.
-    NLM cannot run in place: the prox ping-pongs between the engine's iterate and a buffer of its own and RETURNS the
-    tensor that holds the result."""
-
-    inplace = False                                             # ping-pongs: a hipGraph of an outer iteration cannot hold it
-
-    def __init__(self, sigma=1.0, sigma_modifier=1.0, decay=1.0, denoise_strength=0.0, patch_size=4, patch_distance=5):
-        self.sigma, self.sigma_modifier, self.decay, self.denoise_strength = sigma, sigma_modifier, decay, denoise_strength
-        self.patch_size, self.patch_distance, self.t = patch_size, patch_distance, 0
-
-    def bind(self, batch):
-        self.sig = torch.empty(batch.B, dtype=batch.dtype, device=batch.xrec.device)
-        self.buf = torch.empty_like(batch.xinit)
-
-    def __call__(self, z, xrec, sse_out):
-        self.t += 1
-        if self.sigma > 0:
-            from . import _native as N
-            import ctypes
-            B, H, W = z.shape
-            N.call('pnp_sigma_est', ctypes.c_void_p(z.data_ptr()), H, W, B, 0 if z.dtype == torch.float32 else 1,
-                   ctypes.c_void_p(self.sig.data_ptr()), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-            ops.nlm2d(z, sigma_in=self.sig, sigma_modifier=self.sigma_modifier, patch_size=self.patch_size,
-                      patch_distance=self.patch_distance, xrec=xrec, out=self.buf, sse=sse_out)
-        else:
-            ops.nlm2d(z, fixed_h=self.denoise_strength * self.decay ** self.t, patch_size=self.patch_size,
-                      patch_distance=self.patch_distance, xrec=xrec, out=self.buf, sse=sse_out)
-        out, self.buf = self.buf, z
-        return out
-
-
-# ---------------------------------------------------------------------------------------------------------- engines
 class LoopEngine:
     """State and log machinery shared by the engines: the iterate z [B, H, W], a device log ring of the squared errors
     of every prox evaluation (-> rounded PSNR traces like the reference's psnr_per_iter), the step counter."""
@@ -721,10 +132,7 @@ class _StochEngine(LoopEngine):
         return step_id - base
 
     def _draw_slot(self, slot, step_id):
-        one = Minibatches.__new__(Minibatches)
-        one.n, one.mbd, one.host = 1, self.mbs.mbd[slot:slot + 1], [None]
-        one.selbits = self.mbs.selbits[slot:slot + 1] if self.mbs.selbits is not None else None
-        self.b.draw(one, self._mb_draw, self.seed, step_id, 1, **self._draw_kw)
+        self.b.draw(self.mbs.slot(slot), self._mb_draw, self.seed, step_id, 1, **self._draw_kw)
         self.mbs.host[slot] = None
 
 
@@ -779,39 +187,39 @@ class SvrgEngine(_StochEngine):
         """One inner iteration for all B problems.  idx_s: int32 [B][mb] minibatch index lists (e.g. drawn from
         NumPy's legacy stream for reference-identical runs); None = device draws."""
         b, s = self.b, self.s
-        j = s % self.T2
-        lr = self.eta * self.lr_decay ** (s // self.T2)
+        j, k = s % self.T2, s // self.T2
         if j == 0:                                              # outer: mu = grad_full(z); w = z
             if self.variant == 'svrg' and idx_s is None:
                 b.draw(self.mbs, self._mb_draw, self.seed, s, self.T2, **self._draw_kw)
-            if self.fused and self.fold_outer:
-                # ... folded into the first inner iteration: at j = 0 the SVRG difference gs(z) - gs(w) is exactly zero
-                # (w == z), so that iteration is z <- prox(z - lr * mu); ONE kernel forms mu, stores it and w, and goes on
-                if idx_s is not None:                           # (the minibatch of this step is drawn but cannot matter)
-                    b.set_host(self.mbs, j, idx_s)
-                self._fused_outer(lr, self.sse_log[self.n_prox % self.n_log], s // self.T2)
-                self.n_prox += 1
-                self.s += 1
-                return
-            b.grad_full(self.z, out=self.mu)
-            self.w.copy_(self.z)
+            if not (self.fused and self.fold_outer):            # (folded: the first inner iteration's kernel does it)
+                b.grad_full(self.z, out=self.mu)
+                self.w.copy_(self.z)
         if self.variant == 'svrg':
-            if idx_s is not None:
+            if idx_s is not None:                               # (at a folded j = 0 the minibatch is bound but cannot matter)
                 b.set_host(self.mbs, j, idx_s)
             elif self.mbs.host[j] is not None:                  # a host-fed outer iteration continued with device draws
                 self._draw_slot(j, s)
-            if self.fused:
-                self._fused_inner(j, lr, self.sse_log[self.n_prox % self.n_log], s // self.T2)
-                self.n_prox += 1
-                self.s += 1
-                return
-            k = s // self.T2
-            b.grad_stoch_diff(self.z, self.w, self.mbs, j, out=self.z, alpha=self._c('-lr/mb', k, -lr / self.mb), beta=1.0, c1=self.z,
-                              gamma=self._c('-lr', k, -lr), c2=self.mu)
+        self.z = self._inner(j, self.eta * self.lr_decay ** k, k, self.sse_log[self.n_prox % self.n_log])
+        self.n_prox += 1
+        self.s += 1                                             # eager steps keep the index on the host (no counter launch)
+
+    def _inner(self, j, lr, k, sse_out):
+        """Inner iteration j of the current outer iteration: step size lr, decay exponent k (what the per-problem coefficient
+        vectors are remade on), squared errors to sse_out.  Returns the tensor that holds the new iterate."""
+        if self.fused:
+            # folded refresh: at j = 0 the SVRG difference gs(z) - gs(w) is exactly zero (w == z), so that iteration is
+            # z <- prox(z - lr * mu); ONE kernel forms mu, stores it and w, and goes on
+            if j == 0 and self.fold_outer:
+                self._fused_outer(lr, sse_out, k)
+            else:
+                self._fused_inner(j, lr, sse_out, k)
+            return self.z
+        if self.variant == 'svrg':
+            self.b.grad_stoch_diff(self.z, self.w, self.mbs, j, out=self.z, alpha=self._c('-lr/mb', k, -lr / self.mb), beta=1.0,
+                                   c1=self.z, gamma=self._c('-lr', k, -lr), c2=self.mu)
         else:
             self._step_along_mu(lr)
-        self.z = self._prox(self.z)
-        self.s += 1                                             # eager steps keep the index on the host (no counter launch)
+        return self.prox(self.z, self.b.xrec, sse_out)
 
     def _step_along_mu(self, lr):
         """variant='reference': z <- z - lr * mu.  pnp_axpbypcz has scalar coefficients: per-problem step sizes take one launch
@@ -822,14 +230,14 @@ class SvrgEngine(_StochEngine):
             for i in range(self.b.B):
                 ops.axpbypcz(1.0, self.z[i], -float(lr[i]), self.mu[i], out=self.z[i])
 
-    def _fused_outer(self, lr, sse_out, k=0):
+    def _fused_outer(self, lr, sse_out, k):
         """outer refresh (mu = grad_full(z), w = z) + inner iteration 0 in one kernel (pnp_csmri_svrg_outer_step)."""
         b, px = self.b, self.prox
         b.plan.svrg_outer_step(self.z, b.bits, b.yh_full, b.inv_m0, self._c('lr', k, lr), self.w, self.mu, out=self.z,
                                denoise=px.fused_denoise, xrec=b.xrec, sse=sse_out if px.fused_denoise else None, **px.fused_args())
         px.after_fused(self.z, b.xrec, sse_out)
 
-    def _fused_inner(self, j, lr, sse_out, k=0):
+    def _fused_inner(self, j, lr, sse_out, k):
         """step + estimate_sigma + prox + error of inner iteration j in one kernel (TV), or in one kernel + the network."""
         b, px = self.b, self.prox
         if self.mbs.host[j] is not None:                        # host-drawn selector: pack it to bits (a 5 us launch)
@@ -844,27 +252,14 @@ class SvrgEngine(_StochEngine):
     # ---- hipGraph form: one OUTER iteration (full-gradient refresh + T2 inner iterations) = one graph launch
     def _outer_body(self):
         b = self.b
-        fold = self.variant == 'svrg' and self.fused and self.fold_outer
-        if not fold:
+        if not (self.fused and self.fold_outer):
             b.grad_full(self.z, out=self.mu)
             self.w.copy_(self.z)
-        lr = self.eta
         if self.variant == 'svrg':
             b.draw(self.mbs, self._mb_draw, self.seed, 0, self.T2, step_dev=self.step_dev, **self._draw_kw)
         for j in range(self.T2):
-            if fold and j == 0:
-                self._fused_outer(lr, self.sse_tmp)
-            elif self.variant == 'svrg' and self.fused:
-                self._fused_inner(j, lr, self.sse_tmp)
-            else:
-                if self.variant == 'svrg':
-                    b.grad_stoch_diff(self.z, self.w, self.mbs, j, out=self.z, alpha=self._c('-lr/mb', 0, -lr / self.mb), beta=1.0,
-                                      c1=self.z, gamma=self._c('-lr', 0, -lr), c2=self.mu)
-                else:
-                    self._step_along_mu(lr)
-                out = self.prox(self.z, b.xrec, self.sse_tmp)
-                if out is not self.z:
-                    raise ValueError('graph capture needs an in-place prox')
+            if self._inner(j, self.eta, 0, self.sse_tmp) is not self.z:      # (graph_ok: lr_decay == 1)
+                raise ValueError('graph capture needs an in-place prox')
             ops.log_append(self.sse_tmp, self.sse_log, self.step_dev)
             ops.counter_add(self.step_dev, 1)
 

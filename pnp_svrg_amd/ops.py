@@ -25,13 +25,45 @@ def _p(t):
     return ctypes.c_void_p(t.data_ptr())
 
 
+class _PP(tuple):
+    """(scalar, device array or None): a hyper-parameter marked as per-problem capable in an argument list for `_route`."""
+    __slots__ = ()
+
+
 def _pp(v, B, dtype=torch.float64):
-    """A hyper-parameter that may be per problem -> (scalar, device array or None): a tensor ([B], float64 -- int32 for minibatch
+    """A hyper-parameter that may be per problem -> _PP(scalar, device array or None): a tensor ([B], float64 -- int32 for minibatch
     sizes) goes to the `_pp` entry point's array argument, anything else is the scalar of the plain call."""
     if isinstance(v, torch.Tensor):
         assert v.dtype == dtype and tuple(v.shape) == (B,), f'per-problem values: a [{B}] {dtype} device tensor'
-        return (0 if dtype == torch.int32 else 0.0), v
-    return (int(v) if dtype == torch.int32 else float(v)), None
+        return _PP(((0 if dtype == torch.int32 else 0.0), v))
+    return _PP(((int(v) if dtype == torch.int32 else float(v)), None))
+
+
+def _route(name, args, ptr=_p):
+    """Call entry point `name` with `args`, the `_pp()` values among them as their scalars -- exactly the plain call -- unless one
+    of them holds a per-problem array: then `name_pp`, where every `_pp()` value is a (scalar, array pointer or None) pair."""
+    if any(type(a) is _PP and a[1] is not None for a in args):
+        flat = []
+        for a in args:
+            if type(a) is _PP:
+                flat += (a[0], ptr(a[1]))
+            else:
+                flat.append(a)
+        N.call(name + '_pp', *flat)
+    else:
+        N.call(name, *[a[0] if type(a) is _PP else a for a in args])
+
+
+def _mb_vec(mb, draw_id, B, device):
+    """What the `_pp` draw entry points take for `mb` (an int, or an int32 [B] device tensor) once either it or `draw_id` is per
+    problem: the int32 [B] device vector (they have no scalar form); None when the plain entry point takes the int."""
+    if not isinstance(mb, torch.Tensor):
+        if draw_id is None:
+            return None
+        mb = torch.full((B,), int(mb), dtype=torch.int32, device=device)
+    assert mb.dtype == torch.int32 and tuple(mb.shape) == (B,)
+    assert draw_id is None or (draw_id.dtype == torch.int32 and tuple(draw_id.shape) == (B,))
+    return mb
 
 
 def require_gpu():
@@ -82,12 +114,9 @@ class CsmriPlan:
         out = out if out is not None else torch.empty((nsteps, self.B, 2), dtype=torch.int64, device=bits.device)
         assert out.dtype == torch.int64 and tuple(out.shape) == (nsteps, self.B, 2)
         assert selbits is None or (selbits.dtype == torch.int32 and tuple(selbits.shape) == (nsteps, self.B, self.W, self.H // 32))
-        if isinstance(mb, torch.Tensor) or draw_id is not None:
-            if not isinstance(mb, torch.Tensor):
-                mb = torch.full((self.B,), int(mb), dtype=torch.int32, device=bits.device)
-            assert mb.dtype == torch.int32 and tuple(mb.shape) == (self.B,)
-            assert draw_id is None or (draw_id.dtype == torch.int32 and tuple(draw_id.shape) == (self.B,))
-            N.call('pnp_csmri_draw_thresholds_pp', self._h, _p(bits), _p(mb), _p(draw_id), int(seed) & (2 ** 64 - 1),
+        mb_vec = _mb_vec(mb, draw_id, self.B, bits.device)
+        if mb_vec is not None:
+            N.call('pnp_csmri_draw_thresholds_pp', self._h, _p(bits), _p(mb_vec), _p(draw_id), int(seed) & (2 ** 64 - 1),
                    int(step0) & 0xFFFFFFFF, int(nsteps), _p(step_dev), _p(out), _p(selbits), _stream())
             return out
         N.call('pnp_csmri_draw_thresholds', self._h, _p(bits), int(mb), int(seed) & (2 ** 64 - 1), int(step0) & 0xFFFFFFFF,
@@ -135,13 +164,8 @@ class CsmriPlan:
         assert alpha_vec is None or (alpha_vec.dtype == self.dtype and alpha_vec.numel() == self.B)
         out = out if out is not None else torch.empty_like(a)
         assert YT is None or (YT.dtype == _CDT[self.dtype] and tuple(YT.shape) == (self.B, self.W, self.H))
-        if isinstance(alpha, torch.Tensor) or isinstance(gamma, torch.Tensor):       # float64 [B]: per-problem coefficients
-            (al, al_pp), (ga, ga_pp) = _pp(alpha, self.B), _pp(gamma, self.B)
-            N.call('pnp_csmri_grad_sel_pp', self._h, _p(a), _p(b), _p(selT), _p(bits), _p(yh), _p(YT), al, _p(al_pp), _p(alpha_vec),
-                   float(beta), _p(c1), ga, _p(ga_pp), _p(c2), _p(out), _stream())
-            return out
-        N.call('pnp_csmri_grad_sel', self._h, _p(a), _p(b), _p(selT), _p(bits), _p(yh), _p(YT), float(alpha), _p(alpha_vec),
-               float(beta), _p(c1), float(gamma), _p(c2), _p(out), _stream())
+        _route('pnp_csmri_grad_sel', [self._h, _p(a), _p(b), _p(selT), _p(bits), _p(yh), _p(YT), _pp(alpha, self.B), _p(alpha_vec),
+                                      float(beta), _p(c1), _pp(gamma, self.B), _p(c2), _p(out), _stream()])
         return out
 
     def generate(self, images, image_idx, thresh, snr_fac, seed, item_id, with_mask=True):
@@ -177,17 +201,10 @@ class CsmriPlan:
         assert bits.dtype == torch.int32 and tuple(bits.shape) == (self.B, self.W, self.H // 32)
         out = out if out is not None else torch.empty_like(a)
         sigma_out = sigma_out if sigma_out is not None else torch.empty(self.B, dtype=a.dtype, device=a.device)
-        if any(isinstance(v, torch.Tensor) for v in (alpha, gamma, sigma_modifier)):
-            (al, al_pp), (ga, ga_pp), (sm, sm_pp) = _pp(alpha, self.B), _pp(gamma, self.B), _pp(sigma_modifier, self.B)
-            N.call('pnp_csmri_svrg_step_pp', self._h, _p(a), _p(b), _p(bits), al, _p(al_pp), _p(alpha_vec), float(beta), _p(c1), ga,
-                   _p(ga_pp), _p(c2), _p(out), 1 if denoise else 0, sm, _p(sm_pp), float(fallback_sigma), _p(xrec), _p(sse),
-                   _p(sigma_out), _stream())
-            return out, sse, sigma_out
-        N.call('pnp_csmri_svrg_step', self._h, _p(a), _p(b), _p(bits), float(alpha), _p(alpha_vec), float(beta), _p(c1),
-               float(gamma), _p(c2), _p(out), 1 if denoise else 0, float(sigma_modifier), float(fallback_sigma), _p(xrec),
-               _p(sse), _p(sigma_out), _stream())
+        _route('pnp_csmri_svrg_step', [self._h, _p(a), _p(b), _p(bits), _pp(alpha, self.B), _p(alpha_vec), float(beta), _p(c1),
+                                       _pp(gamma, self.B), _p(c2), _p(out), 1 if denoise else 0, _pp(sigma_modifier, self.B),
+                                       float(fallback_sigma), _p(xrec), _p(sse), _p(sigma_out), _stream()])
         return out, sse, sigma_out
-
 
     def svrg_outer_step(self, z, mask_bits, yh, alpha_vec, lr, w_out, mu_out, out=None, *, denoise=True, sigma_modifier=1.0,
                         fallback_sigma=0.0, xrec=None, sse=None, sigma_out=None):
@@ -199,16 +216,10 @@ class CsmriPlan:
             assert t is None or (t.dtype == self.dtype and t.numel() == self.B * self.H * self.W)
         out = out if out is not None else torch.empty_like(z)
         sigma_out = sigma_out if sigma_out is not None else torch.empty(self.B, dtype=z.dtype, device=z.device)
-        if isinstance(lr, torch.Tensor) or isinstance(sigma_modifier, torch.Tensor):
-            (l, l_pp), (sm, sm_pp) = _pp(lr, self.B), _pp(sigma_modifier, self.B)
-            N.call('pnp_csmri_svrg_outer_step_pp', self._h, _p(z), _p(mask_bits), _p(yh), _p(alpha_vec), l, _p(l_pp), _p(w_out),
-                   _p(mu_out), _p(out), 1 if denoise else 0, sm, _p(sm_pp), float(fallback_sigma), _p(xrec), _p(sse), _p(sigma_out),
-                   _stream())
-            return out, sse, sigma_out
-        N.call('pnp_csmri_svrg_outer_step', self._h, _p(z), _p(mask_bits), _p(yh), _p(alpha_vec), float(lr), _p(w_out), _p(mu_out),
-               _p(out), 1 if denoise else 0, float(sigma_modifier), float(fallback_sigma), _p(xrec), _p(sse), _p(sigma_out), _stream())
+        _route('pnp_csmri_svrg_outer_step', [self._h, _p(z), _p(mask_bits), _p(yh), _p(alpha_vec), _pp(lr, self.B), _p(w_out),
+                                             _p(mu_out), _p(out), 1 if denoise else 0, _pp(sigma_modifier, self.B),
+                                             float(fallback_sigma), _p(xrec), _p(sse), _p(sigma_out), _stream()])
         return out, sse, sigma_out
-
 
     def svrg_outer_iteration(self, z, w, mu, mask_bits, yh, alpha_vec, selbits, T2, lr, mini_batch_size, xrec, sse_log, log_row0,
                              sigma_out, *, sigma_modifier=1.0, fallback_sigma=0.0):
@@ -218,15 +229,10 @@ class CsmriPlan:
             assert t.dtype == self.dtype and t.numel() == self.B * self.H * self.W
         assert selbits.dtype == torch.int32 and tuple(selbits.shape) == (T2, self.B, self.W, self.H // 32)
         assert sse_log.dtype == torch.float64 and sse_log.dim() == 2 and sse_log.shape[1] == self.B and sse_log.is_contiguous()
-        if any(isinstance(v, torch.Tensor) for v in (lr, mini_batch_size, sigma_modifier)):
-            (l, l_pp), (m, m_vec), (sm, sm_pp) = _pp(lr, self.B), _pp(mini_batch_size, self.B, torch.int32), _pp(sigma_modifier, self.B)
-            N.call('pnp_csmri_svrg_outer_iteration_pp', self._h, _p(z), _p(w), _p(mu), _p(mask_bits), _p(yh), _p(alpha_vec), _p(selbits),
-                   int(T2), l, _p(l_pp), m, _p(m_vec), sm, _p(sm_pp), float(fallback_sigma), _p(xrec), _p(sse_log), int(log_row0),
-                   int(sse_log.shape[0]), _p(sigma_out), _stream())
-            return
-        N.call('pnp_csmri_svrg_outer_iteration', self._h, _p(z), _p(w), _p(mu), _p(mask_bits), _p(yh), _p(alpha_vec), _p(selbits), int(T2),
-               float(lr), int(mini_batch_size), float(sigma_modifier), float(fallback_sigma), _p(xrec), _p(sse_log), int(log_row0),
-               int(sse_log.shape[0]), _p(sigma_out), _stream())
+        _route('pnp_csmri_svrg_outer_iteration',
+               [self._h, _p(z), _p(w), _p(mu), _p(mask_bits), _p(yh), _p(alpha_vec), _p(selbits), int(T2), _pp(lr, self.B),
+                _pp(mini_batch_size, self.B, torch.int32), _pp(sigma_modifier, self.B), float(fallback_sigma), _p(xrec), _p(sse_log),
+                int(log_row0), int(sse_log.shape[0]), _p(sigma_out), _stream()])
 
 
 class DncnnPlan:
@@ -343,49 +349,38 @@ class DncnnPlan:
         return out, sse
 
 
-def sigma_est(z):
+def sigma_est(z, out=None):
     """z: [B, H, W] -> [B] (estimate_sigma(multichannel=True, average_sigmas=True))."""
     require_gpu()
     B, H, W = z.shape
-    out = torch.empty(B, dtype=z.dtype, device=z.device)
+    out = out if out is not None else torch.empty(B, dtype=z.dtype, device=z.device)
     N.call('pnp_sigma_est', _p(z), H, W, B, _DT[z.dtype], _p(out), _stream())
     return out
+
+
+def _prox(name, z, sigma_in, sigma_modifier, fallback_sigma, xrec, out, sse, sigma_out):
+    """prox_tv / prox_wavelet2d: two entry points with one signature (sigma_modifier: a scalar, or float64 [B] per problem)."""
+    require_gpu()
+    B, H, W = z.shape
+    out = out if out is not None else torch.empty_like(z)
+    if xrec is not None and sse is None:
+        sse = torch.empty(B, dtype=torch.float64, device=z.device)
+    sigma_out = sigma_out if sigma_out is not None else torch.empty(B, dtype=z.dtype, device=z.device)
+    _route(name, [_p(z), _p(out), H, W, B, _DT[z.dtype], _p(sigma_in), _pp(sigma_modifier, B), float(fallback_sigma), _p(xrec),
+                  _p(sse), _p(sigma_out), _stream()])
+    return out, sse, sigma_out
 
 
 def prox_tv(z, sigma_in=None, sigma_modifier=1.0, fallback_sigma=0.0, xrec=None, out=None, sse=None, sigma_out=None):
     """Fused estimate_sigma + Haar-BayesShrink prox (+ squared error vs xrec).
     Returns (denoised [B,H,W], sse [B] float64 or None, sigma_est [B])."""
-    require_gpu()
-    B, H, W = z.shape
-    out = out if out is not None else torch.empty_like(z)
-    if xrec is not None and sse is None:
-        sse = torch.empty(B, dtype=torch.float64, device=z.device)
-    sigma_out = sigma_out if sigma_out is not None else torch.empty(B, dtype=z.dtype, device=z.device)
-    if isinstance(sigma_modifier, torch.Tensor):                # float64 [B]: per-problem strength
-        N.call('pnp_prox_tv_pp', _p(z), _p(out), H, W, B, _DT[z.dtype], _p(sigma_in), 0.0, _p(_pp(sigma_modifier, B)[1]),
-               float(fallback_sigma), _p(xrec), _p(sse), _p(sigma_out), _stream())
-        return out, sse, sigma_out
-    N.call('pnp_prox_tv', _p(z), _p(out), H, W, B, _DT[z.dtype], _p(sigma_in), float(sigma_modifier),
-           float(fallback_sigma), _p(xrec), _p(sse), _p(sigma_out), _stream())
-    return out, sse, sigma_out
+    return _prox('pnp_prox_tv', z, sigma_in, sigma_modifier, fallback_sigma, xrec, out, sse, sigma_out)
 
 
 def prox_wavelet2d(z, sigma_in=None, sigma_modifier=1.0, fallback_sigma=0.0, xrec=None, out=None, sse=None, sigma_out=None):
     """Fused estimate_sigma + 2-D multi-level Haar BayesShrink prox (TVDenoiser(multi=False)) (+ squared error vs xrec).
     Signature and result of `prox_tv`: (denoised [B,H,W], sse [B] float64 or None, sigma_est [B])."""
-    require_gpu()
-    B, H, W = z.shape
-    out = out if out is not None else torch.empty_like(z)
-    if xrec is not None and sse is None:
-        sse = torch.empty(B, dtype=torch.float64, device=z.device)
-    sigma_out = sigma_out if sigma_out is not None else torch.empty(B, dtype=z.dtype, device=z.device)
-    if isinstance(sigma_modifier, torch.Tensor):                # float64 [B]: per-problem strength
-        N.call('pnp_prox_wavelet2d_pp', _p(z), _p(out), H, W, B, _DT[z.dtype], _p(sigma_in), 0.0, _p(_pp(sigma_modifier, B)[1]),
-               float(fallback_sigma), _p(xrec), _p(sse), _p(sigma_out), _stream())
-        return out, sse, sigma_out
-    N.call('pnp_prox_wavelet2d', _p(z), _p(out), H, W, B, _DT[z.dtype], _p(sigma_in), float(sigma_modifier),
-           float(fallback_sigma), _p(xrec), _p(sse), _p(sigma_out), _stream())
-    return out, sse, sigma_out
+    return _prox('pnp_prox_wavelet2d', z, sigma_in, sigma_modifier, fallback_sigma, xrec, out, sse, sigma_out)
 
 
 def sse(z, xrec, out=None):
@@ -547,12 +542,17 @@ def pr_spectral_init_batch(A, Y, xrec, max_iters=1000, check_every=8):
     return xinit, iters, active
 
 
+def pr_workspace(M, Nn, dtype, device, B=1):
+    """Scratch of the pnp_pr_* gradient / spectral kernels for B problems of an M x Nn matrix."""
+    return torch.empty(B * N.lib().pnp_pr_workspace_elems(M, Nn), dtype=dtype, device=device)
+
+
 def pr_grad(A, w, y, rows=None, scale=1.0, workspace=None, out=None):
     """scale * A_sel^T(((|A_sel w| - y_sel)/|A_sel w|) o A_sel w); A [M,N], rows int32 [nsel] or None."""
     require_gpu()
     M, Nn = A.shape
     if workspace is None:
-        workspace = torch.empty(N.lib().pnp_pr_workspace_elems(M, Nn), dtype=A.dtype, device=A.device)
+        workspace = pr_workspace(M, Nn, A.dtype, A.device)
     out = out if out is not None else torch.empty(Nn, dtype=A.dtype, device=A.device)
     nsel = M if rows is None else rows.numel()
     N.call('pnp_pr_grad', _p(A), _p(w), _p(y), _p(rows), nsel, M, Nn, _DT[A.dtype], float(scale), _p(workspace), _p(out), _stream())
@@ -564,7 +564,7 @@ def pr_grad_batch(A, w, y, rows=None, scale=1.0, workspace=None, out=None):
     require_gpu()
     B, M, Nn = A.shape
     if workspace is None:
-        workspace = torch.empty(B * N.lib().pnp_pr_workspace_elems(M, Nn), dtype=A.dtype, device=A.device)
+        workspace = pr_workspace(M, Nn, A.dtype, A.device, B)
     out = out if out is not None else torch.empty((B, Nn), dtype=A.dtype, device=A.device)
     nsel = M if rows is None else rows.shape[1]
     N.call('pnp_pr_grad_batch', _p(A), _p(w), _p(y), _p(rows), nsel, M, Nn, B, _DT[A.dtype], float(scale), _p(workspace),
@@ -577,12 +577,9 @@ def draw_thresholds(M, B, mb, seed, step0, nsteps=1, out=None, step_dev=None, de
     mb: an int, or an int32 [B] device tensor; draw_id: int32 [B] ids absorbed in place of the batch index (pnp_draw_thresholds_pp)."""
     require_gpu()
     out = out if out is not None else torch.empty((nsteps, B, 2), dtype=torch.int64, device=device)
-    if isinstance(mb, torch.Tensor) or draw_id is not None:
-        if not isinstance(mb, torch.Tensor):
-            mb = torch.full((B,), int(mb), dtype=torch.int32, device=out.device)
-        assert mb.dtype == torch.int32 and tuple(mb.shape) == (B,)
-        assert draw_id is None or (draw_id.dtype == torch.int32 and tuple(draw_id.shape) == (B,))
-        N.call('pnp_draw_thresholds_pp', int(M), int(B), _p(mb), _p(draw_id), int(seed) & (2 ** 64 - 1), int(step0) & 0xFFFFFFFF,
+    mb_vec = _mb_vec(mb, draw_id, B, out.device)
+    if mb_vec is not None:
+        N.call('pnp_draw_thresholds_pp', int(M), int(B), _p(mb_vec), _p(draw_id), int(seed) & (2 ** 64 - 1), int(step0) & 0xFFFFFFFF,
                int(nsteps), _p(step_dev), _p(out), _stream())
         return out
     N.call('pnp_draw_thresholds', int(M), int(B), int(mb), int(seed) & (2 ** 64 - 1), int(step0) & 0xFFFFFFFF, int(nsteps),
@@ -630,7 +627,7 @@ def pr_spectral_apply(A, v, y, scale=1.0, workspace=None, out=None):
     require_gpu()
     M, Nn = A.shape
     if workspace is None:
-        workspace = torch.empty(N.lib().pnp_pr_workspace_elems(M, Nn), dtype=A.dtype, device=A.device)
+        workspace = pr_workspace(M, Nn, A.dtype, A.device)
     out = out if out is not None else torch.empty(Nn, dtype=A.dtype, device=A.device)
     N.call('pnp_pr_spectral_apply', _p(A), _p(v), _p(y), M, Nn, _DT[A.dtype], float(scale), _p(workspace), _p(out), _stream())
     return out
