@@ -259,6 +259,30 @@ int pnp_pr_grad_batch(const void* A, const void* w, const void* y, const int32_t
  * D v for D = A^T diag(y) A / M (scale = 1/M) without forming the N x N matrix.  v, out [N]; same workspace.      */
 int pnp_pr_spectral_apply(const void* A, const void* v, const void* y, int M, int N, int dtype, double scale,
                           void* workspace, void* out, void* stream);
+/* Gradients of batch = G * items problems that SHARE `items` matrices (a trial-batched grid, csrc/pr_shared.hip): problem
+ * b = t * items + i works on A[i] and Y[i].  A [items][M][N], Y [items][M], W [batch][N], W2 [batch][N] or NULL, out [batch][N]:
+ *   out[b] = (alpha_b / alpha_div) * (g_b(W[b]) - g_b(W2[b])) + beta * c1[b] + gamma_b * c2[b]
+ * with g_b(x) = A_sel^T(((|A_sel x| - y_sel) / |A_sel x|) o A_sel x) over the rows problem b selects; the W2 term is dropped when
+ * W2 == NULL; c1, c2 [batch][N] or NULL.  alpha_b = alpha_pp ? alpha_pp[b] : alpha and gamma_b likewise (_pp form; [batch] doubles
+ * on the device); the quotient alpha_b / alpha_div is taken in double and rounded to `dtype` as the host rounds a scalar
+ * (grad_full: alpha_div = M; else 1).
+ * Selection per problem: mbd ([batch] threshold descriptors of pnp_draw_thresholds(M, ...), membership re-derived in the kernel),
+ * or ind (uint8 [batch][M]), or neither (all M rows); both is an argument error.  A row that problem b did not select contributes
+ * exactly zero to b (its weight is written as 0), whatever the matrix holds there.
+ * Both products run on the matrix cores (v_mfma_f32_16x16x4_f32 / v_mfma_f64_16x16x4_f64; the 16-wide dimension is the problem
+ * columns) and A is streamed twice per call and item for up to 64 (W2: 32) problems per item, whatever G is.  Any M, N >= 1
+ * (scalar loads where N is not a multiple of 16 bytes or a pointer is not 16-byte aligned).  Deterministic, no atomics: the split
+ * of the sums depends on (M, N, dtype) only, so a problem's result is bit-identical whatever G is, wherever it sits in the batch
+ * and whatever the other problems select.  out may alias W, c1 or c2 (W and W2 are read before out is written).
+ * workspace: pnp_pr_shared_workspace_elems(M, N, batch) elements of `dtype`, 16-byte aligned (enough for any `items`).           */
+size_t pnp_pr_shared_workspace_elems(int M, int N, int batch);
+int pnp_pr_grad_shared(const void* A, const void* Y, const void* W, const void* W2, const void* mbd, const uint8_t* ind, int M, int N,
+                       int batch, int items, int dtype, double alpha, double alpha_div, double beta, const void* c1, double gamma,
+                       const void* c2, void* workspace, void* out, void* stream);
+int pnp_pr_grad_shared_pp(const void* A, const void* Y, const void* W, const void* W2, const void* mbd, const uint8_t* ind, int M,
+                          int N, int batch, int items, int dtype, double alpha, const double* alpha_pp, double alpha_div, double beta,
+                          const void* c1, double gamma, const double* gamma_pp, const void* c2, void* workspace, void* out,
+                          void* stream);
 
 /* ------------------------------------------------------------------ Deblur / PR sweep batches generated on the device
  * The same stream for the other two problems (tags 0-2 keep the meaning above; state_k and key_k(i) are unchanged), so that a

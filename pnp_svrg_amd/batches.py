@@ -39,6 +39,8 @@ class Minibatches:
 
 
 class _BatchBase:
+    per_problem = False                                         # whether the engines may hand this batch per-problem eta / mb / draw_id
+
     def _init_base(self, xrec, xinit, max_mb):
         """The state every batch has, from its device tensors: xrec, xinit [B, H, W]."""
         self.B, self.H, self.W = xrec.shape
@@ -127,6 +129,7 @@ class CsmriBatch(_BatchBase):
     different numbers of sampled locations (the reference draws Bernoulli masks, CSMRI.py:43-45): grad_full's 1/M0
     is a per-problem device vector."""
     kind = 'csmri'
+    per_problem = True
 
     def __init__(self, xrec, mask, Y, xinit, dtype=torch.float32, device='cuda', *, _state=None):
         if _state is not None:
@@ -368,7 +371,10 @@ class DeblurBatch(_BatchBase):
 
 
 class PrBatch(_BatchBase):
-    """B phase-retrieval problems (reference problems/PR.py:13-87 per problem), each with its own dense M x N matrix."""
+    """B phase-retrieval problems (reference problems/PR.py:13-87 per problem), each with its own dense M x N matrix.
+    `tile(n)` gives the trial-batched form: n * B problems that SHARE the B matrices (problem t * B + i works on A[i]; nothing of
+    A is copied), whose gradients are one pnp_pr_grad_shared call each (csrc/pr_shared.hip: A is streamed twice per call whatever
+    n is) and which takes per-problem eta, mini_batch_size and draw_id from the engines."""
     kind = 'pr'
 
     def __init__(self, xrec, A, Y, xinit, dtype=torch.float32, device='cuda', *, _state=None):
@@ -379,12 +385,29 @@ class PrBatch(_BatchBase):
         self._init(self._upload(xrec, dtype, device), self._upload(xinit, dtype, device, (B, H, W)),
                    self._upload(A, dtype, device).contiguous(), self._upload(Y, dtype, device, (B, A.shape[1])))
 
-    def _init(self, xrec, xinit, A, Y, sigma=None, spec_iters=None):
-        """A: [B, M, N]; sigma ([B] float64 noise levels) and spec_iters (power-iteration steps per item): a generated batch."""
+    def _init(self, xrec, xinit, A, Y, sigma=None, spec_iters=None, items=None):
+        """A: [B, M, N]; sigma ([B] float64 noise levels) and spec_iters (power-iteration steps per item): a generated batch.
+        items: a tiled batch -- A is [items, M, N] and problem b of the B = n * items works on A[b % items]."""
         self._init_base(xrec, xinit, A.shape[1])
         self.M, self.A, self.Y, self.sigma, self.spec_iters = A.shape[1], A, Y, sigma, spec_iters
-        self._ws = ops.pr_workspace(self.M, self.N, self.dtype, self.device, self.B)
+        self.items, self.shared = (self.B, False) if items is None else (int(items), True)
+        self.per_problem = self.shared
+        if self.shared:
+            self._ws = ops.pr_shared_workspace(self.M, self.N, self.dtype, self.device, self.B)
+        else:
+            self._ws = ops.pr_workspace(self.M, self.N, self.dtype, self.device, self.B)
         self._mb = None                                         # size of the last device draw (the row lists' width)
+
+    def tile(self, n):
+        """A batch of n * B problems (problem t * B + i = this batch's problem i) on THIS batch's matrices: xrec, xinit, Y and sigma
+        are repeated by device copies, A is the same tensor -- what a trial-batched grid runs on (sweep.make_runner(...,
+        shared_matrix=True)).  Its gradients go through pnp_pr_grad_shared."""
+        n = int(n)
+        if n < 1:
+            raise ValueError('tile(n) needs n >= 1')
+        rep = lambda v: None if v is None else v.repeat((n,) + (1,) * (v.dim() - 1)).contiguous()
+        return self._of(xrec=rep(self.xrec), xinit=rep(self.xinit), A=self.A, Y=rep(self.Y), sigma=rep(self.sigma),
+                        spec_iters=None if self.spec_iters is None else np.tile(self.spec_iters, n), items=self.items)
 
     @classmethod
     def generate(cls, images, items, H, W, M, dtype=torch.float32, max_iters=1000, check_every=8, device='cuda'):
@@ -415,16 +438,28 @@ class PrBatch(_BatchBase):
         out = np.stack([[np.sort(rng.choice(self.M, mb, replace=False)) for _ in range(self.B)] for _ in range(n_steps)]).astype(np.int32)
         return torch.from_numpy(out).to(self.device)
 
-    def draw(self, mbs, mb, seed, step0, nsteps=1, step_dev=None):
-        self._check_mb(mb)
+    def draw(self, mbs, mb, seed, step0, nsteps=1, step_dev=None, draw_id=None):
+        """mb: an int; on a tiled batch also per problem ([B] integers on the host, or an int32 [B] device tensor taken as
+        checked), with draw_id (int32 [B] device tensor): the ids the minibatch streams absorb in place of the batch index."""
+        if not isinstance(mb, torch.Tensor):
+            self._check_mb(mb)
+            if np.ndim(mb) != 0:
+                mb = torch.from_numpy(np.ascontiguousarray(mb, np.int32)).to(self.device)
+        if (isinstance(mb, torch.Tensor) or draw_id is not None) and not self.shared:
+            raise ValueError('per-problem mini_batch_size / draw_id need a tiled PrBatch (PrBatch.tile)')
         self._mb = mb
-        ops.draw_thresholds(self.M, self.B, mb, seed, step0, nsteps, out=mbs.mbd[:nsteps], step_dev=step_dev)
+        ops.draw_thresholds(self.M, self.B, mb, seed, step0, nsteps, out=mbs.mbd[:nsteps], step_dev=step_dev, draw_id=draw_id)
         for j in range(nsteps):
             mbs.host[j] = None
 
     def set_host(self, mbs, j, idx):
-        """idx: int32 [B, mb] row ids (np.flatnonzero of the indicator: ascending, like A[idx] in PR.py:82-83)."""
-        mbs.host[j] = idx.contiguous()
+        """idx: int32 [B, mb] row ids (np.flatnonzero of the indicator: ascending, like A[idx] in PR.py:82-83).  A tiled batch keeps
+        them as the uint8 [B, M] indicator its kernel takes."""
+        if self.shared:
+            mbs.host[j] = ops.indicator_from_indices(idx.contiguous(), self.M,
+                                                     out=mbs.host[j] if isinstance(mbs.host[j], torch.Tensor) else None)
+        else:
+            mbs.host[j] = idx.contiguous()
 
     def _rows(self, mbs, j):
         if mbs.host[j] is not None:
@@ -442,15 +477,29 @@ class PrBatch(_BatchBase):
                           out=out.reshape(self.B, self.N))
         return out
 
+    def _shared(self, z, w, mbs, j, out, alpha, alpha_div, beta, c1, gamma=0.0, c2=None):
+        """One pnp_pr_grad_shared call: the selection of slot j (None: all rows) goes in as descriptors or as an indicator."""
+        v = lambda t: None if t is None else t.reshape(self.B, self.N)
+        sel = {} if mbs is None else (dict(ind=mbs.host[j]) if mbs.host[j] is not None else dict(mbd=mbs.mbd[j]))
+        ops.pr_grad_shared(self.A, self.Y[:self.items], v(z), v(w), alpha=alpha, alpha_div=alpha_div, beta=beta, c1=v(c1), gamma=gamma,
+                           c2=v(c2), workspace=self._ws, out=v(out), **sel)
+        return out
+
     def grad_full(self, z, out, alpha=1.0, beta=0.0, c1=None):
+        if self.shared:
+            return self._shared(z, None, None, 0, out, alpha, self.M, beta, c1)
         g = self._g(z, None, alpha / self.M, out if c1 is None else self._scratch(z))
         return self._combine(g, out, beta, c1)
 
     def grad_stoch(self, z, mbs, j, out, alpha=1.0, beta=0.0, c1=None):
+        if self.shared:
+            return self._shared(z, None, mbs, j, out, alpha, 1.0, beta, c1)
         g = self._g(z, self._rows(mbs, j), alpha, out if c1 is None else self._scratch(z))
         return self._combine(g, out, beta, c1)
 
     def grad_stoch_diff(self, z, w, mbs, j, out, alpha=1.0, beta=0.0, c1=None, gamma=0.0, c2=None):
+        if self.shared:
+            return self._shared(z, w, mbs, j, out, alpha, 1.0, beta, c1, gamma, c2)
         rows = self._rows(mbs, j)
         g1 = self._g(z, rows, alpha, torch.empty_like(z))
         g2 = self._g(w, rows, alpha, self._scratch(z))

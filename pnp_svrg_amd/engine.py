@@ -15,6 +15,8 @@ Per-problem hyper-parameters (a hyper-parameter grid as one batch): Gd
 array goes to the `_pp` entry points as float64 / int32 device vectors made once on the host (`-lr`, `-lr / mb`: remade when
 lr_decay != 1 changes them), and problem b then walks, bit for bit, the trajectory a scalar engine with b's values walks.
 `draw_id` ([B] ints) replaces the batch index in the minibatch stream, and `CsmriBatch.tile(n)` repeats a batch's data n times.
+A batch says whether it takes them with its `per_problem` attribute: a CsmriBatch does, and so does `PrBatch.tile(n)`, n * B problems
+on the B matrices of the batch it was tiled from (the non-fused paths only; csrc/pr_shared.hip).
 """
 import numpy as np
 import torch
@@ -32,7 +34,7 @@ class LoopEngine:
         self.b, self.prox, self.eta, self.lr_decay, self.seed = batch, prox, eta, lr_decay, seed
         if np.ndim(eta) != 0:                                   # per-problem step sizes
             self.eta = np.ascontiguousarray(eta, np.float64)
-            if self.eta.shape != (batch.B,) or batch.kind != 'csmri':
+            if self.eta.shape != (batch.B,) or not batch.per_problem:
                 raise ValueError(f'per-problem eta: {batch.B} values on a CsmriBatch, got shape {self.eta.shape} on {batch.kind!r}')
         self._coef = {}
         dev = batch.xrec.device
@@ -100,7 +102,7 @@ class _StochEngine(LoopEngine):
         self.mb = self._mb_draw = mini_batch_size               # (host value for the coefficients, what the draws take)
         self._draw_kw = {}
         if np.ndim(mini_batch_size) != 0 or draw_id is not None:
-            if batch.kind != 'csmri':
+            if not batch.per_problem:                           # (a CsmriBatch, or a PrBatch tiled on shared matrices)
                 raise ValueError(f'per-problem mini_batch_size / draw_id need a CsmriBatch (got {batch.kind!r})')
             dev = batch.xrec.device
             if np.ndim(mini_batch_size) != 0:

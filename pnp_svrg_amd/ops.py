@@ -572,6 +572,35 @@ def pr_grad_batch(A, w, y, rows=None, scale=1.0, workspace=None, out=None):
     return out
 
 
+def pr_shared_workspace(M, Nn, dtype, device, B):
+    """Scratch of pnp_pr_grad_shared for B problems on shared M x Nn matrices (any number of items)."""
+    return torch.empty(N.lib().pnp_pr_shared_workspace_elems(M, Nn, B), dtype=dtype, device=device)
+
+
+def pr_grad_shared(A, Y, W, W2=None, mbd=None, ind=None, alpha=1.0, alpha_div=1.0, beta=0.0, c1=None, gamma=0.0, c2=None,
+                   workspace=None, out=None):
+    """B = G * items problems on `items` shared matrices (problem b works on A[b % items], Y[b % items]): A [items, M, N],
+    Y [items, M], W, W2 (or None), c1, c2 (or None), out [B, N]:
+        out[b] = (alpha_b / alpha_div) * (g_b(W[b]) - g_b(W2[b])) + beta * c1[b] + gamma_b * c2[b]
+    alpha, gamma: scalars, or float64 [B] device tensors (per problem).  Rows per problem: mbd (int64 [B, 2], one step's device-drawn
+    descriptors), ind (uint8 [B, M]) or neither (all rows).  out may alias W, c1 or c2."""
+    require_gpu()
+    items, M, Nn = A.shape
+    B = W.numel() // Nn
+    for t in (Y, W, W2, c1, c2, out):
+        assert t is None or t.dtype == A.dtype
+    assert B * Nn == W.numel() and Y.numel() == items * M and all(t is None or t.numel() == B * Nn for t in (W2, c1, c2, out))
+    assert mbd is None or (mbd.dtype == torch.int64 and tuple(mbd.shape) == (B, 2))
+    assert ind is None or (ind.dtype == torch.uint8 and tuple(ind.shape) == (B, M))
+    if workspace is None:
+        workspace = pr_shared_workspace(M, Nn, A.dtype, A.device, B)
+    assert workspace.dtype == A.dtype and workspace.numel() >= N.lib().pnp_pr_shared_workspace_elems(M, Nn, B)
+    out = out if out is not None else torch.empty((B, Nn), dtype=A.dtype, device=A.device)
+    _route('pnp_pr_grad_shared', [_p(A), _p(Y), _p(W), _p(W2), _p(mbd), _p(ind), M, Nn, B, items, _DT[A.dtype], _pp(alpha, B),
+                                  float(alpha_div), float(beta), _p(c1), _pp(gamma, B), _p(c2), _p(workspace), _p(out), _stream()])
+    return out
+
+
 def draw_thresholds(M, B, mb, seed, step0, nsteps=1, out=None, step_dev=None, device='cuda', draw_id=None):
     """Device-side draws of `mb` of M measurements for B problems and `nsteps` steps -> descriptors int64 [nsteps, B, 2].
     mb: an int, or an int32 [B] device tensor; draw_id: int32 [B] ids absorbed in place of the batch index (pnp_draw_thresholds_pp)."""

@@ -152,7 +152,8 @@ def make_prox(denoiser, **kw):
 
 def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta, n_inner, mini_batch_size=None, T2=None,
                 hist_size=50, H=256, W=256, dtype=torch.float32, max_batch=128, seeding='generator', variant='svrg', run_seed=1,
-                keep_trace=False, graph=True, kernel='Minimal', lr_decay=1.0, denoiser_kwargs=None, sigma_modifier=None):
+                keep_trace=False, graph=True, kernel='Minimal', lr_decay=1.0, denoiser_kwargs=None, sigma_modifier=None,
+                shared_matrix=False):
     """Runner for `run_sweep` / `grid_search` over any cell of the reference's sweep (script_diff_sampratio_set12.py:23-25,
     41-51, 64-131): problem in {'csmri', 'deblur', 'pr'} x algorithm in {'gd', 'sgd', 'svrg', 'saga', 'sarah'} x denoiser in
     {'tv', 'nlm', factory}; `n_inner` inner iterations (prox evaluations of the stepped iterate) per item, hyper-parameters
@@ -176,6 +177,9 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
                          iteration, algorithms/pnp_saga.py:25-29,43-47) -- so an item's trajectory equals the reference loop's
                          (and the oracle's) on the same seeds.
     sigma_modifier: shorthand for denoiser_kwargs={'sigma_modifier': ...}, so that a search grid can name it as a key.
+    shared_matrix: problem='pr' only (ValueError otherwise): a trial-batched grid runs its trials on `PrBatch.tile`, every trial of
+    an item on that item's ONE matrix A (nothing of A is copied; csrc/pr_shared.hip streams it twice per gradient whatever the
+    number of trials).  Without it `check_trials` refuses 'pr'.  `run(items)` itself is unchanged by it.
     Beside `run(items)` the runner offers the pieces of a trial-batched grid (`grid_search(batch_trials=True)`):
     `run.prepare_data(items)` builds a rank's batches WITHOUT engines, `run.run_trials(data, trials, max_batch_trials)` runs a list
     of trials ({'eta', 'mini_batch_size', 'sigma_modifier'} overrides) on them as tiled batches, `run.data_key` says which runners
@@ -190,6 +194,8 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
         raise ValueError('T2 is required')
     if seeding == 'device' and problem != 'csmri':
         raise ValueError(f"seeding='device' is supported for problem='csmri' only (got {problem!r}); use 'generator' or 'legacy'")
+    if shared_matrix and problem != 'pr':
+        raise ValueError(f"shared_matrix=True is for problem='pr' (got {problem!r}): only its problems have a matrix to share")
     mb, dkw = mini_batch_size, dict(denoiser_kwargs or {})
     if sigma_modifier is not None:
         dkw['sigma_modifier'] = sigma_modifier
@@ -359,8 +365,11 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
 
     def check_trials(trials):
         """What a trial-batched run supports, each refusal naming the offender."""
-        if problem != 'csmri':
-            raise ValueError(f"batch_trials: problem {problem!r} is not supported (only 'csmri')")
+        if problem == 'pr' and not shared_matrix:
+            raise ValueError(f"batch_trials: problem {problem!r} is not supported (only 'csmri') unless its trials share the "
+                             'matrix: pass shared_matrix=True to make_runner')
+        if problem not in ('csmri', 'pr'):
+            raise ValueError(f"batch_trials: problem {problem!r} is not supported (only 'csmri', and 'pr' with shared_matrix=True)")
         if algorithm not in ('gd', 'sgd', 'svrg'):
             raise ValueError(f"batch_trials: algorithm {algorithm!r} is not supported (only 'gd', 'sgd', 'svrg')")
         if denoiser == 'nlm':
@@ -499,7 +508,8 @@ def grid_search(items, make_runner, grid, group=None, *, batch_trials=False, max
     search the hyper-parameters and keep the best trial.  `make_runner(**params)` returns a runner as `run_sweep`
     takes; each rank runs every trial on ITS shard of the items (one batched engine per trial), the reduction over
     trials is local and the single gather at the end carries one small row per item.
-    batch_trials=True (CSMRI; gd, sgd, svrg; not NLM; not legacy seeding -- ValueError otherwise): the trials of a rank run as
+    batch_trials=True (CSMRI, or PR from runners made with shared_matrix=True: every trial of an item then works on the item's one
+    matrix, which is never copied; gd, sgd, svrg; not NLM; not legacy seeding -- ValueError otherwise): the trials of a rank run as
     ONE batch per chunk instead of one after the other.  Keys 'eta', 'mini_batch_size', 'sigma_modifier' become
     per-problem vectors; trials are grouped by every other key (T2 included), the problem data of a chunk is prepared once and
     shared by all groups, and a group runs on the chunk tiled once per trial in slabs of at most max_batch_trials problems.
