@@ -243,6 +243,14 @@ int pnp_deblur_grad_mb(pnp_deblur_plan* plan, const void* z, const void* Y, cons
                        void* out, void* stream);
 /* forward model S B x (DeblurSR.py:110-112): out [batch][M]                                     */
 int pnp_deblur_forward(pnp_deblur_plan* plan, const void* x, void* out, void* stream);
+/* _pp forms of the two gradients (a Deblur grid as one batch): problem b is scaled by scale_pp ? scale_pp[b] : scale.
+ * Its output factor is formed as the plain call forms it on the host -- (dtype)(scale_b / sqrt((double)(H*W))), the quotient in
+ * double, then the cast -- so problem b equals, bit for bit, problem b of the plain call made with scale_b.  The descriptors of
+ * _mb_pp come from pnp_draw_thresholds_pp (per-problem minibatch sizes and stream ids).                              */
+int pnp_deblur_grad_pp(pnp_deblur_plan* plan, const void* z, const void* Y, const uint8_t* sel, double scale,
+                       const double* scale_pp, void* out, void* stream);
+int pnp_deblur_grad_mb_pp(pnp_deblur_plan* plan, const void* z, const void* Y, const void* mbd, double scale,
+                          const double* scale_pp, void* out, void* stream);
 
 /* ------------------------------------------------------------------ phase retrieval
  * Replaces problems/PR.py:75-87.  A [M][N] row-major, w [N], y [M] (device, `dtype`).
@@ -367,6 +375,13 @@ int pnp_nlm2d(const void* z_in, void* z_out, int H, int W, int batch, int dtype,
               int patch_distance, const void* sigma_in, double sigma_modifier, double fixed_h,
               const double* w0, double w0_sum, const void* xrec, double* sse_out, double* sse_workspace,
               void* stream);
+/* _pp form: h = sigma = sigma_in[b] * (sigma_modifier_pp ? sigma_modifier_pp[b] : sigma_modifier), the product taken in double
+ * and cast as in the plain call ([batch] doubles on the device; without sigma_in the modifier is not read).  Both kernel forms
+ * (LDS-streaming and register-strip) have it; image b equals, bit for bit, image b of the plain call made with its modifier. */
+int pnp_nlm2d_pp(const void* z_in, void* z_out, int H, int W, int batch, int dtype, int patch_size,
+                 int patch_distance, const void* sigma_in, double sigma_modifier, const double* sigma_modifier_pp,
+                 double fixed_h, const double* w0, double w0_sum, const void* xrec, double* sse_out,
+                 double* sse_workspace, void* stream);
 
 /* sum (xrec - z)^2 per problem (Problem.PSNR, problems/problem.py:33-35). sse_out: [batch] double */
 int pnp_sse(const void* z, const void* xrec, int n_per_problem, int batch, int dtype, double* sse_out, void* stream);
@@ -466,6 +481,16 @@ int pnp_indicator_from_indices(const int32_t* idx, int n, int M, int batch, uint
  * written by the previous step (may be the same row), sum = running sum of the table (== sum(table), :47).   */
 int pnp_saga_table_update(void* z, const void* g, void* slot, const void* prev, void* sum, double lr, double inv_hist,
                           size_t n, int dtype, void* stream);
+/* The same step for a whole batch in ONE launch when the problems replace different rows or step with different sizes (_pp form):
+ * table [hist][batch][N] is the table base, problem b replaces row[b] and its previous step wrote prev_row[b] (int32 [batch] on
+ * the device, each in [0, hist); the call does not synchronise and cannot check them: the caller does), and steps with
+ * lr_pp ? lr_pp[b] : lr ([batch] doubles on the device, cast to `dtype` as the plain call casts lr).  z, g, sum [batch][N].  Per
+ * element the arithmetic and its order are those of pnp_saga_table_update, row[b] == prev_row[b] included (prev is read before the
+ * slot is written, by the same thread), so problem b equals, bit for bit, the plain call on its views.  N must be a multiple of 4
+ * and the pointers 16-byte aligned (vector loads and stores); PNP_ERR_ARG otherwise.                                  */
+int pnp_saga_table_update_pp(void* z, const void* g, void* table, const int32_t* row, const int32_t* prev_row, void* sum,
+                             double lr, const double* lr_pp, double inv_hist, int hist, int batch, int N, int dtype,
+                             void* stream);
 
 /* ------------------------------------------------------------------ elementwise
  * out = a*x + b*y + c*w   (y, w may be NULL); n = total element count.

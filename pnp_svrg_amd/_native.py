@@ -89,6 +89,10 @@ SIGNATURES = {
     'pnp_pr_shared_workspace_elems': (_sz, [_i, _i, _i]),
     'pnp_pr_grad_shared': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _d, _d, _d, _vp, _d, _vp, _vp, _vp, _vp]),
     'pnp_pr_grad_shared_pp': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _d, _vp, _d, _d, _vp, _d, _vp, _vp, _vp, _vp, _vp]),
+    'pnp_deblur_grad_pp': (_i, [_vp, _vp, _vp, _vp, _d, _vp, _vp, _vp]),
+    'pnp_deblur_grad_mb_pp': (_i, [_vp, _vp, _vp, _vp, _d, _vp, _vp, _vp]),
+    'pnp_nlm2d_pp': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _d, _vp, _d, _vp, _d, _vp, _vp, _vp, _vp]),
+    'pnp_saga_table_update_pp': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _d, _vp, _d, _i, _i, _i, _i, _vp]),
     'pnp_legacy_choice': (_i, [_vp, ctypes.POINTER(ctypes.c_int), _vp, _i, _i, _vp, _vp]),
 }
 

@@ -118,10 +118,29 @@ class _BatchBase:
         return self._tmp
 
     def _combine(self, g, out, beta, c1, gamma=0.0, c2=None):
-        """g + beta * c1 + gamma * c2 -> out.  With nothing to add, a gradient that was written to `out` is the result as it is."""
+        """g + beta * c1 + gamma * c2 -> out.  With nothing to add, a gradient that was written to `out` is the result as it is.
+        pnp_axpbypcz has scalar coefficients: a per-problem gamma (float64 [B] device tensor) takes one launch per problem on that
+        problem's views, each the scalar call with its value."""
         if c1 is None and c2 is None:
             return g if g is out else out.copy_(g)
+        if isinstance(gamma, torch.Tensor):
+            gam = self._host(gamma)
+            for i in range(self.B):
+                ops.axpbypcz(1.0, g[i], beta, None if c1 is None else c1[i], float(gam[i]), c2[i], out=out[i])
+            return out
         return ops.axpbypcz(1.0, g, beta, c1, gamma, c2, out=out)
+
+    def _host(self, t, fn=None):
+        """The host copy of a per-problem coefficient vector (a float64 [B] device tensor the engines upload once), or fn(host copy)
+        uploaded again: read back once per tensor and kept while the engine keeps passing that very tensor."""
+        hit = getattr(self, '_host_cache', None)
+        if hit is None or hit[0] is not t:
+            hit = self._host_cache = (t, t.cpu().numpy(), {})
+        if fn is None:
+            return hit[1]
+        if fn not in hit[2]:
+            hit[2][fn] = torch.from_numpy(np.ascontiguousarray(fn(hit[1]), np.float64)).to(t.device)
+        return hit[2][fn]
 
 
 class CsmriBatch(_BatchBase):
@@ -275,6 +294,7 @@ class DeblurBatch(_BatchBase):
     """B Deblur / super-resolution problems sharing one blur kernel and one down-sampler (reference
     problems/DeblurSR.py:17-147 per problem; the sweeps vary image, noise and seed, not the operator)."""
     kind = 'deblur'
+    per_problem = True
 
     def __init__(self, xrec, Bk, Y, xinit, dtype=torch.float32, device='cuda', bilinear=None, *, _state=None):
         if _state is not None:
@@ -340,9 +360,25 @@ class DeblurBatch(_BatchBase):
         out = np.stack([[rng.choice(self.M, mb, replace=False) for _ in range(self.B)] for _ in range(n_steps)]).astype(np.int32)
         return torch.from_numpy(out).to(self.device)
 
-    def draw(self, mbs, mb, seed, step0, nsteps=1, step_dev=None):
-        self._check_mb(mb)
-        ops.draw_thresholds(self.M, self.B, mb, seed, step0, nsteps, out=mbs.mbd[:nsteps], step_dev=step_dev)
+    def tile(self, n):
+        """A batch of n * B problems (problem t * B + i = this batch's problem i) on the same kernel spectrum and down-sampler: a plan
+        for n * B problems, xrec, xinit, Y and sigma repeated by device copies -- what a trial-batched grid runs on."""
+        n = int(n)
+        if n < 1:
+            raise ValueError('tile(n) needs n >= 1')
+        rep = lambda v: None if v is None else v.repeat((n,) + (1,) * (v.dim() - 1)).contiguous()
+        return self._of(plan=self.plan.resized(self.B * n), xrec=rep(self.xrec), xinit=rep(self.xinit), Y=rep(self.Y),
+                        sigma=rep(self.sigma))
+
+    def draw(self, mbs, mb, seed, step0, nsteps=1, step_dev=None, draw_id=None):
+        """mb: an int, or per problem: [B] integers on the host (checked, then uploaded) or an int32 [B] device tensor (taken as
+        checked: the engines check their host copy once).  draw_id: int32 [B] device tensor, the ids the minibatch streams absorb in
+        place of the batch index."""
+        if not isinstance(mb, torch.Tensor):
+            self._check_mb(mb)
+            if np.ndim(mb) != 0:
+                mb = torch.from_numpy(np.ascontiguousarray(mb, np.int32)).to(self.device)
+        ops.draw_thresholds(self.M, self.B, mb, seed, step0, nsteps, out=mbs.mbd[:nsteps], step_dev=step_dev, draw_id=draw_id)
         for j in range(nsteps):
             mbs.host[j] = None
 
@@ -355,8 +391,14 @@ class DeblurBatch(_BatchBase):
             return dict(sel=mbs.host[j])
         return dict(mbd=mbs.mbd[j])
 
+    # alpha (and gamma of grad_stoch_diff): a scalar -> the plain calls; a float64 [B] device tensor -> the `_pp` entry points
+    def _over_m(self, a):
+        return a / self.M
+
     def grad_full(self, z, out, alpha=1.0, beta=0.0, c1=None):
-        g = self.plan.grad(z, self.Y, scale=alpha / self.M, out=out if c1 is None else self._scratch(z))
+        # (per problem: alpha_b / M taken on the host in float64, as the scalar's quotient is)
+        scale = self._host(alpha, self._over_m) if isinstance(alpha, torch.Tensor) else alpha / self.M
+        g = self.plan.grad(z, self.Y, scale=scale, out=out if c1 is None else self._scratch(z))
         return self._combine(g, out, beta, c1)
 
     def grad_stoch(self, z, mbs, j, out, alpha=1.0, beta=0.0, c1=None):

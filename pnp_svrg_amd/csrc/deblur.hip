@@ -40,11 +40,14 @@ template <typename T, int RA, int LA> struct LineSmem {
 //   IN_REAL : input real T [n][n]           else complex
 //   TWIDDLE : multiply output k1 of column b by W_N^(+-b*k1)
 //   OUT_REAL: out real = sel ? alpha*Re(v) + beta*c : 0      else complex
-template <typename T, int RA, int LA, bool INV, bool IN_REAL, bool TWIDDLE, bool OUT_REAL>
+//   PP      : alpha of problem b = (T)(alpha_pp[b] / alpha_div), the quotient in double (the _pp gradients: what the host makes
+//             of a scalar scale, per problem); the other instantiations do not read the two arguments
+template <typename T, int RA, int LA, bool INV, bool IN_REAL, bool TWIDDLE, bool OUT_REAL, bool PP = false>
 __global__ __launch_bounds__(256) void k_colpass(const void* __restrict__ in_, void* __restrict__ out_,
                                                  const cx<T>* __restrict__ tw_line, const cx<T>* __restrict__ tw_big,
                                                  T alpha, T beta, const T* __restrict__ c, const uint8_t* __restrict__ sel,
-                                                 const MbDesc* __restrict__ mbd) {
+                                                 const MbDesc* __restrict__ mbd, const double* __restrict__ alpha_pp,
+                                                 double alpha_div) {
     using S = LineSmem<T, RA, LA>;
     constexpr int N = S::N, G = S::G, LG = S::LG;
     __shared__ cx<T> smem[S::ELEMS];
@@ -52,6 +55,7 @@ __global__ __launch_bounds__(256) void k_colpass(const void* __restrict__ in_, v
     const int prob = blockIdx.y, b0 = blockIdx.x * G;
     const size_t base = (size_t)prob * N * N;
     const int p = t % G;
+    if constexpr (PP) alpha = (T)(alpha_pp[prob] / alpha_div);
     for (int a = t / G; a < N; a += 256 / G) {
         const size_t i = base + (size_t)a * N + b0 + p;
         cx<T> val;
@@ -177,7 +181,7 @@ template <typename T, int RA, int LA>
 int col_fwd(pnp_deblur_plan* p, const T* x, int batch, hipStream_t s) {
     constexpr int G = LineSmem<T, RA, LA>::G;
     k_colpass<T, RA, LA, false, true, true, false><<<dim3(p->n / G, batch), 256, 0, s>>>(
-        x, p->w0, (const cx<T>*)p->tw_line, (const cx<T>*)p->tw_big, (T)0, (T)0, nullptr, nullptr, nullptr);
+        x, p->w0, (const cx<T>*)p->tw_line, (const cx<T>*)p->tw_big, (T)0, (T)0, nullptr, nullptr, nullptr, nullptr, 0.0);
     PNP_CHECK_LAUNCH();
     return PNP_OK;
 }
@@ -185,7 +189,7 @@ int col_fwd(pnp_deblur_plan* p, const T* x, int batch, hipStream_t s) {
 // one blur: out = sel ? alpha * (x (*) kernel) * sqrt(N)-normalised + beta*c : 0
 template <typename T, int RA, int LA>
 int blur(pnp_deblur_plan* p, const T* x, bool conj_kernel, T alpha, T beta, const T* c, const uint8_t* sel, T* out,
-         hipStream_t s, const MbDesc* mbd = nullptr) {
+         hipStream_t s, const MbDesc* mbd = nullptr, const double* alpha_pp = nullptr, double alpha_div = 1.0) {
     constexpr int G = LineSmem<T, RA, LA>::G;
     const int B = p->batch;
     int rc = col_fwd<T, RA, LA>(p, x, B, s);
@@ -197,15 +201,19 @@ int blur(pnp_deblur_plan* p, const T* x, bool conj_kernel, T alpha, T beta, cons
     else
         k_rowpass<T, RA, LA, false, false><<<grid, 256, 0, s>>>(w0, w0, (const cx<T>*)p->tw_line, (const cx<T>*)p->tw_big, (const cx<T>*)p->FB);
     PNP_CHECK_LAUNCH();
-    k_colpass<T, RA, LA, true, false, false, true><<<grid, 256, 0, s>>>(w0, out, (const cx<T>*)p->tw_line, (const cx<T>*)p->tw_big,
-                                                                  alpha, beta, c, sel, mbd);
+    if (alpha_pp != nullptr)                                     // per-problem output factor alpha_pp[b] / alpha_div
+        k_colpass<T, RA, LA, true, false, false, true, true><<<grid, 256, 0, s>>>(w0, out, (const cx<T>*)p->tw_line, (const cx<T>*)p->tw_big,
+                                                                            alpha, beta, c, sel, mbd, alpha_pp, alpha_div);
+    else
+        k_colpass<T, RA, LA, true, false, false, true><<<grid, 256, 0, s>>>(w0, out, (const cx<T>*)p->tw_line, (const cx<T>*)p->tw_big,
+                                                                      alpha, beta, c, sel, mbd, nullptr, 0.0);
     PNP_CHECK_LAUNCH();
     return PNP_OK;
 }
 
 template <typename T, int RA, int LA>
 int run_grad(pnp_deblur_plan* p, const T* z, const T* Y, const uint8_t* sel, double scale, T* out, hipStream_t s,
-             const MbDesc* mbd = nullptr) {
+             const MbDesc* mbd = nullptr, const double* scale_pp = nullptr) {
     const int N = p->N, B = p->batch;
     const T inv_sqrtN = (T)(1.0 / std::sqrt((double)N));           // Re ifft(.) * sqrt(N); the inverse carries 1/N
     T* res = (T*)p->r0;
@@ -223,7 +231,8 @@ int run_grad(pnp_deblur_plan* p, const T* z, const T* Y, const uint8_t* sel, dou
         k_csr<T><<<dim3((N + 255) / 256, B), 256, 0, s>>>(down, p->a_rowptr, p->a_col, (const T*)p->a_val, N, p->M, res);
         PNP_CHECK_LAUNCH();
     }
-    return blur<T, RA, LA>(p, res, true, (T)(scale / std::sqrt((double)N)), (T)0, nullptr, nullptr, out, s);
+    return blur<T, RA, LA>(p, res, true, (T)(scale / std::sqrt((double)N)), (T)0, nullptr, nullptr, out, s, nullptr, scale_pp,
+                           std::sqrt((double)N));
 }
 
 template <typename T, int RA, int LA>
@@ -337,6 +346,35 @@ extern "C" int pnp_deblur_plan_destroy(pnp_deblur_plan* p) {
         if (q) (void)hipFree(q);
     delete p;
     return PNP_OK;
+}
+
+// the _pp forms: one dispatch over dtype and line length for both (sel or descriptors, never both)
+static int grad_pp(pnp_deblur_plan* p, const void* z, const void* Y, const uint8_t* sel, const MbDesc* d, double scale,
+                   const double* scale_pp, void* out, hipStream_t s) {
+    if (p->dtype == PNP_F32) {
+        const float *zz = (const float*)z, *yy = (const float*)Y;
+        float* oo = (float*)out;
+        return p->NL == 16 ? run_grad<float, 16, 16>(p, zz, yy, sel, scale, oo, s, d, scale_pp)
+             : p->NL == 12 ? run_grad<float, 8, 16>(p, zz, yy, sel, scale, oo, s, d, scale_pp)
+                           : run_grad<float, 8, 8>(p, zz, yy, sel, scale, oo, s, d, scale_pp);
+    }
+    const double *zz = (const double*)z, *yy = (const double*)Y;
+    double* oo = (double*)out;
+    return p->NL == 16 ? run_grad<double, 16, 16>(p, zz, yy, sel, scale, oo, s, d, scale_pp)
+         : p->NL == 12 ? run_grad<double, 8, 16>(p, zz, yy, sel, scale, oo, s, d, scale_pp)
+                       : run_grad<double, 8, 8>(p, zz, yy, sel, scale, oo, s, d, scale_pp);
+}
+
+extern "C" int pnp_deblur_grad_pp(pnp_deblur_plan* p, const void* z, const void* Y, const uint8_t* sel, double scale,
+                                  const double* scale_pp, void* out, void* stream) {
+    PNP_CHECK_ARG(p && z && Y && out, "null argument");
+    return grad_pp(p, z, Y, sel, nullptr, scale, scale_pp, out, (hipStream_t)stream);
+}
+
+extern "C" int pnp_deblur_grad_mb_pp(pnp_deblur_plan* p, const void* z, const void* Y, const void* mbd, double scale,
+                                     const double* scale_pp, void* out, void* stream) {
+    PNP_CHECK_ARG(p && z && Y && mbd && out, "null argument");
+    return grad_pp(p, z, Y, nullptr, (const MbDesc*)mbd, scale, scale_pp, out, (hipStream_t)stream);
 }
 
 // out = scale * B^T S^T ( sel o (S B z - Y) );  sel (uint8 [batch][M], may be NULL = all measurements)

@@ -32,11 +32,14 @@ __device__ __forceinline__ int reflect_idx(int i, int n) {   // np.pad(mode='ref
     return i;
 }
 
-template <typename T, int S>
+// PP (pnp_nlm2d_pp): the modifier of image b is modifier_pp[b], a double like the scalar it replaces; the plain instantiation
+// does not read the argument.
+template <typename T, int S, bool PP = false>
 __global__ __launch_bounds__(NT * NT) void k_nlm(const T* __restrict__ zin, T* __restrict__ zout, int H, int W, int d,
                                                  const T* __restrict__ sigma_in, double modifier, double fixed_h,
                                                  const double* __restrict__ w0, double w0_sum,
-                                                 const T* __restrict__ xrec, double* __restrict__ sse_part) {
+                                                 const T* __restrict__ xrec, double* __restrict__ sse_part,
+                                                 const double* __restrict__ modifier_pp) {
     constexpr int OFF = S / 2;
     __shared__ T tile[NLM_MAX_SIDE * NLM_MAX_SIDE];
     __shared__ double red[4];
@@ -57,6 +60,7 @@ __global__ __launch_bounds__(NT * NT) void k_nlm(const T* __restrict__ zin, T* _
     // h, var and the patch weights (NLM.py:24-27; non_local_means.py:153)
     T h, var;
     if (sigma_in != nullptr) {
+        if constexpr (PP) modifier = modifier_pp[b];
         h = (T)((double)sigma_in[b] * modifier);
         var = (T)2 * (h * h);
     } else {
@@ -135,11 +139,12 @@ __global__ __launch_bounds__(NT * NT) void k_nlm(const T* __restrict__ zin, T* _
 // k_nlm is bound by its ds_read_b32 stream (25.6 KB per window offset and workgroup against ~150 cycles of arithmetic).
 // Arithmetic and its order are those of k_nlm (the running distance is tested before every patch row; a dead candidate
 // simply stops counting), so the f64 instantiation stays bit-exact.
-template <typename T, int S, int D>
+template <typename T, int S, int D, bool PP = false>
 __global__ __launch_bounds__(NT * NT) void k_nlm_strip(const T* __restrict__ zin, T* __restrict__ zout, int H, int W,
                                                        const T* __restrict__ sigma_in, double modifier, double fixed_h,
                                                        const double* __restrict__ w0, double w0_sum,
-                                                       const T* __restrict__ xrec, double* __restrict__ sse_part) {
+                                                       const T* __restrict__ xrec, double* __restrict__ sse_part,
+                                                       const double* __restrict__ modifier_pp) {
     constexpr int OFF = S / 2, SIDE = NT + 2 * D + S - 1, SW = S + 2 * D;
     __shared__ T tile[SIDE * SIDE];
     __shared__ double red[4];
@@ -157,6 +162,7 @@ __global__ __launch_bounds__(NT * NT) void k_nlm_strip(const T* __restrict__ zin
 
     T h, var;
     if (sigma_in != nullptr) {
+        if constexpr (PP) modifier = modifier_pp[b];
         h = (T)((double)sigma_in[b] * modifier);
         var = (T)2 * (h * h);
     } else {
@@ -246,14 +252,18 @@ __global__ void k_sum_parts_nlm(const double* __restrict__ part, int nparts, dou
 template <typename T, int S>
 int launch_nlm(const void* zin, void* zout, int H, int W, int batch, int d, const void* sigma_in, double modifier,
                double fixed_h, const double* w0, double w0_sum, const void* xrec, double* sse_out, double* sse_part,
-               hipStream_t s) {
+               hipStream_t s, const double* modifier_pp) {
     dim3 grid((W + NT - 1) / NT, (H + NT - 1) / NT, batch);
     static const bool generic = getenv("PNP_NLM_GENERIC") != nullptr;      // diagnostic: the LDS-streaming form for every radius
     if constexpr (S == 5) {                                                 // the reference's configuration (denoisers/NLM.py:22-27)
         // (f64, the parity mode, needs 256 VGPRs for the strip: one wave per SIMD, slower than the LDS form on large batches)
         if (d == 5 && !generic && (sizeof(T) == 4 || batch <= 4)) {
-            k_nlm_strip<T, 5, 5><<<grid, NT * NT, 0, s>>>((const T*)zin, (T*)zout, H, W, (const T*)sigma_in, modifier, fixed_h, w0,
-                                                          w0_sum, (const T*)xrec, sse_out ? sse_part : nullptr);
+            if (modifier_pp != nullptr)
+                k_nlm_strip<T, 5, 5, true><<<grid, NT * NT, 0, s>>>((const T*)zin, (T*)zout, H, W, (const T*)sigma_in, modifier, fixed_h,
+                                                                    w0, w0_sum, (const T*)xrec, sse_out ? sse_part : nullptr, modifier_pp);
+            else
+                k_nlm_strip<T, 5, 5><<<grid, NT * NT, 0, s>>>((const T*)zin, (T*)zout, H, W, (const T*)sigma_in, modifier, fixed_h, w0,
+                                                              w0_sum, (const T*)xrec, sse_out ? sse_part : nullptr, nullptr);
             PNP_CHECK_LAUNCH();
             if (sse_out) {
                 k_sum_parts_nlm<<<batch, 64, 0, s>>>(sse_part, (int)(grid.x * grid.y), sse_out);
@@ -262,10 +272,12 @@ int launch_nlm(const void* zin, void* zout, int H, int W, int batch, int d, cons
             return PNP_OK;
         }
     }
-    {
+    if (modifier_pp != nullptr)
+        k_nlm<T, S, true><<<grid, NT * NT, 0, s>>>((const T*)zin, (T*)zout, H, W, d, (const T*)sigma_in, modifier, fixed_h, w0,
+                                                   w0_sum, (const T*)xrec, sse_out ? sse_part : nullptr, modifier_pp);
+    else
         k_nlm<T, S><<<grid, NT * NT, 0, s>>>((const T*)zin, (T*)zout, H, W, d, (const T*)sigma_in, modifier, fixed_h, w0,
-                                             w0_sum, (const T*)xrec, sse_out ? sse_part : nullptr);
-    }
+                                             w0_sum, (const T*)xrec, sse_out ? sse_part : nullptr, nullptr);
     PNP_CHECK_LAUNCH();
     if (sse_out) {
         k_sum_parts_nlm<<<batch, 64, 0, s>>>(sse_part, (int)(grid.x * grid.y), sse_out);
@@ -278,10 +290,10 @@ int launch_nlm(const void* zin, void* zout, int H, int W, int batch, int d, cons
 
 using namespace pnp;
 
-extern "C" int pnp_nlm2d(const void* z_in, void* z_out, int H, int W, int batch, int dtype, int patch_size,
-                         int patch_distance, const void* sigma_in, double sigma_modifier, double fixed_h,
-                         const double* w0, double w0_sum, const void* xrec, double* sse_out, double* sse_workspace,
-                         void* stream) {
+// both entry points: the argument checks and the dispatch over dtype and patch side
+static int nlm2d(const void* z_in, void* z_out, int H, int W, int batch, int dtype, int patch_size, int patch_distance,
+                 const void* sigma_in, double sigma_modifier, const double* sigma_modifier_pp, double fixed_h, const double* w0,
+                 double w0_sum, const void* xrec, double* sse_out, double* sse_workspace, void* stream) {
     PNP_CHECK_ARG(z_in && z_out && w0 && batch >= 1, "null argument");
     PNP_CHECK_ARG(z_in != z_out, "NLM cannot run in place (every output reads an 15x15 input neighbourhood)");
     const int s = patch_size % 2 == 0 ? patch_size + 1 : patch_size;          // skimage bumps even sizes
@@ -290,7 +302,7 @@ extern "C" int pnp_nlm2d(const void* z_in, void* z_out, int H, int W, int batch,
     PNP_CHECK_ARG(!(sse_out && !(xrec && sse_workspace)), "sse_out needs xrec and a workspace");
     PNP_CHECK_ARG(dtype == PNP_F32 || dtype == PNP_F64, "bad dtype");
     hipStream_t st = (hipStream_t)stream;
-#define PNP_NLM_CASE(TT, SS) return launch_nlm<TT, SS>(z_in, z_out, H, W, batch, patch_distance, sigma_in, sigma_modifier, fixed_h, w0, w0_sum, xrec, sse_out, sse_workspace, st)
+#define PNP_NLM_CASE(TT, SS) return launch_nlm<TT, SS>(z_in, z_out, H, W, batch, patch_distance, sigma_in, sigma_modifier, fixed_h, w0, w0_sum, xrec, sse_out, sse_workspace, st, sigma_modifier_pp)
     if (dtype == PNP_F64) {
         if (s == 3) PNP_NLM_CASE(double, 3);
         if (s == 5) PNP_NLM_CASE(double, 5);
@@ -300,4 +312,20 @@ extern "C" int pnp_nlm2d(const void* z_in, void* z_out, int H, int W, int batch,
     if (s == 5) PNP_NLM_CASE(float, 5);
     PNP_NLM_CASE(float, 7);
 #undef PNP_NLM_CASE
+}
+
+extern "C" int pnp_nlm2d(const void* z_in, void* z_out, int H, int W, int batch, int dtype, int patch_size,
+                         int patch_distance, const void* sigma_in, double sigma_modifier, double fixed_h,
+                         const double* w0, double w0_sum, const void* xrec, double* sse_out, double* sse_workspace,
+                         void* stream) {
+    return nlm2d(z_in, z_out, H, W, batch, dtype, patch_size, patch_distance, sigma_in, sigma_modifier, nullptr, fixed_h, w0, w0_sum,
+                 xrec, sse_out, sse_workspace, stream);
+}
+
+extern "C" int pnp_nlm2d_pp(const void* z_in, void* z_out, int H, int W, int batch, int dtype, int patch_size,
+                            int patch_distance, const void* sigma_in, double sigma_modifier, const double* sigma_modifier_pp,
+                            double fixed_h, const double* w0, double w0_sum, const void* xrec, double* sse_out,
+                            double* sse_workspace, void* stream) {
+    return nlm2d(z_in, z_out, H, W, batch, dtype, patch_size, patch_distance, sigma_in, sigma_modifier, sigma_modifier_pp, fixed_h,
+                 w0, w0_sum, xrec, sse_out, sse_workspace, stream);
 }

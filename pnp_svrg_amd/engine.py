@@ -17,6 +17,9 @@ lr_decay != 1 changes them), and problem b then walks, bit for bit, the trajecto
 `draw_id` ([B] ints) replaces the batch index in the minibatch stream, and `CsmriBatch.tile(n)` repeats a batch's data n times.
 A batch says whether it takes them with its `per_problem` attribute: a CsmriBatch does, and so does `PrBatch.tile(n)`, n * B problems
 on the B matrices of the batch it was tiled from (the non-fused paths only; csrc/pr_shared.hip).
+A DeblurBatch takes them too (`DeblurBatch.tile(n)`: one plan for n * B problems on the same kernel spectrum), NLMProx takes a [B]
+`sigma_modifier`, and SagaEngine takes `eta`, `mini_batch_size` and `draw_id` per problem: a step is then ONE
+`pnp_saga_table_update_pp` launch, as it is when every problem replaces a row of its own.  SarahEngine stays scalar.
 """
 import numpy as np
 import torch
@@ -354,6 +357,8 @@ class SarahEngine(_StochEngine):
     inner loop, and the outer step ignores lr_decay.  One log row per prox: outer rows at s % T2 == 0."""
 
     def __init__(self, batch, prox, eta, T2, mini_batch_size, lr_decay=1.0, n_log=4096, seed=0):
+        if np.ndim(eta) != 0 or np.ndim(mini_batch_size) != 0:
+            raise ValueError('SarahEngine takes a scalar eta and mini_batch_size (pnp_axpbypcz has no per-problem form)')
         super().__init__(batch, prox, eta, mini_batch_size, lr_decay, n_log, seed)
         self.T2 = T2
         self.w_prev = torch.empty_like(self.z)
@@ -385,14 +390,15 @@ class SagaEngine(_StochEngine):
     The replaced row r of every step is drawn on the host (one value per step for the whole batch; pass `r=` to
     `step` to impose the reference's `np.random.choice(hist_size, 1)` stream)."""
 
-    def __init__(self, batch, prox, eta, mini_batch_size, hist_size=50, lr_decay=1.0, n_log=4096, seed=0, idx0=None):
-        super().__init__(batch, prox, eta, mini_batch_size, lr_decay, n_log, seed)
+    def __init__(self, batch, prox, eta, mini_batch_size, hist_size=50, lr_decay=1.0, n_log=4096, seed=0, idx0=None, draw_id=None):
+        super().__init__(batch, prox, eta, mini_batch_size, lr_decay, n_log, seed, draw_id=draw_id)
         self.hist = hist_size
         self.g = torch.empty_like(self.z)
         self._rng = np.random.default_rng(seed + 977)
+        self._rows = None                                       # (host rows, their int32 device vector) of the last batched update
         # pnp_saga.py:25-31: one minibatch gradient at Xinit fills the whole table
         j = self._minibatch(idx0, 0xFFFFFFFF)
-        batch.grad_stoch(self.z, self.mbs, j, out=self.g, alpha=1.0 / self.mb)
+        batch.grad_stoch(self.z, self.mbs, j, out=self.g, alpha=self._c('1/mb', 0, 1.0 / self.mb))
         self.table = self.g.unsqueeze(0).repeat(hist_size, 1, 1, 1).contiguous()
         self.tsum = ops.axpbypcz(float(hist_size), self.g, out=torch.empty_like(self.g))
         self.r_prev = 0
@@ -400,24 +406,33 @@ class SagaEngine(_StochEngine):
     def reset(self):
         raise NotImplementedError('build a new SagaEngine (the table initialisation is part of the constructor)')
 
+    def _row_vec(self, r):
+        """Table rows (one for the batch, or one per problem) as the int32 [B] device vector of the batched update; the vector of
+        the previous step's rows is the one that step made."""
+        if self._rows is not None and r is self._rows[0]:
+            return self._rows[1]
+        rv = np.ascontiguousarray(np.broadcast_to(np.asarray(r, np.int32), (self.b.B,)))
+        return torch.from_numpy(rv).to(self.z.device)
+
     def step(self, idx_s=None, r=None):
         """r: the table row this step replaces -- one value for the whole batch, or one per problem (legacy-seeded sweeps:
         every item follows its own np.random stream, and with masks of different sizes the streams drift apart)."""
         j = self._minibatch(idx_s, self.s)
         if r is None:
             r = int(self._rng.integers(self.hist))
-        self.b.grad_stoch(self.z, self.mbs, j, out=self.g, alpha=1.0 / self.mb)
+        self.b.grad_stoch(self.z, self.mbs, j, out=self.g, alpha=self._c('1/mb', 0, 1.0 / self.mb))
         lr = self.eta * self.lr_decay ** self.s
-        if np.ndim(r) == 0 and np.ndim(self.r_prev) == 0:
+        if np.ndim(r) == 0 and np.ndim(self.r_prev) == 0 and np.ndim(lr) == 0:
             r = int(r)
             ops.saga_table_update(self.z, self.g, self.table[r], self.table[self.r_prev], self.tsum, lr, 1.0 / self.hist)
-        else:
-            rv = np.broadcast_to(np.asarray(r, np.int64), (self.b.B,))
-            pv = np.broadcast_to(np.asarray(self.r_prev, np.int64), (self.b.B,))
-            for b in range(self.b.B):
-                ops.saga_table_update(self.z[b], self.g[b], self.table[int(rv[b]), b], self.table[int(pv[b]), b], self.tsum[b],
-                                      lr, 1.0 / self.hist)
-            r = rv.copy()
+        else:                                                   # per-problem rows or step sizes: ONE launch for the batch
+            r = np.broadcast_to(np.asarray(r, np.int64), (self.b.B,)).copy()
+            if r.min() < 0 or r.max() >= self.hist:
+                raise ValueError(f'SAGA row outside the table: rows in [0, {self.hist}), got {r.tolist()}')
+            prev = self._row_vec(self.r_prev)
+            self._rows = (r, self._row_vec(r))
+            ops.saga_table_update_pp(self.z, self.g, self.table, self._rows[1], prev, self.tsum, self._c('lr', self.s, lr),
+                                     1.0 / self.hist)
         self.r_prev = r
         self.z = self._prox(self.z)
         self.s += 1

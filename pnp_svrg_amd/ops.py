@@ -424,7 +424,8 @@ def _nlm_w0(side, device):
 
 
 def nlm2d(z, sigma_in=None, sigma_modifier=1.0, fixed_h=0.0, patch_size=4, patch_distance=5, xrec=None, out=None, sse=None):
-    """skimage denoise_nl_means(slow mode) semantics on [B,H,W]; returns (denoised, sse or None)."""
+    """skimage denoise_nl_means(slow mode) semantics on [B,H,W]; returns (denoised, sse or None).
+    sigma_modifier: a scalar, or a float64 [B] device tensor (per image: pnp_nlm2d_pp)."""
     require_gpu()
     B, H, W = z.shape
     side = patch_size + 1 if patch_size % 2 == 0 else patch_size
@@ -434,8 +435,8 @@ def nlm2d(z, sigma_in=None, sigma_modifier=1.0, fixed_h=0.0, patch_size=4, patch
     if xrec is not None:
         sse = sse if sse is not None else torch.empty(B, dtype=torch.float64, device=z.device)
         ws = torch.empty(B * ((H + 15) // 16) * ((W + 15) // 16), dtype=torch.float64, device=z.device)
-    N.call('pnp_nlm2d', _p(z), _p(out), H, W, B, _DT[z.dtype], int(patch_size), int(patch_distance), _p(sigma_in),
-           float(sigma_modifier), float(fixed_h), _p(w0), w0_sum, _p(xrec), _p(sse), _p(ws), _stream())
+    _route('pnp_nlm2d', [_p(z), _p(out), H, W, B, _DT[z.dtype], int(patch_size), int(patch_distance), _p(sigma_in),
+                         _pp(sigma_modifier, B), float(fixed_h), _p(w0), w0_sum, _p(xrec), _p(sse), _p(ws), _stream()])
     return out, sse
 
 
@@ -448,6 +449,7 @@ class DeblurPlan:
         self.H, self.W, self.N, self.B, self.dtype = H, W, H * W, batch, dtype
         npdt = np.float32 if dtype == torch.float32 else np.float64
         Bk = np.ascontiguousarray(Bk, dtype=npdt)
+        self._Bk, self._bilinear = Bk, bilinear                 # (host arrays: what `resized` builds the next plan from)
         h = ctypes.c_void_p()
         vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
         if bilinear is None:
@@ -471,16 +473,21 @@ class DeblurPlan:
 
     def grad(self, z, Y, sel=None, scale=1.0, out=None, mbd=None):
         """scale * B^T S^T (sel o (S B z - Y)); sel: uint8 [B, M] indicator, or mbd: int64 [B, 2] = one step's
-        device-drawn minibatch descriptors (draw_thresholds), or neither (all measurements)."""
+        device-drawn minibatch descriptors (draw_thresholds), or neither (all measurements).
+        scale: a scalar, or a float64 [B] device tensor (per problem: pnp_deblur_grad_pp / pnp_deblur_grad_mb_pp)."""
         assert z.dtype == self.dtype and z.numel() == self.B * self.N and Y.numel() == self.B * self.M
         assert sel is None or mbd is None
         out = out if out is not None else torch.empty_like(z)
         if mbd is not None:
             assert mbd.dtype == torch.int64 and tuple(mbd.shape) == (self.B, 2)
-            N.call('pnp_deblur_grad_mb', self._h, _p(z), _p(Y), _p(mbd), float(scale), _p(out), _stream())
+            _route('pnp_deblur_grad_mb', [self._h, _p(z), _p(Y), _p(mbd), _pp(scale, self.B), _p(out), _stream()])
         else:
-            N.call('pnp_deblur_grad', self._h, _p(z), _p(Y), _p(sel), float(scale), _p(out), _stream())
+            _route('pnp_deblur_grad', [self._h, _p(z), _p(Y), _p(sel), _pp(scale, self.B), _p(out), _stream()])
         return out
+
+    def resized(self, batch):
+        """A plan for `batch` problems on this plan's kernel spectrum and down-sampler (DeblurBatch.tile)."""
+        return DeblurPlan(self.H, self.W, int(batch), self.dtype, self._Bk, bilinear=self._bilinear)
 
     def forward(self, x, out=None):
         out = out if out is not None else torch.empty(self.B * self.M, dtype=self.dtype, device=x.device)
@@ -649,6 +656,23 @@ def saga_table_update(z, g, slot, prev, tsum, lr, inv_hist):
         assert t.dtype == z.dtype and t.numel() == z.numel()
     N.call('pnp_saga_table_update', _p(z), _p(g), _p(slot), _p(prev), _p(tsum), float(lr), float(inv_hist), z.numel(),
            _DT[z.dtype], _stream())
+
+
+def saga_table_update_pp(z, g, table, row, prev_row, tsum, lr, inv_hist):
+    """pnp_saga_table_update_pp: one SAGA step of a whole batch in ONE launch.  z, g, tsum [B, ...]; table [hist, B, ...]; row, prev_row:
+    int32 [B] device tensors (problem b replaces table[row[b], b]; its previous step wrote table[prev_row[b], b]); lr: a scalar, or
+    a float64 [B] device tensor."""
+    require_gpu()
+    B, hist = z.shape[0], table.shape[0]
+    n = z.numel() // B
+    for t in (g, tsum):
+        assert t.dtype == z.dtype and t.numel() == z.numel()
+    assert table.dtype == z.dtype and table.numel() == hist * z.numel() and table.shape[1] == B
+    for t in (row, prev_row):
+        assert t.dtype == torch.int32 and tuple(t.shape) == (B,)
+    lr = _pp(lr, B)
+    N.call('pnp_saga_table_update_pp', _p(z), _p(g), _p(table), _p(row), _p(prev_row), _p(tsum), lr[0], _p(lr[1]), float(inv_hist),
+           int(hist), int(B), int(n), _DT[z.dtype], _stream())
 
 
 def pr_spectral_apply(A, v, y, scale=1.0, workspace=None, out=None):

@@ -87,7 +87,7 @@ class NLMProx:
     """denoisers/NLM.py:22-27 semantics for the engines: h = sigma = estimate_sigma * sigma_modifier when
     `self.sigma > 0` (the attribute the reference reads; default 1.0 here), else the decaying fixed strength.
     NLM cannot run in place: the prox ping-pongs between the engine's iterate and a buffer of its own and RETURNS the
-    tensor that holds the result."""
+    tensor that holds the result.  sigma_modifier: a scalar, or [B] values (per problem: pnp_nlm2d_pp)."""
 
     inplace = False                                             # ping-pongs: a hipGraph of an outer iteration cannot hold it
 
@@ -98,6 +98,11 @@ class NLMProx:
     def bind(self, batch):
         self.sig = torch.empty(batch.B, dtype=batch.dtype, device=batch.xrec.device)
         self.buf = torch.empty_like(batch.xinit)
+        if not isinstance(self.sigma_modifier, torch.Tensor) and np.ndim(self.sigma_modifier) != 0:
+            sm = np.ascontiguousarray(self.sigma_modifier, np.float64)      # per problem: a float64 [B] device vector, uploaded once
+            if sm.shape != (batch.B,):
+                raise ValueError(f'per-problem sigma_modifier: {batch.B} values, got shape {sm.shape}')
+            self.sigma_modifier = torch.from_numpy(sm).to(batch.xrec.device)
 
     def __call__(self, z, xrec, sse_out):
         self.t += 1

@@ -153,7 +153,7 @@ def make_prox(denoiser, **kw):
 def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta, n_inner, mini_batch_size=None, T2=None,
                 hist_size=50, H=256, W=256, dtype=torch.float32, max_batch=128, seeding='generator', variant='svrg', run_seed=1,
                 keep_trace=False, graph=True, kernel='Minimal', lr_decay=1.0, denoiser_kwargs=None, sigma_modifier=None,
-                shared_matrix=False):
+                shared_matrix=False, wide_trials=False):
     """Runner for `run_sweep` / `grid_search` over any cell of the reference's sweep (script_diff_sampratio_set12.py:23-25,
     41-51, 64-131): problem in {'csmri', 'deblur', 'pr'} x algorithm in {'gd', 'sgd', 'svrg', 'saga', 'sarah'} x denoiser in
     {'tv', 'nlm', factory}; `n_inner` inner iterations (prox evaluations of the stepped iterate) per item, hyper-parameters
@@ -180,6 +180,10 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
     shared_matrix: problem='pr' only (ValueError otherwise): a trial-batched grid runs its trials on `PrBatch.tile`, every trial of
     an item on that item's ONE matrix A (nothing of A is copied; csrc/pr_shared.hip streams it twice per gradient whatever the
     number of trials).  Without it `check_trials` refuses 'pr'.  `run(items)` itself is unchanged by it.
+    wide_trials: opt in to the wider ground of a trial-batched grid: problem='deblur' (on `DeblurBatch.tile`, seeding
+    'counter' or 'generator'), algorithm='saga' on csmri or deblur (one pnp_saga_table_update_pp launch per step; `run_trials` caps a
+    slab so that its gradient table stays within max_table_bytes) and denoiser='nlm' with sigma_modifier as a per-problem key.
+    Without it `check_trials` answers as it always has.  `run(items)` itself is unchanged by it.
     Beside `run(items)` the runner offers the pieces of a trial-batched grid (`grid_search(batch_trials=True)`):
     `run.prepare_data(items)` builds a rank's batches WITHOUT engines, `run.run_trials(data, trials, max_batch_trials)` runs a list
     of trials ({'eta', 'mini_batch_size', 'sigma_modifier'} overrides) on them as tiled batches, `run.data_key` says which runners
@@ -368,12 +372,17 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
         if problem == 'pr' and not shared_matrix:
             raise ValueError(f"batch_trials: problem {problem!r} is not supported (only 'csmri') unless its trials share the "
                              'matrix: pass shared_matrix=True to make_runner')
-        if problem not in ('csmri', 'pr'):
-            raise ValueError(f"batch_trials: problem {problem!r} is not supported (only 'csmri', and 'pr' with shared_matrix=True)")
-        if algorithm not in ('gd', 'sgd', 'svrg'):
-            raise ValueError(f"batch_trials: algorithm {algorithm!r} is not supported (only 'gd', 'sgd', 'svrg')")
-        if denoiser == 'nlm':
-            raise ValueError("batch_trials: denoiser 'nlm' is not supported (NLMProx has no per-problem form)")
+        if wide_trials:                                         # + deblur, saga (csmri, deblur), nlm
+            if algorithm == 'sarah' or (algorithm == 'saga' and problem == 'pr'):
+                raise ValueError(f"batch_trials: algorithm {algorithm!r} is not supported on problem {problem!r} (wide_trials: 'gd', "
+                                 "'sgd', 'svrg', and 'saga' on 'csmri' or 'deblur'; SarahEngine has no per-problem form)")
+        else:
+            if problem not in ('csmri', 'pr'):
+                raise ValueError(f"batch_trials: problem {problem!r} is not supported (only 'csmri', and 'pr' with shared_matrix=True)")
+            if algorithm not in ('gd', 'sgd', 'svrg'):
+                raise ValueError(f"batch_trials: algorithm {algorithm!r} is not supported (only 'gd', 'sgd', 'svrg')")
+            if denoiser == 'nlm':
+                raise ValueError("batch_trials: denoiser 'nlm' is not supported (NLMProx has no per-problem form)")
         if seeding == 'legacy':
             raise ValueError("batch_trials: seeding 'legacy' is not supported (host index lists; use 'counter' or 'generator')")
         for tr in trials:
@@ -386,14 +395,18 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
         """This rank's batches as `prepare` chunks them (the same groups, order and max_batch), data only."""
         return [_Chunk(c, with_engine=False) for c in _group_chunks(items)]
 
-    def run_trials(data, trials, max_batch_trials=1024):
+    def run_trials(data, trials, max_batch_trials=1024, max_table_bytes=MAX_TABLE_BYTES):
         """trials: dicts of per-problem overrides -> [results of run(items) per trial], on `data` = prepare_data(items): every
-        chunk runs its trials in slabs of at most max_batch_trials problems (at least one trial)."""
+        chunk runs its trials in slabs of at most max_batch_trials problems (at least one trial); a pnp_saga slab also keeps its
+        gradient table (hist_size * problems * H * W elements) within max_table_bytes, again with at least one trial."""
         check_trials(trials)
         out = [[] for _ in trials]
         for base in data:
             n = len(base.items)
-            for t0, t1 in trial_slabs(len(trials), n, max_batch_trials):
+            cap = None
+            if algorithm == 'saga':
+                cap = table_trial_cap(n, hist_size, H * W, torch.empty((), dtype=dtype).element_size(), max_table_bytes)
+            for t0, t1 in trial_slabs(len(trials), n, max_batch_trials, cap):
                 slab = _TrialSlab(base, trials[t0:t1])
                 slab.advance(n_inner)
                 for j, r in enumerate(slab.results()):
@@ -483,9 +496,22 @@ def group_trials(trials):
     return [(dict(key), idx) for key, idx in groups.items()]
 
 
-def trial_slabs(n_trials, n_items, max_batch_trials):
-    """[t0, t1) trial ranges of the slabs: as many whole trials as fit into max_batch_trials problems, at least one."""
+MAX_TABLE_BYTES = 8 * 2 ** 30                                   # default bound on the SAGA gradient table of one trial slab
+
+
+def table_trial_cap(n_items, hist_size, n_elems, itemsize, max_table_bytes=MAX_TABLE_BYTES):
+    """Trials per slab that keep a SAGA gradient table -- hist_size * (trials * n_items) * n_elems elements of itemsize bytes --
+    within max_table_bytes; never below one trial (a single trial's table is what the per-trial runner allocates anyway)."""
+    per_trial = int(hist_size) * max(1, int(n_items)) * int(n_elems) * int(itemsize)
+    return max(1, int(max_table_bytes) // per_trial)
+
+
+def trial_slabs(n_trials, n_items, max_batch_trials, max_trials=None):
+    """[t0, t1) trial ranges of the slabs: as many whole trials as fit into max_batch_trials problems -- and, when given, at most
+    max_trials of them (table_trial_cap) -- at least one."""
     per = max(1, int(max_batch_trials) // max(1, int(n_items)))
+    if max_trials is not None:
+        per = max(1, min(per, int(max_trials)))
     return [(t0, min(t0 + per, n_trials)) for t0 in range(0, n_trials, per)]
 
 
@@ -503,7 +529,7 @@ def trial_layout(n_items, trials, defaults):
     return lay
 
 
-def grid_search(items, make_runner, grid, group=None, *, batch_trials=False, max_batch_trials=1024):
+def grid_search(items, make_runner, grid, group=None, *, batch_trials=False, max_batch_trials=1024, max_table_bytes=MAX_TABLE_BYTES):
     """The sweep the reference scripts run (process_img, script_diff_sampratio_set12.py:103-131): for every work item
     search the hyper-parameters and keep the best trial.  `make_runner(**params)` returns a runner as `run_sweep`
     takes; each rank runs every trial on ITS shard of the items (one batched engine per trial), the reduction over
@@ -513,6 +539,8 @@ def grid_search(items, make_runner, grid, group=None, *, batch_trials=False, max
     ONE batch per chunk instead of one after the other.  Keys 'eta', 'mini_batch_size', 'sigma_modifier' become
     per-problem vectors; trials are grouped by every other key (T2 included), the problem data of a chunk is prepared once and
     shared by all groups, and a group runs on the chunk tiled once per trial in slabs of at most max_batch_trials problems.
+    Runners made with wide_trials=True also take Deblur, pnp_saga (csmri, deblur) and the NLM prox; a pnp_saga slab is
+    capped so that its gradient table stays within max_table_bytes (never below one trial).
     The rows returned are those of batch_trials=False."""
     if dist.is_available() and dist.is_initialized():
         rank, world = dist.get_rank(group), dist.get_world_size(group)
@@ -531,7 +559,7 @@ def grid_search(items, make_runner, grid, group=None, *, batch_trials=False, max
             run.check_trials(sub)
             if run.data_key not in data:
                 data[run.data_key] = run.prepare_data(mine)
-            for t, res in zip(idx, run.run_trials(data[run.data_key], sub, max_batch_trials)):
+            for t, res in zip(idx, run.run_trials(data[run.data_key], sub, max_batch_trials, max_table_bytes)):
                 per_trial[t] = (trials[t], [{k: v for k, v in r.items() if k != 'z'} for r in res])
     else:
         for params in trials:
