@@ -497,6 +497,16 @@ int pnp_saga_table_update_pp(void* z, const void* g, void* table, const int32_t*
  * Covers z -= lr*v (pnp_gd.py:35), SAGA/SARAH combines (pnp_saga.py:47, pnp_sarah.py:72). */
 int pnp_axpbypcz(double a, const void* x, double b, const void* y, double c, const void* w,
                  void* out, size_t n, int dtype, void* stream);
+/* The same combine with per-problem coefficients (_pp form), ONE launch for a batch: n = total element count, problem p owns the
+ * elements [p * n / batch, (p + 1) * n / batch) and takes a_pp ? a_pp[p] : a (likewise b, c): [batch] doubles on the device, each
+ * cast to `dtype` once, as the plain call casts its scalar.  All three arrays NULL is the plain call.  Per element the arithmetic
+ * and its order are those of pnp_axpbypcz (y, w may be NULL), so problem p equals, bit for bit, the plain call on its views.
+ * 16 bytes per lane when x, y, w, out are 16-byte aligned and n / batch elements are a multiple of 16 bytes; any other views
+ * (offset by one element, odd lengths) take an element-by-element path.  out may alias x, y or w EXACTLY (every thread loads all
+ * operands of its elements before it stores them); partially overlapping operands are not supported.
+ * PNP_ERR_ARG before any device work: NULL x or out, batch <= 0, n % batch != 0, an unknown dtype.                     */
+int pnp_axpbypcz_pp(double a, const double* a_pp, const void* x, double b, const double* b_pp, const void* y,
+                    double c, const double* c_pp, const void* w, void* out, size_t n, int batch, int dtype, void* stream);
 
 /* ------------------------------------------------------------------ host: the legacy RNG draw of select_mb
  * np.random.choice(pool, size, replace=False) (problems/CSMRI.py:72, problems/problem.py:114) on the legacy MT19937 stream,

@@ -118,16 +118,11 @@ class _BatchBase:
         return self._tmp
 
     def _combine(self, g, out, beta, c1, gamma=0.0, c2=None):
-        """g + beta * c1 + gamma * c2 -> out.  With nothing to add, a gradient that was written to `out` is the result as it is.
-        pnp_axpbypcz has scalar coefficients: a per-problem gamma (float64 [B] device tensor) takes one launch per problem on that
-        problem's views, each the scalar call with its value."""
+        """g + beta * c1 + gamma * c2 -> out, ONE launch.  With nothing to add, a gradient that was written to `out` is the result
+        as it is.  A per-problem gamma (float64 [B] device tensor) goes to pnp_axpbypcz_pp as it is: per problem the scalar call
+        with its value, bit for bit."""
         if c1 is None and c2 is None:
             return g if g is out else out.copy_(g)
-        if isinstance(gamma, torch.Tensor):
-            gam = self._host(gamma)
-            for i in range(self.B):
-                ops.axpbypcz(1.0, g[i], beta, None if c1 is None else c1[i], float(gam[i]), c2[i], out=out[i])
-            return out
         return ops.axpbypcz(1.0, g, beta, c1, gamma, c2, out=out)
 
     def _host(self, t, fn=None):

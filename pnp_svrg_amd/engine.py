@@ -19,7 +19,11 @@ A batch says whether it takes them with its `per_problem` attribute: a CsmriBatc
 on the B matrices of the batch it was tiled from (the non-fused paths only; csrc/pr_shared.hip).
 A DeblurBatch takes them too (`DeblurBatch.tile(n)`: one plan for n * B problems on the same kernel spectrum), NLMProx takes a [B]
 `sigma_modifier`, and SagaEngine takes `eta`, `mini_batch_size` and `draw_id` per problem: a step is then ONE
-`pnp_saga_table_update_pp` launch, as it is when every problem replaces a row of its own.  SarahEngine stays scalar.
+`pnp_saga_table_update_pp` launch, as it is when every problem replaces a row of its own.
+SarahEngine takes `eta`, `mini_batch_size` and `draw_id` per problem as well: its two elementwise steps are one
+`pnp_axpbypcz_pp` launch each (`ops.axpbypcz` with a [B] coefficient), its difference of minibatch gradients takes 1 / mb per problem.
+The same launch carries every per-problem combine `g + beta * c1 + gamma * c2` of the Deblur and PR batches and the step of
+SvrgEngine(variant='reference').
 """
 import numpy as np
 import torch
@@ -223,17 +227,13 @@ class SvrgEngine(_StochEngine):
             self.b.grad_stoch_diff(self.z, self.w, self.mbs, j, out=self.z, alpha=self._c('-lr/mb', k, -lr / self.mb), beta=1.0,
                                    c1=self.z, gamma=self._c('-lr', k, -lr), c2=self.mu)
         else:
-            self._step_along_mu(lr)
+            self._step_along_mu(lr, k)
         return self.prox(self.z, self.b.xrec, sse_out)
 
-    def _step_along_mu(self, lr):
-        """variant='reference': z <- z - lr * mu.  pnp_axpbypcz has scalar coefficients: per-problem step sizes take one launch
-        per problem (this variant documents what v1 executes; it is not a throughput path)."""
-        if np.ndim(lr) == 0:
-            ops.axpbypcz(1.0, self.z, -lr, self.mu, out=self.z)
-        else:
-            for i in range(self.b.B):
-                ops.axpbypcz(1.0, self.z[i], -float(lr[i]), self.mu[i], out=self.z[i])
+    def _step_along_mu(self, lr, k):
+        """variant='reference': z <- z - lr * mu, one launch: per-problem step sizes go in as the uploaded -lr vector
+        (pnp_axpbypcz_pp), a scalar as itself (pnp_axpbypcz)."""
+        ops.axpbypcz(1.0, self.z, self._c('-lr', k, -lr), self.mu, out=self.z)
 
     def _fused_outer(self, lr, sse_out, k):
         """outer refresh (mu = grad_full(z), w = z) + inner iteration 0 in one kernel (pnp_csmri_svrg_outer_step)."""
@@ -354,12 +354,11 @@ class SvrgEngine(_StochEngine):
 class SarahEngine(_StochEngine):
     """pnp_sarah over a batch (algorithms/pnp_sarah.py:28-104) with the quirks of v1: the outer step
     `w_next = prox(w_prev - eta * grad_full(z))` is logged but never adopted by z, w_next stays fixed through the
-    inner loop, and the outer step ignores lr_decay.  One log row per prox: outer rows at s % T2 == 0."""
+    inner loop, and the outer step ignores lr_decay.  One log row per prox: outer rows at s % T2 == 0.
+    eta, mini_batch_size: scalars, or [B] arrays on a batch that takes them per problem; draw_id as in SgdEngine."""
 
-    def __init__(self, batch, prox, eta, T2, mini_batch_size, lr_decay=1.0, n_log=4096, seed=0):
-        if np.ndim(eta) != 0 or np.ndim(mini_batch_size) != 0:
-            raise ValueError('SarahEngine takes a scalar eta and mini_batch_size (pnp_axpbypcz has no per-problem form)')
-        super().__init__(batch, prox, eta, mini_batch_size, lr_decay, n_log, seed)
+    def __init__(self, batch, prox, eta, T2, mini_batch_size, lr_decay=1.0, n_log=4096, seed=0, draw_id=None):
+        super().__init__(batch, prox, eta, mini_batch_size, lr_decay, n_log, seed, draw_id=draw_id)
         self.T2 = T2
         self.w_prev = torch.empty_like(self.z)
         self.w_next = torch.empty_like(self.z)
@@ -371,12 +370,15 @@ class SarahEngine(_StochEngine):
         if s % self.T2 == 0:
             self.w_prev.copy_(self.z)
             b.grad_full(self.z, out=self.v_prev)
-            ops.axpbypcz(1.0, self.w_prev, -self.eta, self.v_prev, out=self.w_next)
+            # (F6: no lr_decay here -- '-eta' is a coefficient of its own, made once whatever the decay exponent)
+            ops.axpbypcz(1.0, self.w_prev, self._c('-eta', 0, -self.eta), self.v_prev, out=self.w_next)
             self.w_next = self._prox(self.w_next)
         j = self._minibatch(idx_s, s)
-        b.grad_stoch_diff(self.w_next, self.w_prev, self.mbs, j, out=self.v_next, alpha=1.0 / self.mb, beta=1.0, c1=self.v_prev)
-        lr = self.eta * self.lr_decay ** (s // self.T2)
-        ops.axpbypcz(1.0, self.z, -lr, self.v_next, out=self.z)
+        b.grad_stoch_diff(self.w_next, self.w_prev, self.mbs, j, out=self.v_next, alpha=self._c('1/mb', 0, 1.0 / self.mb), beta=1.0,
+                          c1=self.v_prev)
+        k = s // self.T2
+        lr = self.eta * self.lr_decay ** k
+        ops.axpbypcz(1.0, self.z, self._c('-lr', k, -lr), self.v_next, out=self.z)
         self.z = self._prox(self.z)
         self.v_prev, self.v_next = self.v_next, self.v_prev
         self.w_prev.copy_(self.z)

@@ -39,9 +39,11 @@ def _pp(v, B, dtype=torch.float64):
     return _PP(((int(v) if dtype == torch.int32 else float(v)), None))
 
 
-def _route(name, args, ptr=_p):
+def _route(name, args, ptr=None):
     """Call entry point `name` with `args`, the `_pp()` values among them as their scalars -- exactly the plain call -- unless one
-    of them holds a per-problem array: then `name_pp`, where every `_pp()` value is a (scalar, array pointer or None) pair."""
+    of them holds a per-problem array: then `name_pp`, where every `_pp()` value is a (scalar, array pointer or None) pair.
+    ptr: what turns an array into the pointer argument (default: `_p`)."""
+    ptr = ptr or _p
     if any(type(a) is _PP and a[1] is not None for a in args):
         flat = []
         for a in args:
@@ -400,9 +402,16 @@ def minmax(z):
 
 
 def axpbypcz(a, x, b=0.0, y=None, c=0.0, w=None, out=None):
+    """out = a * x + b * y + c * w (y, w may be None; out may be x, y or w).  a, b, c: scalars -- the plain pnp_axpbypcz call -- or
+    float64 [B] device tensors with B = x.shape[0]: problem p = x[p] takes its own value, ONE pnp_axpbypcz_pp launch, bit for bit
+    the plain call on p's views with float(coef[p])."""
     require_gpu()
     out = out if out is not None else torch.empty_like(x)
-    N.call('pnp_axpbypcz', float(a), _p(x), float(b), _p(y), float(c), _p(w), _p(out), x.numel(), _DT[x.dtype], _stream())
+    B = x.shape[0] if x.dim() else 1
+    args = [_pp(a, B), _p(x), _pp(b, B), _p(y), _pp(c, B), _p(w), _p(out), x.numel(), _DT[x.dtype], _stream()]
+    if any(v[1] is not None for v in args[0:5:2]):              # the `_pp` call alone takes the number of problems, behind n
+        args.insert(8, int(B))
+    _route('pnp_axpbypcz', args)
     return out
 
 

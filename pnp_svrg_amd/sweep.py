@@ -153,7 +153,7 @@ def make_prox(denoiser, **kw):
 def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta, n_inner, mini_batch_size=None, T2=None,
                 hist_size=50, H=256, W=256, dtype=torch.float32, max_batch=128, seeding='generator', variant='svrg', run_seed=1,
                 keep_trace=False, graph=True, kernel='Minimal', lr_decay=1.0, denoiser_kwargs=None, sigma_modifier=None,
-                shared_matrix=False, wide_trials=False):
+                shared_matrix=False, wide_trials=False, sarah_trials=False):
     """Runner for `run_sweep` / `grid_search` over any cell of the reference's sweep (script_diff_sampratio_set12.py:23-25,
     41-51, 64-131): problem in {'csmri', 'deblur', 'pr'} x algorithm in {'gd', 'sgd', 'svrg', 'saga', 'sarah'} x denoiser in
     {'tv', 'nlm', factory}; `n_inner` inner iterations (prox evaluations of the stepped iterate) per item, hyper-parameters
@@ -184,6 +184,10 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
     'counter' or 'generator'), algorithm='saga' on csmri or deblur (one pnp_saga_table_update_pp launch per step; `run_trials` caps a
     slab so that its gradient table stays within max_table_bytes) and denoiser='nlm' with sigma_modifier as a per-problem key.
     Without it `check_trials` answers as it always has.  `run(items)` itself is unchanged by it.
+    sarah_trials: opt in to algorithm='sarah' in a trial-batched grid (SarahEngine with per-problem eta, mini_batch_size and
+    draw_id, its elementwise steps one pnp_axpbypcz_pp launch each) on 'csmri', on 'deblur' with wide_trials=True and on 'pr' with
+    shared_matrix=True; per-problem keys eta, mini_batch_size, sigma_modifier (T2 stays structural).  Without it `check_trials`
+    refuses 'sarah' as it always has.  `run(items)` itself is unchanged by it.
     Beside `run(items)` the runner offers the pieces of a trial-batched grid (`grid_search(batch_trials=True)`):
     `run.prepare_data(items)` builds a rank's batches WITHOUT engines, `run.run_trials(data, trials, max_batch_trials)` runs a list
     of trials ({'eta', 'mini_batch_size', 'sigma_modifier'} overrides) on them as tiled batches, `run.data_key` says which runners
@@ -373,13 +377,13 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
             raise ValueError(f"batch_trials: problem {problem!r} is not supported (only 'csmri') unless its trials share the "
                              'matrix: pass shared_matrix=True to make_runner')
         if wide_trials:                                         # + deblur, saga (csmri, deblur), nlm
-            if algorithm == 'sarah' or (algorithm == 'saga' and problem == 'pr'):
+            if (algorithm == 'sarah' and not sarah_trials) or (algorithm == 'saga' and problem == 'pr'):
                 raise ValueError(f"batch_trials: algorithm {algorithm!r} is not supported on problem {problem!r} (wide_trials: 'gd', "
                                  "'sgd', 'svrg', and 'saga' on 'csmri' or 'deblur'; SarahEngine has no per-problem form)")
         else:
             if problem not in ('csmri', 'pr'):
                 raise ValueError(f"batch_trials: problem {problem!r} is not supported (only 'csmri', and 'pr' with shared_matrix=True)")
-            if algorithm not in ('gd', 'sgd', 'svrg'):
+            if algorithm not in ('gd', 'sgd', 'svrg') and not (sarah_trials and algorithm == 'sarah'):
                 raise ValueError(f"batch_trials: algorithm {algorithm!r} is not supported (only 'gd', 'sgd', 'svrg')")
             if denoiser == 'nlm':
                 raise ValueError("batch_trials: denoiser 'nlm' is not supported (NLMProx has no per-problem form)")
@@ -540,7 +544,8 @@ def grid_search(items, make_runner, grid, group=None, *, batch_trials=False, max
     per-problem vectors; trials are grouped by every other key (T2 included), the problem data of a chunk is prepared once and
     shared by all groups, and a group runs on the chunk tiled once per trial in slabs of at most max_batch_trials problems.
     Runners made with wide_trials=True also take Deblur, pnp_saga (csmri, deblur) and the NLM prox; a pnp_saga slab is
-    capped so that its gradient table stays within max_table_bytes (never below one trial).
+    capped so that its gradient table stays within max_table_bytes (never below one trial).  Runners made with sarah_trials=True
+    also take pnp_sarah on csmri, on deblur with wide_trials=True and on pr with shared_matrix=True.
     The rows returned are those of batch_trials=False."""
     if dist.is_available() and dist.is_initialized():
         rank, world = dist.get_rank(group), dist.get_world_size(group)

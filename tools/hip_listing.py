@@ -20,7 +20,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # the per-file flags of csrc/Makefile that bear on device code
 W44_FLAGS = ['-mllvm', '-pragma-unroll-threshold=200000', '-fno-slp-vectorize']
 FILE_FLAGS = {'dncnn_wino44.hip': W44_FLAGS, 'dncnn_wino44b.hip': W44_FLAGS, 'prox.hip': ['-ffp-contract=off'],
-              'prox_wavelet2d.hip': ['-ffp-contract=off'], 'nlm.hip': ['-ffp-contract=off']}
+              'prox_wavelet2d.hip': ['-ffp-contract=off'], 'nlm.hip': ['-ffp-contract=off'], 'axpbypcz_pp.hip': ['-ffp-contract=off']}
 
 
 def listing(name, defines=(), root=ROOT):
