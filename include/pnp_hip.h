@@ -364,7 +364,8 @@ int pnp_prox_wavelet2d(const void* z_in, void* z_out, int H, int W, int batch, i
 
 /* NLMDenoiser.denoise (denoisers/NLM.py:22-27 -> skimage 0.18 _nl_means_denoising_2d, slow mode,
  * Schraudolph fast_exp).  patch_size as the caller passes it (even sizes are bumped to the
- * next odd one like skimage: 4 -> 5; supported sides 3/5/7), patch_distance in [1, 8].
+ * next odd one like skimage: 4 -> 5; supported sides 3/5/7), patch_distance in [1, 8].  H and W must be
+ * at least side/2 + 1 (2, 3, 4): the border is reflected once, as np.pad(mode='reflect') does down to there.
  *   sigma_in != NULL : h = sigma = sigma_in[b]*sigma_modifier, var = 2 sigma^2   (NLM.py:25)
  *   sigma_in == NULL : h = fixed_h, var = 0                                     (NLM.py:27)
  *   w0 [side*side] (device, double) = exp(-(x^2+y^2)/(2A^2)), A = (side-1)/4, and w0_sum = its sum as

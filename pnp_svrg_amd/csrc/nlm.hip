@@ -299,6 +299,9 @@ static int nlm2d(const void* z_in, void* z_out, int H, int W, int batch, int dty
     const int s = patch_size % 2 == 0 ? patch_size + 1 : patch_size;          // skimage bumps even sizes
     PNP_CHECK_ARG(s == 3 || s == 5 || s == 7, "patch side must be 3, 5 or 7 (after the even->odd bump)");
     PNP_CHECK_ARG(patch_distance >= 1 && patch_distance <= 8, "patch_distance must be in [1, 8]");
+    // reflect_idx reflects once: np.pad(mode='reflect') only while the image is at least s/2 + 1 pixels each way
+    PNP_CHECK_ARG(H >= s / 2 + 1 && W >= s / 2 + 1, "H and W must be at least " + std::to_string(s / 2 + 1) + " for patch side " +
+                                                        std::to_string(s) + " (patch side / 2 + 1: the border is reflected once)");
     PNP_CHECK_ARG(!(sse_out && !(xrec && sse_workspace)), "sse_out needs xrec and a workspace");
     PNP_CHECK_ARG(dtype == PNP_F32 || dtype == PNP_F64, "bad dtype");
     hipStream_t st = (hipStream_t)stream;

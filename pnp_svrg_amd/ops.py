@@ -435,9 +435,11 @@ def _nlm_w0(side, device):
 def nlm2d(z, sigma_in=None, sigma_modifier=1.0, fixed_h=0.0, patch_size=4, patch_distance=5, xrec=None, out=None, sse=None):
     """skimage denoise_nl_means(slow mode) semantics on [B,H,W]; returns (denoised, sse or None).
     sigma_modifier: a scalar, or a float64 [B] device tensor (per image: pnp_nlm2d_pp)."""
-    require_gpu()
     B, H, W = z.shape
     side = patch_size + 1 if patch_size % 2 == 0 else patch_size
+    if min(H, W) < side // 2 + 1:                               # nlm2d() in nlm.hip refuses it too: the border is reflected once
+        raise N.NativeError(f'pnp_nlm2d: H and W must be at least {side // 2 + 1} for patch side {side} (got {H} x {W})')
+    require_gpu()
     w0, w0_sum = _nlm_w0(side, z.device)
     out = out if out is not None else torch.empty_like(z)
     ws = None
