@@ -213,6 +213,24 @@ int pnp_csmri_svrg_outer_iteration_pp(pnp_csmri_plan* plan, void* z, void* w, vo
                                       int mini_batch_size, const int32_t* mb_vec, double sigma_modifier,
                                       const double* sigma_modifier_pp, double fallback_sigma, const void* xrec, double* sse_log,
                                       int log_row0, int n_log, void* sigma_out, void* stream);
+/* Per-problem T2: n_steps consecutive inner iterations s = step0 .. step0 + n_steps - 1 of every problem in ONE launch, with the TV
+ * prox.  Problem b refreshes (mu = grad_full(z), w = z) at the steps with s % T2_b == 0, T2_b = t2_vec ? t2_vec[b] : T2 -- at its own
+ * outer iterations, wherever the span starts or ends inside them (a problem with step0 % T2_b != 0 does not refresh at the span
+ * start).  At a refresh step the workgroup that owns b runs pnp_csmri_svrg_outer_step on it, at every other step
+ * pnp_csmri_svrg_step (a = z, b = w, c1 = z, c2 = mu, alpha = -lr / mini_batch_size, beta = 1, gamma = -lr, out = z), back to back;
+ * the results are bit for bit those of the separate calls.  lr_pp, mb_vec, sigma_modifier_pp: as pnp_csmri_svrg_outer_iteration_pp.
+ *   t2_vec   int32 [batch], nullable.  The call does not synchronise, so it cannot read t2_vec: entries must be >= 1 (the Python
+ *            front end checks its host copy and raises; an entry below 1 that reaches the kernel counts as 1);
+ *   selbits  [n_steps][batch][W][H/32]: slot i = the selector of step step0 + i (drawn with the absolute step id, so a problem
+ *            sees the minibatch a scalar-T2 run gives it at that step); the slot of a refresh step is not read;
+ *   sse_log  [n_log][batch] double: step s writes row (log_row0 + s - step0) % n_log.
+ * PNP_ERR_ARG before any device work: a NULL pointer (t2_vec and the _pp arrays excepted), n_steps <= 0, step0 < 0, T2 <= 0 with a
+ * NULL t2_vec, mini_batch_size <= 0 with a NULL mb_vec, a plan that is not f32 256 x 256, z, w, mu not three buffers.        */
+int pnp_csmri_svrg_span_pp(pnp_csmri_plan* plan, void* z, void* w, void* mu, const uint32_t* mask_bitsT, const void* yh,
+                           const void* alpha_vec, const uint32_t* selbits, int step0, int n_steps, int T2, const int32_t* t2_vec,
+                           double lr, const double* lr_pp, int mini_batch_size, const int32_t* mb_vec, double sigma_modifier,
+                           const double* sigma_modifier_pp, double fallback_sigma, const void* xrec, double* sse_log,
+                           int log_row0, int n_log, void* sigma_out, void* stream);
 /* pnp_prox_tv / pnp_prox_wavelet2d with sigma used = sigma_est * (sigma_modifier_pp ? sigma_modifier_pp[b] : sigma_modifier). */
 int pnp_prox_tv_pp(const void* z_in, void* z_out, int H, int W, int batch, int dtype, const void* sigma_in,
                    double sigma_modifier, const double* sigma_modifier_pp, double fallback_sigma, const void* xrec,
@@ -508,6 +526,16 @@ int pnp_axpbypcz(double a, const void* x, double b, const void* y, double c, con
  * PNP_ERR_ARG before any device work: NULL x or out, batch <= 0, n % batch != 0, an unknown dtype.                     */
 int pnp_axpbypcz_pp(double a, const double* a_pp, const void* x, double b, const double* b_pp, const void* y,
                     double c, const double* c_pp, const void* w, void* out, size_t n, int batch, int dtype, void* stream);
+
+/* The outer refresh of the SVRG loop -- algorithms/pnp_svrg.py:32-38 -- where every problem has a T2 of its own, ONE launch for a batch of
+ * any kind: for every problem p with step % t2_vec[p] == 0:  mu[p] = mu_new[p], w[p] = z[p]; the other problems' mu and w are
+ * neither written nor read.  n = total element count, problem p owns [p * n / batch, (p + 1) * n / batch); t2_vec: int32 [batch]
+ * on the device (entries >= 1: the front end checks its host copy; an entry below 1 counts as 1); step: the host's step index.
+ * 16 bytes per lane when the four arrays are 16-byte aligned and n / batch elements are a multiple of 16 bytes, else element by
+ * element.  PNP_ERR_ARG before any device work: a NULL pointer, batch <= 0, n % batch != 0, an unknown dtype, step < 0, mu_new
+ * aliasing mu (or w aliasing any of the other three, or z aliasing mu).                                                    */
+int pnp_refresh_pp(const void* mu_new, const void* z, void* mu, void* w, const int32_t* t2_vec, int step, size_t n, int batch,
+                   int dtype, void* stream);
 
 /* ------------------------------------------------------------------ host: the legacy RNG draw of select_mb
  * np.random.choice(pool, size, replace=False) (problems/CSMRI.py:72, problems/problem.py:114) on the legacy MT19937 stream,

@@ -94,6 +94,10 @@ SIGNATURES = {
     'pnp_nlm2d_pp': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _d, _vp, _d, _vp, _d, _vp, _vp, _vp, _vp]),
     'pnp_saga_table_update_pp': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _d, _vp, _d, _i, _i, _i, _i, _vp]),
     'pnp_axpbypcz_pp': (_i, [_d, _vp, _vp, _d, _vp, _vp, _d, _vp, _vp, _vp, _sz, _i, _i, _vp]),
+    # per-problem T2: a span of inner iterations in one launch, and the refresh of the streaming paths
+    'pnp_csmri_svrg_span_pp': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _d, _vp, _i, _vp, _d, _vp, _d, _vp, _vp, _i,
+                                    _i, _vp, _vp]),
+    'pnp_refresh_pp': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _sz, _i, _i, _vp]),
     'pnp_legacy_choice': (_i, [_vp, ctypes.POINTER(ctypes.c_int), _vp, _i, _i, _vp, _vp]),
 }
 

@@ -337,6 +337,11 @@ int csmri_fused_outer_launch(int batch, const void* twtab, void* z, void* w, voi
                              double sigma_modifier, double fallback_sigma, const void* xrec, double* sse_log, int log_row0, int n_log,
                              void* sigma_out, void* stream, const double* lr_pp = nullptr, const int32_t* mb_vec = nullptr,
                              const double* sm_pp = nullptr);
+int csmri_fused_span_launch(int batch, const void* twtab, void* z, void* w, void* mu, const uint32_t* mask_bits, const void* yh,
+                            const void* alpha_vec, const uint32_t* selbits, int step0, int n_steps, int T2, const int32_t* t2_vec,
+                            double lr, const double* lr_pp, int mini_batch_size, const int32_t* mb_vec, double sigma_modifier,
+                            const double* sm_pp, double fallback_sigma, const void* xrec, double* sse_log, int log_row0, int n_log,
+                            void* sigma_out, void* stream);
 }
 
 namespace {
@@ -491,4 +496,22 @@ extern "C" int pnp_csmri_svrg_outer_iteration_pp(pnp_csmri_plan* p, void* z, voi
     return csmri_fused_outer_launch(p->batch, p->twtab, z, w, mu, mask_bitsT, yh, alpha_vec, selbits, T2, lr, mini_batch_size,
                                     sigma_modifier, fallback_sigma, xrec, sse_log, log_row0, n_log, sigma_out, stream, lr_pp, mb_vec,
                                     sigma_modifier_pp);
+}
+
+// ---- n_steps inner iterations in one launch, every problem refreshing by its own T2 (t2_vec: int32 [batch]; NULL = the scalar)
+extern "C" int pnp_csmri_svrg_span_pp(pnp_csmri_plan* p, void* z, void* w, void* mu, const uint32_t* mask_bitsT, const void* yh,
+                                      const void* alpha_vec, const uint32_t* selbits, int step0, int n_steps, int T2,
+                                      const int32_t* t2_vec, double lr, const double* lr_pp, int mini_batch_size, const int32_t* mb_vec,
+                                      double sigma_modifier, const double* sigma_modifier_pp, double fallback_sigma, const void* xrec,
+                                      double* sse_log, int log_row0, int n_log, void* sigma_out, void* stream) {
+    PNP_CHECK_ARG(p && z && w && mu && mask_bitsT && yh && alpha_vec && selbits && xrec && sse_log && sigma_out, "null argument");
+    PNP_CHECK_ARG(n_steps >= 1 && step0 >= 0 && step0 <= INT32_MAX - n_steps, "bad step0 / n_steps");
+    PNP_CHECK_ARG(t2_vec != nullptr || T2 >= 1, "bad T2: a scalar T2 >= 1 or a t2_vec");
+    PNP_CHECK_ARG((mb_vec != nullptr || mini_batch_size >= 1) && n_log >= 1 && log_row0 >= 0 && log_row0 <= INT32_MAX - n_steps,
+                  "bad mini_batch_size / log");
+    PNP_CHECK_ARG(p->dtype == PNP_F32 && p->H == 256 && p->W == 256, "the one-kernel iteration exists for f32 plans of 256 x 256");
+    PNP_CHECK_ARG(z != w && z != mu && w != mu, "z, w and mu must be buffers of their own");
+    return csmri_fused_span_launch(p->batch, p->twtab, z, w, mu, mask_bitsT, yh, alpha_vec, selbits, step0, n_steps, T2, t2_vec, lr, lr_pp,
+                                   mini_batch_size, mb_vec, sigma_modifier, sigma_modifier_pp, fallback_sigma, xrec, sse_log, log_row0,
+                                   n_log, sigma_out, stream);
 }

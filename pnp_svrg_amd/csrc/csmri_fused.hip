@@ -874,6 +874,58 @@ __global__ __launch_bounds__(FT) void k_svrg_outer_pp(float* z, float* w, float*
     }
 }
 
+// Per-problem T2 (pnp_csmri_svrg_span_pp): n_steps consecutive inner iterations s = step0 .. step0 + n_steps - 1 of every problem in
+// one launch, where problem b refreshes (mu = grad_full(z), w = z) at the steps with s % T2_b == 0 -- its own outer iterations,
+// wherever the span starts and ends inside them.  T2_b = t2_vec[prob] (int32 [batch]; NULL: the scalar T2; an entry below 1 counts
+// as 1).  One workgroup owns one problem, so "does this step refresh" is wave-uniform: a refresh step runs the folded body of
+// k_svrg_outer's first iteration on mask_bits / yh, every other step its plain body on selbits slot s - step0
+// (selbits: [n_steps][batch][W][H/32]; the slot of a refresh step is not read).  lr_pp, mb_vec, sm_pp and the coefficients:
+// k_svrg_outer_pp's, expression for expression.  sse_log row (log_row0 + s - step0) % n_log.
+__global__ __launch_bounds__(FT) void k_svrg_span_pp(float* z, float* w, float* mu, const uint32_t* __restrict__ mask_bits,
+                                                     const cx<float>* __restrict__ yh, const float* __restrict__ alpha_vec,
+                                                     const uint32_t* __restrict__ selbits, int step0, int n_steps, int T2,
+                                                     const int32_t* __restrict__ t2_vec, double lr, const double* __restrict__ lr_pp,
+                                                     int mini_batch_size, const int32_t* __restrict__ mb_vec,
+                                                     const cx<float>* __restrict__ twtab, float sigma_modifier,
+                                                     const double* __restrict__ sm_pp, float fallback_sigma,
+                                                     const float* __restrict__ xrec, double* __restrict__ sse_log, int log_row0, int n_log,
+                                                     float* __restrict__ sigma_out) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    __shared__ FusedShared sh;
+    const int prob = blockIdx.x;
+    if (lr_pp != nullptr) lr = lr_pp[prob];
+    if (mb_vec != nullptr) mini_batch_size = mb_vec[prob];
+    if (sm_pp != nullptr) sigma_modifier = (float)sm_pp[prob];
+    if (t2_vec != nullptr) T2 = t2_vec[prob];
+    if (T2 < 1) T2 = 1;
+    const double alpha = -lr / (double)mini_batch_size;
+    const float scale_inner = (float)(alpha * (1.0 / ((double)FN * (double)FN))), gamma = (float)(-lr);
+    const int batch = gridDim.x;
+    const size_t img = (size_t)prob * FN * FN;
+    const float inv_n = 1.0f / ((float)FN * (float)FN);
+    float* zi = z + img;
+    int j = step0 % T2;                                         // position of step s inside this problem's outer iteration
+#pragma unroll 1
+    for (int i = 0; i < n_steps; ++i) {
+        if (i > 0) {
+            // this iteration reads what the last one wrote (same lanes, same addresses): stores done, no stale line in the L1
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            __syncthreads();
+        }
+        double* sse_row = sse_log + (size_t)((log_row0 + i) % n_log) * batch + prob;
+        if (j == 0)
+            svrg_iter_body<FUSED_FULL, true, 0>(lds_raw, sh, zi, nullptr, mask_bits + (size_t)prob * FN * 8, yh + (size_t)prob * (FN / 2) * FN,
+                                                twtab, inv_n * alpha_vec[prob], 1.0f, zi, gamma, nullptr, zi, sigma_modifier, fallback_sigma,
+                                                xrec + img, sse_row, sigma_out + prob, w + img, mu + img);
+        else
+            svrg_iter_body<FUSED_FULL, false, 2>(lds_raw, sh, zi, w + img, selbits + ((size_t)i * batch + prob) * FN * 8, nullptr, twtab,
+                                                 scale_inner, 1.0f, zi, gamma, mu + img, zi, sigma_modifier, fallback_sigma, xrec + img,
+                                                 sse_row, sigma_out + prob, nullptr, nullptr);
+        if (++j == T2) j = 0;
+    }
+}
+
 // stagger (see startup_stagger): only launches of more than one workgroup per CU pay for it and profit from it
 static int stagger_config(int* num_cu_out, int* groups, int* units) {
     static int num_cu = 0, st_groups = 2, st_units = 40;    // same-box sweep (tools/dev/stagger_sweep.py): 0.588 ms per config-2 step without, 0.575 with (2, 40), slower from (8, 20) on
@@ -913,6 +965,7 @@ static int fused_lds_optin() {
 #undef PNP_FUSED_ATTR
         PNP_CHECK_HIP(hipFuncSetAttribute((const void*)k_svrg_outer, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F_LDS_BYTES));
         PNP_CHECK_HIP(hipFuncSetAttribute((const void*)k_svrg_outer_pp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F_LDS_BYTES));
+        PNP_CHECK_HIP(hipFuncSetAttribute((const void*)k_svrg_span_pp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F_LDS_BYTES));
         attr_done |= 1ull << (dev & 63);
     }
     return PNP_OK;
@@ -942,6 +995,22 @@ int csmri_fused_outer_launch(int batch, const void* twtab, void* z, void* w, voi
                                                                  (const cx<float>*)twtab, (float)sigma_modifier, (float)fallback_sigma,
                                                                  (const float*)xrec, sse_log, log_row0, n_log, (float*)sigma_out, num_cu,
                                                                  st_groups, 0);     // (no stagger: same-box A/B 0.539 ms per step without, 0.546 with (2, 40))
+    PNP_CHECK_LAUNCH();
+    return PNP_OK;
+}
+
+// one launch = n_steps inner iterations of every problem, refreshes where a problem's own T2 puts them (k_svrg_span_pp)
+int csmri_fused_span_launch(int batch, const void* twtab, void* z, void* w, void* mu, const uint32_t* mask_bits, const void* yh,
+                            const void* alpha_vec, const uint32_t* selbits, int step0, int n_steps, int T2, const int32_t* t2_vec,
+                            double lr, const double* lr_pp, int mini_batch_size, const int32_t* mb_vec, double sigma_modifier,
+                            const double* sm_pp, double fallback_sigma, const void* xrec, double* sse_log, int log_row0, int n_log,
+                            void* sigma_out, void* stream) {
+    { const int rc = fused_lds_optin(); if (rc != PNP_OK) return rc; }
+    k_svrg_span_pp<<<batch, FT, F_LDS_BYTES, (hipStream_t)stream>>>((float*)z, (float*)w, (float*)mu, mask_bits, (const cx<float>*)yh,
+                                                                   (const float*)alpha_vec, selbits, step0, n_steps, T2, t2_vec, lr, lr_pp,
+                                                                   mini_batch_size, mb_vec, (const cx<float>*)twtab, (float)sigma_modifier,
+                                                                   sm_pp, (float)fallback_sigma, (const float*)xrec, sse_log, log_row0,
+                                                                   n_log, (float*)sigma_out);
     PNP_CHECK_LAUNCH();
     return PNP_OK;
 }

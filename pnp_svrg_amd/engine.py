@@ -24,6 +24,10 @@ SarahEngine takes `eta`, `mini_batch_size` and `draw_id` per problem as well (DE
 `pnp_axpbypcz_pp` launch each (`ops.axpbypcz` with a [B] coefficient), its difference of minibatch gradients takes 1 / mb per problem.
 The same launch carries every per-problem combine `g + beta * c1 + gamma * c2` of the Deblur and PR batches and the step of
 SvrgEngine(variant='reference').
+SvrgEngine takes `T2` per problem as well: a [B] integer array makes problem b refresh mu and w at the steps with
+s % T2[b] == 0 -- one `pnp_refresh_pp` launch behind a full gradient at the steps where any problem refreshes -- and `run_span(n)`
+runs n steps in launches of `pnp_csmri_svrg_span_pp` where the one-kernel iteration holds the TV prox.  A scalar T2 takes exactly
+the calls it always took.
 """
 import numpy as np
 import torch
@@ -64,7 +68,7 @@ class LoopEngine:
         made on the host) is uploaded -- once when lr_decay == 1, else whenever the decay exponent k changes."""
         if np.ndim(v) == 0:
             return v
-        key = k if self.lr_decay != 1.0 else 0
+        key = (k if np.ndim(k) == 0 else tuple(k)) if self.lr_decay != 1.0 else 0       # (per-problem T2: one exponent per problem)
         hit = self._coef.get(name)
         if hit is None or hit[0] != key:
             hit = self._coef[name] = (key, torch.from_numpy(np.ascontiguousarray(v, np.float64)).to(self.z.device))
@@ -160,13 +164,39 @@ class SvrgEngine(_StochEngine):
     """pnp_svrg over a batch.  variant='svrg' is the true direction (pnp_svrg.py:53), 'reference' is what v1
     executes (v = mu, :54).  `step()` = one inner iteration (the outer full-gradient refresh happens inside when
     s % T2 == 0, as in the reference's loop nest).  Device draws of a whole outer iteration are ONE launch at the
-    refresh (T2 descriptor slots)."""
+    refresh (T2 descriptor slots).
+    T2: an int, or a [B] integer array on a batch that takes per-problem values: problem b then refreshes at the steps
+    with s % T2[b] == 0 and walks, bit for bit, the trajectory a scalar engine with T2[b] walks.  The draw slots then hold a window
+    of `span` steps (default: AHEAD) drawn with the absolute step ids, `step()` refreshes with a full gradient into a scratch and
+    one pnp_refresh_pp launch (the unfolded refresh, also on the one-kernel path), `run_span(n)` runs n steps in launches of at
+    most `span` steps where `outer_kernel_ok()` holds, and there is no hipGraph form (`graph_ok()` is False, `run_outer` raises)."""
     FUSED_MIN_BATCH = 192
 
     def __init__(self, batch, prox, eta, T2, mini_batch_size, lr_decay=1.0, variant='svrg', n_log=4096, seed=0, fused=None,
-                 fold_outer=True, draw_id=None):
-        super().__init__(batch, prox, eta, mini_batch_size, lr_decay, n_log, seed, n_slots=T2, draw_id=draw_id)
+                 fold_outer=True, draw_id=None, span=None):
+        t2 = None
+        if np.ndim(T2) != 0:                                    # per-problem T2: checked on the host (the kernels cannot)
+            t2 = np.asarray(T2)
+            if not batch.per_problem:
+                raise ValueError(f'per-problem T2 needs a batch that takes per-problem values (got {batch.kind!r})')
+            if t2.shape != (batch.B,) or not np.issubdtype(t2.dtype, np.integer):
+                raise ValueError(f'per-problem T2: {batch.B} integers, got shape {t2.shape} of {t2.dtype}')
+            bad = np.flatnonzero((t2 < 1) | (t2 > np.iinfo(np.int32).max))
+            if bad.size:
+                raise ValueError(f'per-problem T2: entries must be >= 1 (problem {int(bad[0])}: T2 {int(t2[bad[0]])})')
+            T2 = np.ascontiguousarray(t2, np.int64)
+            self.span = int(self.AHEAD if span is None else span)
+            if self.span < 1:
+                raise ValueError(f'span: at least one step per draw window, got {span}')
+        elif span is not None:
+            raise ValueError('span is the draw window of a per-problem T2; a scalar T2 draws an outer iteration at a time')
+        super().__init__(batch, prox, eta, mini_batch_size, lr_decay, n_log, seed, n_slots=T2 if t2 is None else self.span, draw_id=draw_id)
         self.T2, self.variant = T2, variant
+        self._t2_dev = self._mu_new = None                      # per-problem T2: its int32 device vector, the refresh's scratch
+        self._drawn_n = 0                                       # ... and the steps [_drawn_base, _drawn_base + _drawn_n) the slots hold
+        if t2 is not None:
+            self._t2_dev = torch.from_numpy(T2.astype(np.int32)).to(batch.xrec.device)
+            self._mu_new = torch.empty_like(self.z)
         # the one-kernel inner iteration (csrc/csmri_fused.hip): CSMRI, f32, 256 x 256, true SVRG direction, a prox that
         # can follow it (TV inside the kernel, DnCNN after it)
         ok = (batch.kind == 'csmri' and batch.dtype == torch.float32 and batch.H == 256 and batch.W == 256
@@ -195,6 +225,8 @@ class SvrgEngine(_StochEngine):
     def step(self, idx_s=None):
         """One inner iteration for all B problems.  idx_s: int32 [B][mb] minibatch index lists (e.g. drawn from
         NumPy's legacy stream for reference-identical runs); None = device draws."""
+        if self._t2_dev is not None:
+            return self._step_pp(idx_s)
         b, s = self.b, self.s
         j, k = s % self.T2, s // self.T2
         if j == 0:                                              # outer: mu = grad_full(z); w = z
@@ -212,13 +244,73 @@ class SvrgEngine(_StochEngine):
         self.n_prox += 1
         self.s += 1                                             # eager steps keep the index on the host (no counter launch)
 
+    def refreshes(self, s):
+        """Per-problem T2: whether any problem refreshes at step s (the host knows s and the vector)."""
+        return bool((s % self.T2 == 0).any())
+
+    def _lr_pp(self, s):
+        """Per-problem T2: (step sizes, decay exponents k_b = s // T2_b) of step s.  Each step size is the product the scalar engine
+        forms from problem b's values, eta_b * lr_decay ** k_b in Python floats; lr_decay == 1 leaves eta as it was given."""
+        k = s // self.T2
+        if self.lr_decay == 1.0:
+            return self.eta, k
+        eta = np.broadcast_to(np.asarray(self.eta, np.float64), k.shape)
+        return np.array([float(e) * self.lr_decay ** int(kb) for e, kb in zip(eta, k)], np.float64), k
+
+    def _slot_pp(self, idx_s, s):
+        """Per-problem T2: the slot that holds step s's minibatch -- a window of `span` steps from s on, drawn with the absolute step
+        ids when s is outside the window the slots hold; host index lists go to slot 0."""
+        if idx_s is not None:
+            self.b.set_host(self.mbs, 0, idx_s)
+            self._drawn_base = None
+            return 0
+        if self._drawn_base is None or not self._drawn_base <= s < self._drawn_base + self._drawn_n:
+            self.b.draw(self.mbs, self._mb_draw, self.seed, s, self.span, **self._draw_kw)
+            self._drawn_base, self._drawn_n = s, self.span
+        return s - self._drawn_base
+
+    def _step_pp(self, idx_s):
+        """`step()` with a per-problem T2: where any problem refreshes, grad_full into the scratch and ONE pnp_refresh_pp; then the
+        ordinary inner iteration for all problems (at a problem's own refresh step w == z: its SVRG difference is exactly zero)."""
+        s = self.s
+        if self.refreshes(s):
+            self.b.grad_full(self.z, out=self._mu_new)
+            ops.refresh_pp(self._mu_new, self.z, self.mu, self.w, self._t2_dev, s)
+        j = self._slot_pp(idx_s, s) if self.variant == 'svrg' else 0
+        lr, k = self._lr_pp(s)
+        self.z = self._inner(j, lr, k, self.sse_log[self.n_prox % self.n_log])
+        self.n_prox += 1
+        self.s += 1
+
+    def run_span(self, n):
+        """n inner iterations from any step count.  With a per-problem T2, `outer_kernel_ok()` and lr_decay == 1 they run in
+        launches of at most `span` steps -- one draw launch plus one pnp_csmri_svrg_span_pp each, in which the workgroup that owns
+        a problem runs its steps back to back and refreshes where its own T2 says -- the same bits as stepping; otherwise eager
+        steps."""
+        if not (self._t2_dev is not None and self.lr_decay == 1.0 and self.outer_kernel_ok()):
+            for _ in range(n):
+                self.step()
+            return
+        b, px = self.b, self.prox
+        while n > 0:
+            m = min(n, self.span)
+            b.draw(self.mbs, self._mb_draw, self.seed, self.s, m, **self._draw_kw)
+            self._drawn_base, self._drawn_n = self.s, m
+            b.plan.svrg_span(self.z, self.w, self.mu, b.bits, b.yh_full, b.inv_m0, self.mbs.selbits, self.s, m, self._t2_dev,
+                             self._c('lr', 0, self.eta), self._mb_draw, b.xrec, self.sse_log, self.n_prox % self.n_log, px.sig,
+                             sigma_modifier=px.sigma_modifier)
+            self.s += m
+            self.n_prox += m
+            px.t += m
+            n -= m
+
     def _inner(self, j, lr, k, sse_out):
         """Inner iteration j of the current outer iteration: step size lr, decay exponent k (what the per-problem coefficient
         vectors are remade on), squared errors to sse_out.  Returns the tensor that holds the new iterate."""
         if self.fused:
             # folded refresh: at j = 0 the SVRG difference gs(z) - gs(w) is exactly zero (w == z), so that iteration is
             # z <- prox(z - lr * mu); ONE kernel forms mu, stores it and w, and goes on
-            if j == 0 and self.fold_outer:
+            if j == 0 and self.fold_outer and self._t2_dev is None:     # (per-problem T2: j is a draw slot; refresh_pp came first)
                 self._fused_outer(lr, sse_out, k)
             else:
                 self._fused_inner(j, lr, sse_out, k)
@@ -270,8 +362,9 @@ class SvrgEngine(_StochEngine):
 
     def graph_ok(self):
         """Whether one outer iteration of this engine can be captured: constant step size, a prox that works in place and keeps
-        no host-side per-call state (TVProx with denoise_strength == 0, DnCNNProx; not NLMProx, which ping-pongs)."""
-        return (self.lr_decay == 1.0 and getattr(self.prox, 'inplace', False)
+        no host-side per-call state (TVProx with denoise_strength == 0, DnCNNProx; not NLMProx, which ping-pongs).  Never with a
+        per-problem T2: the problems' outer iterations have no common period short of the lcm of their T2."""
+        return (self._t2_dev is None and self.lr_decay == 1.0 and getattr(self.prox, 'inplace', False)
                 and getattr(self.prox, 'denoise_strength', 0.0) == 0.0)
 
     def capture(self):
@@ -323,6 +416,8 @@ class SvrgEngine(_StochEngine):
         one_launch (default: when `outer_kernel_ok()`): every outer iteration is ONE draw launch + ONE kernel in which the
         workgroup that owns a problem runs its T2 inner iterations back to back -- the same bits as stepping; otherwise
         replays of the captured hipGraph."""
+        if self._t2_dev is not None:
+            raise ValueError('run_outer: with a per-problem T2 the batch has no common outer iteration; use run_span(n_steps)')
         if one_launch is None:
             one_launch = self.outer_kernel_ok()
         if one_launch:
@@ -358,6 +453,8 @@ class SarahEngine(_StochEngine):
     eta, mini_batch_size: scalars, or [B] arrays on a batch that takes them per problem; draw_id as in SgdEngine."""
 
     def __init__(self, batch, prox, eta, T2, mini_batch_size, lr_decay=1.0, n_log=4096, seed=0, draw_id=None):
+        if np.ndim(T2) != 0:
+            raise ValueError('SarahEngine takes a scalar T2 (its outer prox logs a row of its own: rows would stop lining up)')
         super().__init__(batch, prox, eta, mini_batch_size, lr_decay, n_log, seed, draw_id=draw_id)
         self.T2 = T2
         self.w_prev = torch.empty_like(self.z)

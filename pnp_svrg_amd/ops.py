@@ -236,6 +236,22 @@ class CsmriPlan:
                 _pp(mini_batch_size, self.B, torch.int32), _pp(sigma_modifier, self.B), float(fallback_sigma), _p(xrec), _p(sse_log),
                 int(log_row0), int(sse_log.shape[0]), _p(sigma_out), _stream()])
 
+    def svrg_span(self, z, w, mu, mask_bits, yh, alpha_vec, selbits, step0, n_steps, T2, lr, mini_batch_size, xrec, sse_log, log_row0,
+                  sigma_out, *, sigma_modifier=1.0, fallback_sigma=0.0):
+        """pnp_csmri_svrg_span_pp: inner iterations step0 .. step0 + n_steps - 1 with the TV prox in ONE launch, every problem
+        refreshing at the steps its own T2 names (z in place; w, mu updated where a problem refreshes).  T2: an int32 [B] device
+        tensor (or an int); selbits: int32 [>= n_steps, B, W, H/32], slot i = step step0 + i."""
+        assert self.dtype == torch.float32 and self.H == 256 and self.W == 256
+        for t in (z, w, mu, xrec):
+            assert t.dtype == self.dtype and t.numel() == self.B * self.H * self.W
+        assert selbits.dtype == torch.int32 and selbits.shape[0] >= n_steps and tuple(selbits.shape[1:]) == (self.B, self.W, self.H // 32)
+        assert sse_log.dtype == torch.float64 and sse_log.dim() == 2 and sse_log.shape[1] == self.B and sse_log.is_contiguous()
+        args = [self._h, _p(z), _p(w), _p(mu), _p(mask_bits), _p(yh), _p(alpha_vec), _p(selbits), int(step0), int(n_steps)]
+        for v in (_pp(T2, self.B, torch.int32), _pp(lr, self.B), _pp(mini_batch_size, self.B, torch.int32), _pp(sigma_modifier, self.B)):
+            args += (v[0], _p(v[1]))                            # (scalar, array or NULL): the entry point has the _pp form only
+        N.call('pnp_csmri_svrg_span_pp', *args, float(fallback_sigma), _p(xrec), _p(sse_log), int(log_row0), int(sse_log.shape[0]),
+               _p(sigma_out), _stream())
+
 
 class DncnnPlan:
     """pnp_dncnn_plan_*: DnCNN-17 prox for B images of H x W (fp32 network on the f32 matrix cores).
@@ -413,6 +429,17 @@ def axpbypcz(a, x, b=0.0, y=None, c=0.0, w=None, out=None):
         args.insert(8, int(B))
     _route('pnp_axpbypcz', args)
     return out
+
+
+def refresh_pp(mu_new, z, mu, w, t2_vec, step):
+    """pnp_refresh_pp: mu[p] = mu_new[p], w[p] = z[p] for every problem p = row p of the [B, ...] tensors with step % t2_vec[p] == 0
+    (t2_vec: int32 [B] device tensor, entries >= 1; step: a host int); the other problems' mu and w stay untouched.  ONE launch."""
+    require_gpu()
+    B = z.shape[0]
+    assert t2_vec.dtype == torch.int32 and tuple(t2_vec.shape) == (B,), f'per-problem T2: an int32 [{B}] device tensor'
+    for t in (mu_new, mu, w):
+        assert t.dtype == z.dtype and t.shape == z.shape
+    N.call('pnp_refresh_pp', _p(mu_new), _p(z), _p(mu), _p(w), _p(t2_vec), int(step), z.numel(), int(B), _DT[z.dtype], _stream())
 
 
 _NLM_W0 = {}

@@ -153,7 +153,7 @@ def make_prox(denoiser, **kw):
 def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta, n_inner, mini_batch_size=None, T2=None,
                 hist_size=50, H=256, W=256, dtype=torch.float32, max_batch=128, seeding='generator', variant='svrg', run_seed=1,
                 keep_trace=False, graph=True, kernel='Minimal', lr_decay=1.0, denoiser_kwargs=None, sigma_modifier=None,
-                shared_matrix=False, wide_trials=False, sarah_trials=False):
+                shared_matrix=False, wide_trials=False, sarah_trials=False, t2_trials=False):
     """Runner for `run_sweep` / `grid_search` over any cell of the reference's sweep (script_diff_sampratio_set12.py:23-25,
     41-51, 64-131): problem in {'csmri', 'deblur', 'pr'} x algorithm in {'gd', 'sgd', 'svrg', 'saga', 'sarah'} x denoiser in
     {'tv', 'nlm', factory}; `n_inner` inner iterations (prox evaluations of the stepped iterate) per item, hyper-parameters
@@ -188,6 +188,10 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
     draw_id, its elementwise steps one pnp_axpbypcz_pp launch each) on 'csmri', on 'deblur' with wide_trials=True and on 'pr' with
     shared_matrix=True; per-problem keys eta, mini_batch_size, sigma_modifier (T2 stays structural).  Without it `check_trials`
     refuses 'sarah' as it always has.  `run(items)` itself is unchanged by it.
+    t2_trials: opt in to 'T2' as a per-problem trial key of a trial-batched grid, algorithm='svrg' only (ValueError for
+    another algorithm once a trial names 'T2'), on the batches batch_trials already takes for svrg: a slab whose trials name 'T2'
+    runs on an SvrgEngine with a [B] T2 and advances by `run_span`.  Without it `check_trials` refuses the key as it always has.
+    `run(items)` itself is unchanged by it.
     Beside `run(items)` the runner offers the pieces of a trial-batched grid (`grid_search(batch_trials=True)`):
     `run.prepare_data(items)` builds a rank's batches WITHOUT engines, `run.run_trials(data, trials, max_batch_trials)` runs a list
     of trials ({'eta', 'mini_batch_size', 'sigma_modifier'} overrides) on them as tiled batches, `run.data_key` says which runners
@@ -311,6 +315,10 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
 
         def advance(self, n):
             eng, idx_d = self.eng, self.idx_d
+            if np.ndim(getattr(eng, 'T2', 0)) != 0:             # per-problem T2: no common outer iteration, the engine's own spans
+                eng.run_span(n)
+                self.done += n
+                return
             # device-drawn minibatches: whole outer iterations replay as hipGraphs (bit-identical to stepping; a rank's share
             # of a sweep is a small batch, where the ~25 launches of an inner iteration are a tenth of its time) -- when the
             # engine can be captured at all (an NLM prox ping-pongs between buffers and cannot: eager steps)
@@ -353,11 +361,13 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
             if nt not in base.tiles:
                 base.tiles = {nt: base.batch.tile(nt)}           # (one tiled copy at a time: slabs of one size reuse it)
             self.batch = base.tiles[nt]
-            lay = trial_layout(n, trials, {'eta': eta, 'mini_batch_size': mb, 'sigma_modifier': dkw.get('sigma_modifier', 1.0)})
+            per_t2 = t2_trials and any('T2' in tr for tr in trials)
+            lay = trial_layout(n, trials, {'eta': eta, 'mini_batch_size': mb, 'sigma_modifier': dkw.get('sigma_modifier', 1.0), 'T2': T2},
+                               keys=PER_PROBLEM_KEYS + ('T2',) if per_t2 else PER_PROBLEM_KEYS)
             pkw = dict(dkw)
             if any('sigma_modifier' in tr for tr in trials):
                 pkw['sigma_modifier'] = lay['sigma_modifier']
-            self.eng = E.make_engine(self.batch, make_prox(denoiser, **pkw), lay['eta'], T2,
+            self.eng = E.make_engine(self.batch, make_prox(denoiser, **pkw), lay['eta'], lay['T2'] if per_t2 else T2,
                                      None if algorithm == 'gd' else lay['mini_batch_size'], lr_decay=lr_decay, variant=variant,
                                      algorithm=algorithm, hist_size=hist_size, seed=base.items[0]['id'] + 1, draw_id=lay['draw_id'])
 
@@ -373,6 +383,12 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
 
     def check_trials(trials):
         """What a trial-batched run supports, each refusal naming the offender."""
+        keys = PER_PROBLEM_KEYS
+        if t2_trials and any('T2' in tr for tr in trials):
+            if algorithm != 'svrg':
+                raise ValueError(f"batch_trials: trial key 'T2' has no per-problem form for algorithm {algorithm!r} (t2_trials: 'svrg' "
+                                 'only; SarahEngine logs its outer prox in a row of its own, the others have no T2)')
+            keys = PER_PROBLEM_KEYS + ('T2',)
         if problem == 'pr' and not shared_matrix:
             raise ValueError(f"batch_trials: problem {problem!r} is not supported (only 'csmri') unless its trials share the "
                              'matrix: pass shared_matrix=True to make_runner')
@@ -390,10 +406,10 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
         if seeding == 'legacy':
             raise ValueError("batch_trials: seeding 'legacy' is not supported (host index lists; use 'counter' or 'generator')")
         for tr in trials:
-            bad = [k for k in tr if k not in PER_PROBLEM_KEYS]
+            bad = [k for k in tr if k not in keys]
             if bad or (callable(denoiser) and 'sigma_modifier' in tr):
                 raise ValueError(f'batch_trials: trial key {(bad or ["sigma_modifier"])[0]!r} has no per-problem form here '
-                                 f'(per-problem keys: {PER_PROBLEM_KEYS}; a prox factory takes no sigma_modifier)')
+                                 f'(per-problem keys: {keys}; a prox factory takes no sigma_modifier)')
 
     def prepare_data(items):
         """This rank's batches as `prepare` chunks them (the same groups, order and max_batch), data only."""
@@ -490,12 +506,13 @@ def best_over_trials(per_trial):
 PER_PROBLEM_KEYS = ('eta', 'mini_batch_size', 'sigma_modifier')
 
 
-def group_trials(trials):
+def group_trials(trials, per_problem_keys=PER_PROBLEM_KEYS):
     """Trials (dicts, grid order) -> [(structural params, [trial indices])]: trials that agree in every key that is not per
-    problem (T2 included: it changes the schedule) form a group, groups and members in order of first appearance."""
+    problem (by default T2 included: it changes the schedule; `per_problem_keys` with 'T2' among them groups across it)
+    form a group, groups and members in order of first appearance."""
     groups = {}
     for t, tr in enumerate(trials):
-        key = tuple((k, tr[k]) for k in tr if k not in PER_PROBLEM_KEYS)
+        key = tuple((k, tr[k]) for k in tr if k not in per_problem_keys)
         groups.setdefault(key, []).append(t)
     return [(dict(key), idx) for key, idx in groups.items()]
 
@@ -519,21 +536,23 @@ def trial_slabs(n_trials, n_items, max_batch_trials, max_trials=None):
     return [(t0, min(t0 + per, n_trials)) for t0 in range(0, n_trials, per)]
 
 
-def trial_layout(n_items, trials, defaults):
+def trial_layout(n_items, trials, defaults, keys=PER_PROBLEM_KEYS):
     """Per-problem vectors of a slab of len(trials) trials over n_items items: problem b = t * n_items + i carries trial t's
-    value of every per-problem key (`defaults` where the trial names none) and draw_id[b] = i."""
+    value of every per-problem key (`defaults` where the trial names none) and draw_id[b] = i.  keys: the per-problem keys to lay
+    out; with 'T2' among them the layout holds an int32 'T2' vector as well."""
     nt = len(trials)
     lay = {'draw_id': np.tile(np.arange(n_items, dtype=np.int64), nt)}
-    for k in PER_PROBLEM_KEYS:
+    for k in keys:
         if defaults.get(k) is None and not any(k in tr for tr in trials):
             lay[k] = None
             continue
         vals = np.repeat(np.array([tr.get(k, defaults.get(k)) for tr in trials]), n_items)
-        lay[k] = vals.astype(np.int32 if k == 'mini_batch_size' else np.float64)
+        lay[k] = vals.astype(np.int32 if k in ('mini_batch_size', 'T2') else np.float64)
     return lay
 
 
-def grid_search(items, make_runner, grid, group=None, *, batch_trials=False, max_batch_trials=1024, max_table_bytes=MAX_TABLE_BYTES):
+def grid_search(items, make_runner, grid, group=None, *, batch_trials=False, max_batch_trials=1024, max_table_bytes=MAX_TABLE_BYTES,
+                batch_T2=False):
     """The sweep the reference scripts run (process_img, script_diff_sampratio_set12.py:103-131): for every work item
     search the hyper-parameters and keep the best trial.  `make_runner(**params)` returns a runner as `run_sweep`
     takes; each rank runs every trial on ITS shard of the items (one batched engine per trial), the reduction over
@@ -546,6 +565,8 @@ def grid_search(items, make_runner, grid, group=None, *, batch_trials=False, max
     Runners made with wide_trials=True also take Deblur, pnp_saga (csmri, deblur) and the NLM prox; a pnp_saga slab is
     capped so that its gradient table stays within max_table_bytes (never below one trial).  Runners made with sarah_trials=True
     also take pnp_sarah on csmri, on deblur with wide_trials=True and on pr with shared_matrix=True.
+    batch_T2=True (with batch_trials=True; runners made with t2_trials=True, pnp_svrg only -- ValueError otherwise): 'T2' is a
+    per-problem key too, so trials that differ in T2 share a batch instead of splitting the grid.  Off by default.
     The rows returned are those of batch_trials=False."""
     if dist.is_available() and dist.is_initialized():
         rank, world = dist.get_rank(group), dist.get_world_size(group)
@@ -554,13 +575,16 @@ def grid_search(items, make_runner, grid, group=None, *, batch_trials=False, max
     mine = shard(items, rank, world)
     trials = grid_points(grid)
     per_trial = []
+    if batch_T2 and not batch_trials:
+        raise ValueError('batch_T2 groups the trials of a trial-batched grid: it needs batch_trials=True')
     if batch_trials:
         per_trial, data = [None] * len(trials), {}
-        for _, idx in group_trials(trials):
+        keys = PER_PROBLEM_KEYS + ('T2',) if batch_T2 else PER_PROBLEM_KEYS
+        for _, idx in group_trials(trials, keys):
             run = make_runner(**trials[idx[0]])
             if not hasattr(run, 'run_trials'):
                 raise ValueError('batch_trials needs runners of sweep.make_runner (run.prepare_data / run.run_trials)')
-            sub = [{k: v for k, v in trials[t].items() if k in PER_PROBLEM_KEYS} for t in idx]
+            sub = [{k: v for k, v in trials[t].items() if k in keys} for t in idx]
             run.check_trials(sub)
             if run.data_key not in data:
                 data[run.data_key] = run.prepare_data(mine)

@@ -11,6 +11,7 @@ this script verifies on the ISA of every k_svrg_iter instantiation that
     at labels).
 
     python tools/check_fused_isa.py [listing.s]        (without argument: compiles csmri_fused.hip with hipcc -S first)
+    python tools/check_fused_isa.py --pp [listing.s]   ... and the per-problem loops k_svrg_outer_pp and k_svrg_span_pp as well
 
 Also prints, per kernel, the spill traffic between workgroup barriers (where the register pressure bites)."""
 import re
@@ -36,12 +37,14 @@ def regs_of(text):
     return out
 
 
-def kernels(txt):
+def kernels(txt, pp=False):
+    """(name, body) of every k_svrg_iter instantiation and of k_svrg_outer; pp: also k_svrg_outer_pp and k_svrg_span_pp"""
+    names = ('_ZN3pnp11k_svrg_iter', '_ZN3pnp12k_svrg_outer') + (('_ZN3pnp15k_svrg_outer_pp', '_ZN3pnp14k_svrg_span_pp') if pp else ())
     lines = txt.split('\n')
     i = 0
     while i < len(lines):
         l = lines[i]
-        if l.startswith(('_ZN3pnp11k_svrg_iter', '_ZN3pnp12k_svrg_outer')) and l.split(';')[0].rstrip().endswith(':'):
+        if l.startswith(names) and l.split(';')[0].rstrip().endswith(':'):
             name = l.split(':')[0]
             body = []
             i += 1
@@ -138,11 +141,12 @@ def check(name, body):
 def main():
     args = sys.argv[1:]
     defines = [a for a in args if a.startswith('-D')]          # e.g. -DPNP_FUSED_CLOCK: the diagnostic build
-    paths = [a for a in args if not a.startswith('-D')]
+    pp = '--pp' in args                                         # also the per-problem loops: k_svrg_outer_pp, k_svrg_span_pp
+    paths = [a for a in args if not a.startswith('-')]
     txt = listing(paths[0] if paths else None, defines)
     bad = []
     nk = 0
-    for name, body in kernels(txt):
+    for name, body in kernels(txt, pp):
         nk += 1
         errors, n_loads, n_waits, segs = check(name, body)
         spill = ' '.join(f'{i}:{s["sst"]}/{s["sld"]}' for i, s in enumerate(segs) if s['sst'] or s['sld'])
