@@ -537,6 +537,29 @@ int pnp_axpbypcz_pp(double a, const double* a_pp, const void* x, double b, const
 int pnp_refresh_pp(const void* mu_new, const void* z, void* mu, void* w, const int32_t* t2_vec, int step, size_t n, int batch,
                    int dtype, void* stream);
 
+/* ------------------------------------------------------------------ the data-fidelity objective f(z), per problem
+ * f = || Y - forward_model(z) ||^2 / 2 / M (problems/CSMRI.py:61-64 with M = N, DeblurSR.py:114-117 with M = lrH * lrW, PR.py:70-73
+ * with M = num_meas): the forward passes of the gradients ending in a per-problem reduction -- no inverse / adjoint pass and no
+ * image write.  All three write f_out [batch] doubles = scale * (sum of squared residuals); the host passes scale = 1 / (2 M).
+ * The sums are taken in double whatever `dtype`, in a fixed order and without atomics: a problem's value depends neither on the
+ * batch size nor on its index in the batch.  Nothing is allocated and nothing synchronises (scratch: the plans' own workspaces,
+ * the caller's for PR), so the calls may be captured.  PNP_ERR_ARG before any device work: a NULL pointer, batch <= 0, a bad dtype.
+ *
+ * CSMRI: sum over the FULL spectrum of mask(k) |fft2(z)(k) - Y(k)|^2 (the mask need not be Hermitian, so the packed yh of
+ *   pnp_csmri_pack_y is not enough): YT [batch][W][H] complex, bitsT [batch][W][H/32] the bit-packed mask.  Entries of YT outside
+ *   the mask are not read into the sum.  Uses the plan's half-spectrum workspace, like pnp_csmri_grad_sel.                       */
+int pnp_csmri_objective(pnp_csmri_plan* plan, const void* z, const void* YT, const uint32_t* bitsT, double scale, double* f_out,
+                        void* stream);
+/* Deblur: sum over the M measurements of (S B z - Y)^2; z [batch][N], Y [batch][M].  Uses the plan's scratch, like pnp_deblur_grad. */
+int pnp_deblur_objective(pnp_deblur_plan* plan, const void* z, const void* Y, double scale, double* f_out, void* stream);
+/* PR: sum over the M rows of (|A w| - y)^2, A streamed once with 16-byte loads (any M, N; N % (16 / sizeof) != 0 takes scalar
+ *   loads).  w [batch][N], y [batch][M]; A [n_mat][M][N] with n_mat == batch (every problem its own matrix) or a divisor of batch
+ *   (the tiled batches of pnp_pr_grad_shared: problem b works on A[b % n_mat]).  workspace: pnp_pr_objective_workspace_bytes(M,
+ *   batch) bytes, 8-byte aligned.                                                                                              */
+size_t pnp_pr_objective_workspace_bytes(int M, int batch);
+int pnp_pr_objective(const void* A, const void* w, const void* y, int M, int N, int batch, int n_mat, int dtype, double scale,
+                     void* workspace, double* f_out, void* stream);
+
 /* ------------------------------------------------------------------ host: the legacy RNG draw of select_mb
  * np.random.choice(pool, size, replace=False) (problems/CSMRI.py:72, problems/problem.py:114) on the legacy MT19937 stream,
  * restated in C (no device work): out[k] = pool[perm[k]] (pool NULL: perm[k]) for the first `size` entries of

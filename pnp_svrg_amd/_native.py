@@ -98,7 +98,12 @@ SIGNATURES = {
     'pnp_csmri_svrg_span_pp': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _d, _vp, _i, _vp, _d, _vp, _d, _vp, _vp, _i,
                                     _i, _vp, _vp]),
     'pnp_refresh_pp': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _sz, _i, _i, _vp]),
-    'pnp_legacy_choice': (_i, [_vp, ctypes.POINTER(ctypes.c_int), _vp, _i, _i, _vp, _vp]),
+    # the data-fidelity objective per problem (csrc/objective.hip): f_out [batch] doubles
+    'pnp_csmri_objective': (_i, [_vp, _vp, _vp, _vp, _d, _vp, _vp]),
+    'pnp_deblur_objective': (_i, [_vp, _vp, _vp, _d, _vp, _vp]),
+    'pnp_pr_objective_workspace_bytes': (_sz, [_i, _i]),
+    'pnp_pr_objective': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _d, _vp, _vp, _vp]),
+    'pnp_legacy_choice':(_i, [_vp, ctypes.POINTER(ctypes.c_int), _vp, _i, _i, _vp, _vp]),
 }
 
 _lib = None

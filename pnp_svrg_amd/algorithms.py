@@ -293,7 +293,7 @@ class _SvrgGraph:
         torch.cuda.synchronize()
         self.t_per_outer = getattr(self.d, 't', 0) - t0          # the denoiser's call counter advances per prox (TV.py:22)
         g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
+        with ops.collector_held(), torch.cuda.graph(g):         # (no plan may be destroyed, hipFree, while the stream captures)
             self.outer_body()
         torch.cuda.synchronize()
         for dst, src in zip((self.z, self.log, self.cnt), keep):

@@ -5,6 +5,7 @@ A *batch problem* (CsmriBatch, DeblurBatch, PrBatch) holds the device-resident d
     grad_stoch(z, mbs, j, out, alpha, beta, c1)                alpha * grad_stoch(z, minibatch j) + beta * c1
     grad_stoch_diff(z, w, mbs, j, out, alpha, beta, c1, gamma, c2)
                                                                alpha * (gs(z) - gs(w)) + beta * c1 + gamma * c2
+    objective(z, out)                                          f(z) = ||Y - forward_model(z)||^2 / 2 / M per problem, float64 [B]
     minibatches(n) / draw(mbs, mb, seed, step0, nsteps) / set_host(mbs, j, idx)
 Minibatches are drawn on the device by default (counter-based keys + a threshold per (problem, step): csrc/draw.h;
 the selection itself is re-derived inside the gradient kernels and never stored); for reference-identical runs pass
@@ -273,6 +274,11 @@ class CsmriBatch(_BatchBase):
             return dict(selT=mbs.host[j])
         return dict(bits=mbs.selbits[j])
 
+    def objective(self, z, out=None):
+        """f(z) = ||Y - mask o fft2(z)||^2 / 2 / N per problem (problems/CSMRI.py:61-64) -> float64 [B] on the device: the forward row
+        pass and a column pass that ends in the sum over the full spectrum (pnp_csmri_objective); nothing is read back."""
+        return self.plan.objective(z, self.YT, self.bits, 0.5 / self.N, out=out)
+
     # ---- gradients
     def grad_full(self, z, out, alpha=1.0, beta=0.0, c1=None):
         return self.plan.grad(z, bits=self.bits, yh=self.yh_full, alpha=alpha, alpha_vec=self.inv_m0, beta=beta, c1=c1, out=out)
@@ -386,6 +392,11 @@ class DeblurBatch(_BatchBase):
             return dict(sel=mbs.host[j])
         return dict(mbd=mbs.mbd[j])
 
+    def objective(self, z, out=None):
+        """f(z) = ||Y - S B z||^2 / 2 / M per problem (problems/DeblurSR.py:114-117) -> float64 [B] on the device
+        (pnp_deblur_objective); nothing is read back."""
+        return self.plan.objective(z, self.Y, 0.5 / self.M, out=out)
+
     # alpha (and gamma of grad_stoch_diff): a scalar -> the plain calls; a float64 [B] device tensor -> the `_pp` entry points
     def _over_m(self, a):
         return a / self.M
@@ -434,6 +445,7 @@ class PrBatch(_BatchBase):
         else:
             self._ws = ops.pr_workspace(self.M, self.N, self.dtype, self.device, self.B)
         self._mb = None                                         # size of the last device draw (the row lists' width)
+        self._obj_ws = None                                     # scratch of `objective`, made on first use
 
     def tile(self, n):
         """A batch of n * B problems (problem t * B + i = this batch's problem i) on THIS batch's matrices: xrec, xinit, Y and sigma
@@ -508,6 +520,13 @@ class PrBatch(_BatchBase):
         if key not in buf:
             buf[key] = torch.empty((self.B, self._mb), dtype=torch.int32, device=self.device)
         return ops.rows_from_thresholds(self.M, self._mb, mbs.mbd[j], out=buf[key])
+
+    def objective(self, z, out=None):
+        """f(z) = ||Y - |A z|||^2 / 2 / M per problem (problems/PR.py:70-73) -> float64 [B] on the device (pnp_pr_objective: A is
+        streamed once; a tiled batch reads the matrix of its item, A[b % items]); nothing is read back."""
+        if self._obj_ws is None:
+            self._obj_ws = ops.pr_objective_workspace(self.M, self.B, self.device)
+        return ops.pr_objective(self.A, z.reshape(self.B, self.N), self.Y, 0.5 / self.M, workspace=self._obj_ws, out=out)
 
     def _g(self, z, rows, scale, out):
         ops.pr_grad_batch(self.A, z.reshape(self.B, self.N), self.Y, rows=rows, scale=scale, workspace=self._ws,

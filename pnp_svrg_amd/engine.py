@@ -28,6 +28,10 @@ SvrgEngine takes `T2` per problem as well: a [B] integer array make
 s % T2[b] == 0 -- one `pnp_refresh_pp` launch behind a full gradient at the steps where any problem refreshes -- and `run_span(n)`
 runs n steps in launches of `pnp_csmri_svrg_span_pp` where the one-kernel iteration holds the TV prox.  A scalar T2 takes exactly
 the calls it always took.
+Every engine takes `log_objective=True`: beside the squared errors, a second ring `obj_log` gets the data-fidelity
+objective f(z) of the iterate every logged prox returned (`batch.objective`, row for row with `sse_log`; `objective_log()` reads it
+back) -- the convergence signal on measured data, where there is no ground truth for a PSNR.  Such an engine steps eagerly
+(`graph_ok()` and `outer_kernel_ok()` are False); with it off nothing changes.
 """
 import numpy as np
 import torch
@@ -41,8 +45,9 @@ class LoopEngine:
     """State and log machinery shared by the engines: the iterate z [B, H, W], a device log ring of the squared errors
     of every prox evaluation (-> rounded PSNR traces like the reference's psnr_per_iter), the step counter."""
 
-    def __init__(self, batch, prox, eta, lr_decay=1.0, n_log=4096, seed=0):
+    def __init__(self, batch, prox, eta, lr_decay=1.0, n_log=4096, seed=0, log_objective=False):
         self.b, self.prox, self.eta, self.lr_decay, self.seed = batch, prox, eta, lr_decay, seed
+        self.log_objective = bool(log_objective)
         if np.ndim(eta) != 0:                                   # per-problem step sizes
             self.eta = np.ascontiguousarray(eta, np.float64)
             if self.eta.shape != (batch.B,) or not batch.per_problem:
@@ -52,6 +57,8 @@ class LoopEngine:
         self.z = batch.xinit.clone()
         self.sse_log = torch.zeros((n_log, batch.B), dtype=torch.float64, device=dev)
         self.n_log = n_log
+        # log_objective: a second ring, row for row beside sse_log, of f(iterate the logged prox returned) (batch.objective)
+        self.obj_log = torch.zeros((n_log, batch.B), dtype=torch.float64, device=dev) if self.log_objective else None
         prox.bind(batch)
         self.s = 0                                              # inner iterations done
         self.n_prox = 0                                         # prox evaluations logged
@@ -76,8 +83,28 @@ class LoopEngine:
 
     def _prox(self, z):
         out = self.prox(z, self.b.xrec, self.sse_log[self.n_prox % self.n_log])
+        if self.log_objective:
+            self._log_obj(self.n_prox % self.n_log, out)
         self.n_prox += 1
         return out
+
+    def _log_obj(self, row, z):
+        """log_objective: f(z) per problem into the row of obj_log that the SSE of this prox went to."""
+        self.b.objective(z, out=self.obj_log[row])
+
+    def _ring(self, log):
+        """The rows of a log ring in chronological order: when more than n_log evaluations were logged, the last n_log of them."""
+        if self.n_prox > self.n_log:
+            return torch.roll(log, -(self.n_prox % self.n_log), 0)             # oldest surviving row first
+        return log[:self.n_prox]
+
+    def objective_log(self):
+        """[prox evaluations][B] float64: f of the iterate every logged prox returned, in chronological order, read back once; the
+        rows are those of `psnr_trace` (when more than n_log evaluations were logged, the last n_log of them).  Needs an engine made
+        with log_objective=True."""
+        if not self.log_objective:
+            raise ValueError('objective_log() needs an engine made with log_objective=True')
+        return self._ring(self.obj_log).cpu().numpy()
 
     def psnr_trace(self):
         """[prox evaluations][B] PSNR (rounded to 0.01 dB like problems/problem.py:33-35) in chronological order,
@@ -107,8 +134,9 @@ class _StochEngine(LoopEngine):
     # (seed, step, problem) only, so a window of steps drawn together holds the very same selections.
     AHEAD = 16
 
-    def __init__(self, batch, prox, eta, mini_batch_size, lr_decay=1.0, n_log=4096, seed=0, n_slots=None, draw_id=None):
-        super().__init__(batch, prox, eta, lr_decay, n_log, seed)
+    def __init__(self, batch, prox, eta, mini_batch_size, lr_decay=1.0, n_log=4096, seed=0, n_slots=None, draw_id=None,
+                 log_objective=False):
+        super().__init__(batch, prox, eta, lr_decay, n_log, seed, log_objective=log_objective)
         batch._check_mb(mini_batch_size)
         self.mb = self._mb_draw = mini_batch_size               # (host value for the coefficients, what the draws take)
         self._draw_kw = {}
@@ -173,7 +201,7 @@ class SvrgEngine(_StochEngine):
     FUSED_MIN_BATCH = 192
 
     def __init__(self, batch, prox, eta, T2, mini_batch_size, lr_decay=1.0, variant='svrg', n_log=4096, seed=0, fused=None,
-                 fold_outer=True, draw_id=None, span=None):
+                 fold_outer=True, draw_id=None, span=None, log_objective=False):
         t2 = None
         if np.ndim(T2) != 0:                                    # per-problem T2: checked on the host (the kernels cannot)
             t2 = np.asarray(T2)
@@ -190,7 +218,8 @@ class SvrgEngine(_StochEngine):
                 raise ValueError(f'span: at least one step per draw window, got {span}')
         elif span is not None:
             raise ValueError('span is the draw window of a per-problem T2; a scalar T2 draws an outer iteration at a time')
-        super().__init__(batch, prox, eta, mini_batch_size, lr_decay, n_log, seed, n_slots=T2 if t2 is None else self.span, draw_id=draw_id)
+        super().__init__(batch, prox, eta, mini_batch_size, lr_decay, n_log, seed, n_slots=T2 if t2 is None else self.span, draw_id=draw_id,
+                         log_objective=log_objective)
         self.T2, self.variant = T2, variant
         self._t2_dev = self._mu_new = None                      # per-problem T2: its int32 device vector, the refresh's scratch
         self._drawn_n = 0                                       # ... and the steps [_drawn_base, _drawn_base + _drawn_n) the slots hold
@@ -241,6 +270,8 @@ class SvrgEngine(_StochEngine):
             elif self.mbs.host[j] is not None:                  # a host-fed outer iteration continued with device draws
                 self._draw_slot(j, s)
         self.z = self._inner(j, self.eta * self.lr_decay ** k, k, self.sse_log[self.n_prox % self.n_log])
+        if self.log_objective:
+            self._log_obj(self.n_prox % self.n_log, self.z)
         self.n_prox += 1
         self.s += 1                                             # eager steps keep the index on the host (no counter launch)
 
@@ -279,6 +310,8 @@ class SvrgEngine(_StochEngine):
         j = self._slot_pp(idx_s, s) if self.variant == 'svrg' else 0
         lr, k = self._lr_pp(s)
         self.z = self._inner(j, lr, k, self.sse_log[self.n_prox % self.n_log])
+        if self.log_objective:
+            self._log_obj(self.n_prox % self.n_log, self.z)
         self.n_prox += 1
         self.s += 1
 
@@ -365,7 +398,7 @@ class SvrgEngine(_StochEngine):
         no host-side per-call state (TVProx with denoise_strength == 0, DnCNNProx; not NLMProx, which ping-pongs).  Never with a
         per-problem T2: the problems' outer iterations have no common period short of the lcm of their T2."""
         return (self._t2_dev is None and self.lr_decay == 1.0 and getattr(self.prox, 'inplace', False)
-                and getattr(self.prox, 'denoise_strength', 0.0) == 0.0)
+                and getattr(self.prox, 'denoise_strength', 0.0) == 0.0 and not self.log_objective)
 
     def capture(self):
         """Capture one outer iteration into a hipGraph (torch.cuda.CUDAGraph on ROCm).  Needs `graph_ok()`, a step count that
@@ -387,7 +420,7 @@ class SvrgEngine(_StochEngine):
             torch.cuda.current_stream().wait_stream(side)
             torch.cuda.synchronize()
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
+            with ops.collector_held(), torch.cuda.graph(g):     # (no plan may be destroyed, hipFree, while the stream captures)
                 self._outer_body()
             torch.cuda.synchronize()
         finally:
@@ -409,7 +442,8 @@ class SvrgEngine(_StochEngine):
         """Whether whole outer iterations can run as ONE launch each (pnp_csmri_svrg_outer_iteration): the one-kernel iteration
         with the prox inside it (TV, no host-side per-call state), the outer refresh folded in, device-drawn minibatches."""
         return (self.fused and self.fold_outer and self.variant == 'svrg' and getattr(self.prox, 'fused_denoise', False)
-                and getattr(self.prox, 'denoise_strength', 0.0) == 0.0 and all(h is None for h in self.mbs.host))
+                and getattr(self.prox, 'denoise_strength', 0.0) == 0.0 and all(h is None for h in self.mbs.host)
+                and not self.log_objective)
 
     def run_outer(self, n_outer=1, one_launch=None):
         """n_outer outer iterations = n_outer * T2 inner iterations, from a step count that is a multiple of T2.
@@ -452,10 +486,10 @@ class SarahEngine(_StochEngine):
     inner loop, and the outer step ignores lr_decay.  One log row per prox: outer rows at s % T2 == 0.
     eta, mini_batch_size: scalars, or [B] arrays on a batch that takes them per problem; draw_id as in SgdEngine."""
 
-    def __init__(self, batch, prox, eta, T2, mini_batch_size, lr_decay=1.0, n_log=4096, seed=0, draw_id=None):
+    def __init__(self, batch, prox, eta, T2, mini_batch_size, lr_decay=1.0, n_log=4096, seed=0, draw_id=None, log_objective=False):
         if np.ndim(T2) != 0:
             raise ValueError('SarahEngine takes a scalar T2 (its outer prox logs a row of its own: rows would stop lining up)')
-        super().__init__(batch, prox, eta, mini_batch_size, lr_decay, n_log, seed, draw_id=draw_id)
+        super().__init__(batch, prox, eta, mini_batch_size, lr_decay, n_log, seed, draw_id=draw_id, log_objective=log_objective)
         self.T2 = T2
         self.w_prev = torch.empty_like(self.z)
         self.w_next = torch.empty_like(self.z)
@@ -489,8 +523,9 @@ class SagaEngine(_StochEngine):
     The replaced row r of every step is drawn on the host (one value per step for the whole batch; pass `r=` to
     `step` to impose the reference's `np.random.choice(hist_size, 1)` stream)."""
 
-    def __init__(self, batch, prox, eta, mini_batch_size, hist_size=50, lr_decay=1.0, n_log=4096, seed=0, idx0=None, draw_id=None):
-        super().__init__(batch, prox, eta, mini_batch_size, lr_decay, n_log, seed, draw_id=draw_id)
+    def __init__(self, batch, prox, eta, mini_batch_size, hist_size=50, lr_decay=1.0, n_log=4096, seed=0, idx0=None, draw_id=None,
+                 log_objective=False):
+        super().__init__(batch, prox, eta, mini_batch_size, lr_decay, n_log, seed, draw_id=draw_id, log_objective=log_objective)
         self.hist = hist_size
         self.g = torch.empty_like(self.z)
         self._rng = np.random.default_rng(seed + 977)

@@ -1,6 +1,8 @@
 """Torch-tensor front end of the C-ABI calls.  PyTorch is plumbing here: it owns HBM
 allocations and the HIP stream; every op below is one call into libpnp_hip.so."""
+import contextlib
 import ctypes
+import gc
 import torch
 from . import _native as N
 
@@ -74,8 +76,31 @@ def require_gpu():
     N.lib()
 
 
+@contextlib.contextmanager
+def collector_held():
+    """Around a hipGraph capture.  A plan frees its device buffers when it is destroyed (hipFree), and a hipFree while a stream
+    captures invalidates the capture.  A plan that died inside a reference cycle goes whenever the cyclic collector next runs, and
+    torch.cuda.graph does not collect before it begins: collect now, and hold the collector off until the block ends."""
+    gc.collect()
+    was_on = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was_on:
+            gc.enable()
+
+
+def _f_out(out, B, device):
+    """The float64 [B] result vector of the objective calls (as pnp_sse's)."""
+    if out is None:
+        return torch.empty(B, dtype=torch.float64, device=device)
+    assert out.dtype == torch.float64 and tuple(out.shape) == (B,)
+    return out
+
+
 class CsmriPlan:
-    """pnp_csmri_plan_* : masked-FFT gradient of B independent H x W CSMRI problems."""
+    """pnp_csmri_plan_*: masked-FFT gradient of B independent H x W CSMRI problems."""
 
     def __init__(self, H, W, batch, dtype=torch.float32):
         require_gpu()
@@ -168,6 +193,16 @@ class CsmriPlan:
         assert YT is None or (YT.dtype == _CDT[self.dtype] and tuple(YT.shape) == (self.B, self.W, self.H))
         _route('pnp_csmri_grad_sel', [self._h, _p(a), _p(b), _p(selT), _p(bits), _p(yh), _p(YT), _pp(alpha, self.B), _p(alpha_vec),
                                       float(beta), _p(c1), _pp(gamma, self.B), _p(c2), _p(out), _stream()])
+        return out
+
+    def objective(self, z, YT, bits, scale, out=None):
+        """pnp_csmri_objective: scale * sum over the full spectrum of mask |fft2(z) - Y|^2 per problem -> float64 [B].
+        YT: complex [B, W, H] (Y transposed), bits: the bit-packed mask int32 [B, W, H/32]."""
+        assert z.dtype == self.dtype and z.numel() == self.B * self.H * self.W
+        assert YT.dtype == _CDT[self.dtype] and tuple(YT.shape) == (self.B, self.W, self.H)
+        assert bits.dtype == torch.int32 and tuple(bits.shape) == (self.B, self.W, self.H // 32)
+        out = _f_out(out, self.B, z.device)
+        N.call('pnp_csmri_objective', self._h, _p(z), _p(YT), _p(bits), float(scale), _p(out), _stream())
         return out
 
     def generate(self, images, image_idx, thresh, snr_fac, seed, item_id, with_mask=True):
@@ -532,6 +567,13 @@ class DeblurPlan:
         N.call('pnp_deblur_forward', self._h, _p(x), _p(out), _stream())
         return out
 
+    def objective(self, z, Y, scale, out=None):
+        """pnp_deblur_objective: scale * sum over the M measurements of (S B z - Y)^2 per problem -> float64 [B]."""
+        assert z.dtype == self.dtype and Y.dtype == self.dtype and z.numel() == self.B * self.N and Y.numel() == self.B * self.M
+        out = _f_out(out, self.B, z.device)
+        N.call('pnp_deblur_objective', self._h, _p(z), _p(Y), float(scale), _p(out), _stream())
+        return out
+
     def generate(self, images, image_idx, snr_fac, seed, item_id):
         """pnp_deblur_generate: the B problems of this plan generated on the device from the counter-based stream of
         include/pnp_hip.h.  images: [n, H, W] of the plan's dtype (normalised); per item device vectors image_idx (int32),
@@ -643,6 +685,28 @@ def pr_grad_shared(A, Y, W, W2=None, mbd=None, ind=None, alpha=1.0, alpha_div=1.
     out = out if out is not None else torch.empty((B, Nn), dtype=A.dtype, device=A.device)
     _route('pnp_pr_grad_shared', [_p(A), _p(Y), _p(W), _p(W2), _p(mbd), _p(ind), M, Nn, B, items, _DT[A.dtype], _pp(alpha, B),
                                   float(alpha_div), float(beta), _p(c1), _pp(gamma, B), _p(c2), _p(workspace), _p(out), _stream()])
+    return out
+
+
+def pr_objective_workspace(M, B, device):
+    """Scratch of pnp_pr_objective for B problems of M measurements (float64: the per-workgroup partial sums)."""
+    return torch.empty(max(1, N.lib().pnp_pr_objective_workspace_bytes(int(M), int(B)) // 8), dtype=torch.float64, device=device)
+
+
+def pr_objective(A, w, y, scale, workspace=None, out=None):
+    """pnp_pr_objective: scale * sum over the M rows of (|A w| - y)^2 per problem -> float64 [B].  A [n_mat, M, N] with n_mat == B
+    or a divisor of B (problem b works on A[b % n_mat]: the tiled batches of pr_grad_shared); w [B, N]; y [B, M]."""
+    require_gpu()
+    n_mat, M, Nn = A.shape
+    B = w.numel() // Nn
+    assert w.dtype == A.dtype and y.dtype == A.dtype and w.numel() == B * Nn and y.numel() == B * M
+    if B % n_mat != 0:
+        raise ValueError(f'pr_objective: {B} problems on {n_mat} matrices (the number of matrices must divide the batch)')
+    if workspace is None:
+        workspace = pr_objective_workspace(M, B, A.device)
+    assert workspace.dtype == torch.float64 and workspace.numel() * 8 >= N.lib().pnp_pr_objective_workspace_bytes(M, B)
+    out = _f_out(out, B, A.device)
+    N.call('pnp_pr_objective', _p(A), _p(w), _p(y), M, Nn, B, n_mat, _DT[A.dtype], float(scale), _p(workspace), _p(out), _stream())
     return out
 
 

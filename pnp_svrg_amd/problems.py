@@ -199,6 +199,14 @@ class CSMRI(Problem):
         w = w.double().cpu().numpy() if self._is_dev(w) else w
         return np.linalg.norm(self.Y - self.forward_model(w)) ** 2 / 2 / self.M
 
+    def objective(self, w):
+        """`f(w)` from the device path (pnp_csmri_objective: real row pass, column pass ending in the sum over the full spectrum)
+        instead of the host forward model; w: a NumPy array or a device tensor.  Returns a float64 scalar."""
+        wd = (w if self._is_dev(w) else self.to_device(w)).reshape(1, self.H, self.W)
+        if self.__dict__.get('_bits') is None:
+            self._bits = self.plan.pack_mask(self._maskT)
+        return np.float64(self.plan.objective(wd, self._YT, self._bits, 0.5 / self.M).item())
+
     # ---- device state
     def _upload(self):
         H, W = self.H, self.W
@@ -377,6 +385,12 @@ class Deblur(Problem):
         w = w.double().cpu().numpy() if self._is_dev(w) else w
         return np.linalg.norm(self.Y - self.forward_model(w)) ** 2 / 2 / self.M
 
+    def objective(self, w):
+        """`f(w)` from the device path (pnp_deblur_objective) with nothing but the scalar read back; w: a NumPy array or a device
+        tensor.  Returns a float64 scalar."""
+        wd = (w if self._is_dev(w) else self.to_device(w)).reshape(1, self.N)
+        return np.float64(self.plan.objective(wd, self._Y_d, 0.5 / self.M).item())
+
     def grad_full(self, z):
         zd = (z if self._is_dev(z) else self.to_device(z)).reshape(1, self.N)
         g = self.plan.grad(zd, self._Y_d, scale=1.0 / self.M)
@@ -441,6 +455,12 @@ class PhaseRetrieval(Problem):
 
     def f(self, w):
         return np.linalg.norm(self.Y - self.forward_model(w)) ** 2 / 2 / self.M
+
+    def objective(self, w):
+        """`f(w)` from the device path (pnp_pr_objective: the device copy of A streamed once) instead of the host product; w: a
+        NumPy array or a device tensor.  Returns a float64 scalar."""
+        wd = (w if self._is_dev(w) else self.to_device(w)).reshape(1, self.N)
+        return np.float64(ops.pr_objective(self._A_d.reshape(1, self.M, self.N), wd, self._Y_d.reshape(1, self.M), 0.5 / self.M).item())
 
     def _grad(self, z, rows, scale):
         zd = (z if self._is_dev(z) else self.to_device(z)).reshape(-1)

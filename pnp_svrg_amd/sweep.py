@@ -153,7 +153,7 @@ def make_prox(denoiser, **kw):
 def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta, n_inner, mini_batch_size=None, T2=None,
                 hist_size=50, H=256, W=256, dtype=torch.float32, max_batch=128, seeding='generator', variant='svrg', run_seed=1,
                 keep_trace=False, graph=True, kernel='Minimal', lr_decay=1.0, denoiser_kwargs=None, sigma_modifier=None,
-                shared_matrix=False, wide_trials=False, sarah_trials=False, t2_trials=False):
+                shared_matrix=False, wide_trials=False, sarah_trials=False, t2_trials=False, objective=False):
     """Runner for `run_sweep` / `grid_search` over any cell of the reference's sweep (script_diff_sampratio_set12.py:23-25,
     41-51, 64-131): problem in {'csmri', 'deblur', 'pr'} x algorithm in {'gd', 'sgd', 'svrg', 'saga', 'sarah'} x denoiser in
     {'tv', 'nlm', factory}; `n_inner` inner iterations (prox evaluations of the stepped iterate) per item, hyper-parameters
@@ -192,6 +192,10 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
     another algorithm once a trial names 'T2'), on the batches batch_trials already takes for svrg: a slab whose trials name 'T2'
     runs on an SvrgEngine with a [B] T2 and advances by `run_span`.  Without it `check_trials` refuses the key as it always has.
     `run(items)` itself is unchanged by it.
+    objective: True makes every engine log the data-fidelity objective f(z) beside the squared errors (engine `log_objective`,
+    DESIGN 10; such engines step eagerly): result rows gain 'f_final' (f of the last logged iterate) and, with keep_trace=True,
+    'f_trace' (one value per 'psnr_trace' entry); trial-batched runs carry it through.  False (default): rows, engines and launches
+    are exactly what they were.  Anything but a bool is a ValueError.
     Beside `run(items)` the runner offers the pieces of a trial-batched grid (`grid_search(batch_trials=True)`):
     `run.prepare_data(items)` builds a rank's batches WITHOUT engines, `run.run_trials(data, trials, max_batch_trials)` runs a list
     of trials ({'eta', 'mini_batch_size', 'sigma_modifier'} overrides) on them as tiled batches, `run.data_key` says which runners
@@ -206,6 +210,9 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
         raise ValueError('T2 is required')
     if seeding == 'device' and problem != 'csmri':
         raise ValueError(f"seeding='device' is supported for problem='csmri' only (got {problem!r}); use 'generator' or 'legacy'")
+    if not isinstance(objective, (bool, np.bool_)):
+        raise ValueError(f'objective: True or False, got {objective!r}')
+    obj_kw = {'log_objective': True} if objective else {}       # (off: the engines are made with the arguments they always got)
     if shared_matrix and problem != 'pr':
         raise ValueError(f"shared_matrix=True is for problem='pr' (got {problem!r}): only its problems have a matrix to share")
     mb, dkw = mini_batch_size, dict(denoiser_kwargs or {})
@@ -310,7 +317,7 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
             if algorithm == 'saga' and self.idx_d is not None:
                 kw['idx0'] = self.idx_d[0]
             self.eng = E.make_engine(self.batch, make_prox(denoiser, **dkw), eta, T2, mb, lr_decay=lr_decay, variant=variant,
-                                     algorithm=algorithm, hist_size=hist_size, **kw)
+                                     algorithm=algorithm, hist_size=hist_size, **kw, **obj_kw)
             self.done = 0
 
         def advance(self, n):
@@ -339,6 +346,7 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
             tr = self.eng.psnr_trace()
             psnr0 = self.batch.psnr_init()
             z = self.eng.z.cpu().numpy()
+            fl = self.eng.objective_log() if objective else None
             out = []
             for j, it in enumerate(self.items):
                 r = {'id': it['id'], 'item': it, 'psnr_init': float(psnr0[j]), 'psnr_final': float(tr[-1, j]),
@@ -347,6 +355,10 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
                     r['M0'] = int(self.batch.M0[j])
                 if keep_trace:
                     r['psnr_trace'] = tr[:, j].copy()
+                if objective:
+                    r['f_final'] = float(fl[-1, j])
+                    if keep_trace:
+                        r['f_trace'] = fl[:, j].copy()
                 out.append(r)
             return out
 
@@ -369,7 +381,8 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
                 pkw['sigma_modifier'] = lay['sigma_modifier']
             self.eng = E.make_engine(self.batch, make_prox(denoiser, **pkw), lay['eta'], lay['T2'] if per_t2 else T2,
                                      None if algorithm == 'gd' else lay['mini_batch_size'], lr_decay=lr_decay, variant=variant,
-                                     algorithm=algorithm, hist_size=hist_size, seed=base.items[0]['id'] + 1, draw_id=lay['draw_id'])
+                                     algorithm=algorithm, hist_size=hist_size, seed=base.items[0]['id'] + 1, draw_id=lay['draw_id'],
+                                     **obj_kw)
 
     def _group_chunks(items):
         groups = {}
@@ -456,6 +469,7 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
     run.prepare, run.advance, run.collect, run.warm = prepare, advance, collect, warm
     run.prepare_data, run.run_trials, run.check_trials = prepare_data, run_trials, check_trials
     run.data_key = (id(images), problem, seeding, H, W, dtype, max_batch, kernel)
+    run.objective = bool(objective)
     run.names = (_REF_NAMES[problem], 'CNN' if callable(denoiser) else _REF_NAMES.get(denoiser, str(denoiser)), 'pnp_' + algorithm)
     return run
 
@@ -489,17 +503,35 @@ def grid_points(grid):
     return [dict(zip(keys, vals)) for vals in itertools.product(*(grid[k] for k in keys))]
 
 
-def best_over_trials(per_trial):
+SCORES = ('psnr', 'objective')
+
+
+def _check_score(score):
+    if score not in SCORES:
+        raise ValueError(f'score: one of {SCORES}, got {score!r}')
+
+
+def best_over_trials(per_trial, score='psnr'):
     """per_trial: list of (params, [result dict per item]) -> one row per item with the minimum loss (ties: first trial,
-    like hyperopt's best_trial on equal losses) and the parameters that achieved it.  NaN losses never win."""
+    like hyperopt's best_trial on equal losses) and the parameters that achieved it.  NaN losses never win.
+    score='objective': the trial with the smallest 'f_final' wins instead (same ties, NaN never wins), and the row carries it; the
+    results must hold 'f_final' (runners made with objective=True) -- ValueError otherwise."""
+    _check_score(score)
+    key = 'loss' if score == 'psnr' else 'f_final'
+    if score == 'objective':
+        for _, results in per_trial:
+            if any('f_final' not in r for r in results):
+                raise ValueError("score='objective' needs result rows with 'f_final': make the runners with objective=True")
     best = {}
     for params, results in per_trial:
         for r in results:
             cur = best.get(r['id'])
-            loss = r['loss']
-            if cur is None or (not np.isnan(loss) and (np.isnan(cur['loss']) or loss < cur['loss'])):
-                best[r['id']] = {'id': r['id'], 'item': r['item'], 'loss': loss, 'params': dict(params),
+            val = r[key]
+            if cur is None or (not np.isnan(val) and (np.isnan(cur[key]) or val < cur[key])):
+                best[r['id']] = {'id': r['id'], 'item': r['item'], 'loss': r['loss'], 'params': dict(params),
                                  'psnr_init': r.get('psnr_init'), 'psnr_final': r.get('psnr_final')}
+                if score == 'objective':
+                    best[r['id']]['f_final'] = val
     return [best[k] for k in sorted(best)]
 
 
@@ -552,7 +584,7 @@ def trial_layout(n_items, trials, defaults, keys=PER_PROBLEM_KEYS):
 
 
 def grid_search(items, make_runner, grid, group=None, *, batch_trials=False, max_batch_trials=1024, max_table_bytes=MAX_TABLE_BYTES,
-                batch_T2=False):
+                batch_T2=False, score='psnr'):
     """The sweep the reference scripts run (process_img, script_diff_sampratio_set12.py:103-131): for every work item
     search the hyper-parameters and keep the best trial.  `make_runner(**params)` returns a runner as `run_sweep`
     takes; each rank runs every trial on ITS shard of the items (one batched engine per trial), the reduction over
@@ -567,7 +599,16 @@ def grid_search(items, make_runner, grid, group=None, *, batch_trials=False, max
     also take pnp_sarah on csmri, on deblur with wide_trials=True and on pr with shared_matrix=True.
     batch_T2=True (with batch_trials=True; runners made with t2_trials=True, pnp_svrg only -- ValueError otherwise): 'T2' is a
     per-problem key too, so trials that differ in T2 share a batch instead of splitting the grid.  Off by default.
-    The rows returned are those of batch_trials=False."""
+    The rows returned are those of batch_trials=False.
+    score: 'psnr' (default) keeps the trial with the smallest PSNR loss, as always; 'objective' keeps the trial with the smallest
+    'f_final' -- the selection for measured data, where there is no ground truth -- and needs runners made with objective=True
+    (ValueError before anything runs otherwise); its rows also carry 'f_final'."""
+    _check_score(score)
+
+    def check_runner(run):
+        if score == 'objective' and not getattr(run, 'objective', True):       # (a runner that does not say is judged by its rows)
+            raise ValueError("score='objective' needs runners made with objective=True (their rows carry 'f_final')")
+        return run
     if dist.is_available() and dist.is_initialized():
         rank, world = dist.get_rank(group), dist.get_world_size(group)
     else:
@@ -581,7 +622,7 @@ def grid_search(items, make_runner, grid, group=None, *, batch_trials=False, max
         per_trial, data = [None] * len(trials), {}
         keys = PER_PROBLEM_KEYS + ('T2',) if batch_T2 else PER_PROBLEM_KEYS
         for _, idx in group_trials(trials, keys):
-            run = make_runner(**trials[idx[0]])
+            run = check_runner(make_runner(**trials[idx[0]]))
             if not hasattr(run, 'run_trials'):
                 raise ValueError('batch_trials needs runners of sweep.make_runner (run.prepare_data / run.run_trials)')
             sub = [{k: v for k, v in trials[t].items() if k in keys} for t in idx]
@@ -592,9 +633,9 @@ def grid_search(items, make_runner, grid, group=None, *, batch_trials=False, max
                 per_trial[t] = (trials[t], [{k: v for k, v in r.items() if k != 'z'} for r in res])
     else:
         for params in trials:
-            res = make_runner(**params)(mine) if mine else []
+            res = check_runner(make_runner(**params))(mine) if mine else []
             per_trial.append((params, [{k: v for k, v in r.items() if k != 'z'} for r in res]))
-    return gather_results(best_over_trials(per_trial), 0, group)
+    return gather_results(best_over_trials(per_trial, score), 0, group)
 
 
 def write_tuning_csv(path, rows, problem='csmri', denoiser='', algorithm='pnp_svrg'):
