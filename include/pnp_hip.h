@@ -155,6 +155,25 @@ int pnp_csmri_svrg_outer_step(pnp_csmri_plan* plan, const void* z, const uint32_
                               double sigma_modifier, double fallback_sigma, const void* xrec, double* sse_out,
                               void* sigma_out, void* stream);
 
+/* One whole inner iteration of the SARAH loop -- algorithms/pnp_sarah.py:72-104: the recursive direction, step, estimate_sigma,
+ * TVDenoiser.denoise, Problem.PSNR, w_prev = z -- in one kernel -- the SARAH form of pnp_csmri_svrg_step (f32 plans of 256 x 256):
+ *     v_out = alpha * alpha_vec[b] * Re ifft2( sel o fft2(a - b) ) + beta * c1        (a = w_next, b = w_prev, c1 = v_prev, beta = 1)
+ *     out   = prox_TV( c2 + gamma * v_out )                                          (c2 = z, gamma = -lr)
+ *     out2  = out                                                                    (nullable; w_prev)
+ * v_out is recursion state: it is stored before c2 is folded in, and equals, bit for bit, what pnp_csmri_grad_sel (bits form,
+ * one-kernel route) gives for the same a, b, alpha, beta, c1; the step is one fused multiply-add per element.  No data term:
+ * grad_stoch is affine, the Y terms of the difference cancel.  bitsT, alpha_vec, sigma_modifier, fallback_sigma, xrec, sse_out,
+ * sigma_out as in pnp_csmri_svrg_step.  denoise == 0: stop after the noise estimate and store c2 + gamma * v_out (for a prox that is
+ * not this one); out2 must then be NULL.
+ * Aliasing: v_out may alias c1, out may alias c2, out2 may alias b (the engine's in-place form: v, z and w_prev each updated where
+ * they lie).  v_out must not alias a, b, c2, out or out2.
+ * PNP_ERR_ARG before any device work: a NULL plan, a, b, bitsT, c1, c2, v_out or out; sse_out without xrec; out2 with
+ * denoise == 0; a plan that is not f32 256 x 256; v_out aliasing anything but c1.                                  */
+int pnp_csmri_sarah_step(pnp_csmri_plan* plan, const void* a, const void* b, const uint32_t* bitsT, double alpha,
+                         const void* alpha_vec, double beta, const void* c1, double gamma, const void* c2, void* v_out,
+                         void* out, void* out2, int denoise, double sigma_modifier, double fallback_sigma, const void* xrec,
+                         double* sse_out, void* sigma_out, void* stream);
+
 /* A whole OUTER iteration of the SVRG loop with the TV prox -- algorithms/pnp_svrg.py:32-95 for T2 inner iterations: the refresh
  * mu = grad_full(z), w = z, then T2 times { minibatch SVRG direction, step, estimate_sigma, TVDenoiser.denoise, PSNR } -- in ONE
  * launch: the workgroup that owns a problem runs pnp_csmri_svrg_outer_step and then T2 - 1 times pnp_csmri_svrg_step (a = z,
@@ -204,6 +223,12 @@ int pnp_csmri_svrg_step_pp(pnp_csmri_plan* plan, const void* a, const void* b, c
                            const double* gamma_pp, const void* c2, void* out, int denoise, double sigma_modifier,
                            const double* sigma_modifier_pp, double fallback_sigma, const void* xrec, double* sse_out,
                            void* sigma_out, void* stream);
+/* pnp_csmri_sarah_step with alpha_pp, gamma_pp, sigma_modifier_pp: converted as pnp_csmri_svrg_step_pp converts them.         */
+int pnp_csmri_sarah_step_pp(pnp_csmri_plan* plan, const void* a, const void* b, const uint32_t* bitsT, double alpha,
+                            const double* alpha_pp, const void* alpha_vec, double beta, const void* c1, double gamma,
+                            const double* gamma_pp, const void* c2, void* v_out, void* out, void* out2, int denoise,
+                            double sigma_modifier, const double* sigma_modifier_pp, double fallback_sigma, const void* xrec,
+                            double* sse_out, void* sigma_out, void* stream);
 int pnp_csmri_svrg_outer_step_pp(pnp_csmri_plan* plan, const void* z, const uint32_t* mask_bitsT, const void* yh,
                                  const void* alpha_vec, double lr, const double* lr_pp, void* w_out, void* mu_out, void* out,
                                  int denoise, double sigma_modifier, const double* sigma_modifier_pp, double fallback_sigma,

@@ -35,6 +35,7 @@ SIGNATURES = {
     'pnp_csmri_grad': (_i, [_vp, _vp, _vp, _vp, _vp, _d, _d, _vp, _d, _vp, _vp, _vp]),
     'pnp_csmri_grad_sel': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _vp, _d, _vp, _d, _vp, _vp, _vp]),
     'pnp_csmri_svrg_step': (_i, [_vp, _vp, _vp, _vp, _d, _vp, _d, _vp, _d, _vp, _vp, _i, _d, _d, _vp, _vp, _vp, _vp]),
+    'pnp_csmri_sarah_step': (_i, [_vp, _vp, _vp, _vp, _d, _vp, _d, _vp, _d, _vp, _vp, _vp, _vp, _i, _d, _d, _vp, _vp, _vp, _vp]),
     'pnp_csmri_svrg_outer_step': (_i, [_vp, _vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _i, _d, _d, _vp, _vp, _vp, _vp]),
     'pnp_csmri_svrg_outer_iteration': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _d, _i, _d, _d, _vp, _vp, _i, _i, _vp, _vp]),
     'pnp_deblur_plan_create': (_i, [ctypes.POINTER(_vp), _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
@@ -81,6 +82,7 @@ SIGNATURES = {
     'pnp_draw_thresholds_pp': (_i, [_i, _i, _vp, _vp, ctypes.c_uint64, ctypes.c_uint32, _i, _vp, _vp, _vp]),
     'pnp_csmri_grad_sel_pp': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _vp, _vp, _d, _vp, _d, _vp, _vp, _vp, _vp]),
     'pnp_csmri_svrg_step_pp': (_i, [_vp, _vp, _vp, _vp, _d, _vp, _vp, _d, _vp, _d, _vp, _vp, _vp, _i, _d, _vp, _d, _vp, _vp, _vp, _vp]),
+    'pnp_csmri_sarah_step_pp': (_i, [_vp, _vp, _vp, _vp, _d, _vp, _vp, _d, _vp, _d, _vp, _vp, _vp, _vp, _vp, _i, _d, _vp, _d, _vp, _vp, _vp, _vp]),
     'pnp_csmri_svrg_outer_step_pp': (_i, [_vp, _vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp, _i, _d, _vp, _d, _vp, _vp, _vp, _vp]),
     'pnp_csmri_svrg_outer_iteration_pp': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _d, _vp, _i, _vp, _d, _vp, _d, _vp, _vp, _i,
                                                _i, _vp, _vp]),

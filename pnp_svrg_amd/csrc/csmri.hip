@@ -342,6 +342,10 @@ int csmri_fused_span_launch(int batch, const void* twtab, void* z, void* w, void
                             double lr, const double* lr_pp, int mini_batch_size, const int32_t* mb_vec, double sigma_modifier,
                             const double* sm_pp, double fallback_sigma, const void* xrec, double* sse_log, int log_row0, int n_log,
                             void* sigma_out, void* stream);
+int csmri_sarah_launch(int batch, const void* twtab, const void* a, const void* b, const uint32_t* bitsT, double alpha,
+                       const void* alpha_vec, double beta, const void* c1, double gamma, const void* c2, void* v_out, void* out,
+                       void* out2, int mode, double sigma_modifier, double fallback_sigma, const void* xrec, double* sse_out,
+                       void* sigma_out, void* stream, const double* alpha_pp, const double* gamma_pp, const double* sm_pp);
 }
 
 namespace {
@@ -441,6 +445,38 @@ extern "C" int pnp_csmri_svrg_step_pp(pnp_csmri_plan* p, const void* a, const vo
     return csmri_fused_launch(p->batch, p->twtab, a, b, bitsT, nullptr, alpha, alpha_vec, beta, c1, gamma, c2, out, denoise ? 0 : 1,
                               sigma_modifier, fallback_sigma, xrec, sse_out, sigma_out, stream, nullptr, nullptr, alpha_pp, gamma_pp,
                               sigma_modifier_pp);
+}
+
+// ---- the SARAH form of the one-kernel iteration: v_out stored from the epilogue, then out = prox_TV(c2 + gamma * v_out), out2 = out
+static int sarah_step_impl(pnp_csmri_plan* p, const void* a, const void* b, const uint32_t* bitsT, double alpha, const double* alpha_pp,
+                           const void* alpha_vec, double beta, const void* c1, double gamma, const double* gamma_pp, const void* c2,
+                           void* v_out, void* out, void* out2, int denoise, double sigma_modifier, const double* sigma_modifier_pp,
+                           double fallback_sigma, const void* xrec, double* sse_out, void* sigma_out, void* stream) {
+    PNP_CHECK_ARG(p && a && b && bitsT && c1 && c2 && v_out && out, "null argument");
+    PNP_CHECK_ARG(!(sse_out && !xrec), "sse_out needs xrec");
+    PNP_CHECK_ARG(denoise || out2 == nullptr, "out2 needs denoise != 0 (without the prox the stored image is not the iterate)");
+    PNP_CHECK_ARG(v_out != a && v_out != b && v_out != c2 && v_out != out && v_out != out2,
+                  "v_out may alias c1 only (not a, b, c2, out or out2)");
+    PNP_CHECK_ARG(p->dtype == PNP_F32 && p->H == 256 && p->W == 256, "the one-kernel iteration exists for f32 plans of 256 x 256");
+    return csmri_sarah_launch(p->batch, p->twtab, a, b, bitsT, alpha, alpha_vec, beta, c1, gamma, c2, v_out, out, out2, denoise ? 0 : 1,
+                              sigma_modifier, fallback_sigma, xrec, sse_out, sigma_out, stream, alpha_pp, gamma_pp, sigma_modifier_pp);
+}
+
+extern "C" int pnp_csmri_sarah_step(pnp_csmri_plan* p, const void* a, const void* b, const uint32_t* bitsT, double alpha,
+                                    const void* alpha_vec, double beta, const void* c1, double gamma, const void* c2, void* v_out,
+                                    void* out, void* out2, int denoise, double sigma_modifier, double fallback_sigma, const void* xrec,
+                                    double* sse_out, void* sigma_out, void* stream) {
+    return sarah_step_impl(p, a, b, bitsT, alpha, nullptr, alpha_vec, beta, c1, gamma, nullptr, c2, v_out, out, out2, denoise,
+                           sigma_modifier, nullptr, fallback_sigma, xrec, sse_out, sigma_out, stream);
+}
+
+extern "C" int pnp_csmri_sarah_step_pp(pnp_csmri_plan* p, const void* a, const void* b, const uint32_t* bitsT, double alpha,
+                                       const double* alpha_pp, const void* alpha_vec, double beta, const void* c1, double gamma,
+                                       const double* gamma_pp, const void* c2, void* v_out, void* out, void* out2, int denoise,
+                                       double sigma_modifier, const double* sigma_modifier_pp, double fallback_sigma, const void* xrec,
+                                       double* sse_out, void* sigma_out, void* stream) {
+    return sarah_step_impl(p, a, b, bitsT, alpha, alpha_pp, alpha_vec, beta, c1, gamma, gamma_pp, c2, v_out, out, out2, denoise,
+                           sigma_modifier, sigma_modifier_pp, fallback_sigma, xrec, sse_out, sigma_out, stream);
 }
 
 // ---- the same with the outer-loop refresh folded in (first inner iteration of an outer iteration)

@@ -551,6 +551,49 @@ __device__ __forceinline__ void fused_gradient(RImg& R, const float* a, const fl
     }
 }
 
+// SARAH form (pnp_csmri_sarah_step), second epilogue stage.  On entry R = v_out = alpha * g + beta * c1, left by
+// fused_gradient<false, 1>, whose last wait was vmcnt(0): every load of c1 has landed, so v_out may alias c1.  v_out is recursion
+// state (algorithms/pnp_sarah.py:86): it is stored from here, in the R layout, BEFORE the second operand is folded in as
+// R <- c2 + gamma * R -- one fused multiply-add per element, the form of the OUTER epilogue.  Batches of two passes (8 pieces), two
+// in flight, as in `stage`; the 8 stores of a batch go out in front of its wait (they need nothing from it), so the order of issue
+// is   L0 L1 | S0 wait(L0) F0 L2 | S1 wait(L1) F1 L3 | S2 wait(L2) F2 | S3 wait(L3) F3   and behind a batch in the queue are
+//   L0: L1 S0 = 16;   L1: S0 L2 S1 = 24;   L2: S1 L3 S2 = 24;   L3: S2 S3 = 16.
+// out may alias c2: every piece of c2 is waited for here, the stores to out are issued in phase 5.
+__device__ __forceinline__ void sarah_epilogue(RImg& R, float gamma, const float* c2, float* v_out, int t) {
+    const RLane L(t);
+    f4 U[2][2][2][2];                                           // [buffer][pass of the batch][h2][row01]
+    gld_passes<2>(U[0], c2, 0, L.voff);
+    gld_passes<2>(U[1], c2, 2, L.voff);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        f4 v2[2][2][2];
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int h2 = 0; h2 < 2; ++h2)
+#pragma unroll
+                for (int q = 0; q < 2; ++q) v2[j][h2][q] = R[2 * k + j][h2][q];
+        gst_passes<2>(v_out, 2 * k, L.voff, v2);
+        if (k == 0 || k == 3) gwait<16, 2>(U[k & 1]);
+        else gwait<24, 2>(U[k & 1]);
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int h2 = 0; h2 < 2; ++h2)
+#pragma unroll
+                for (int q = 0; q < 2; ++q) {
+                    const f4 uv = U[k & 1][j][h2][q];
+                    f4& rv = R[2 * k + j][h2][q];
+                    rv = f4{fma_(gamma, rv.x, uv.x), fma_(gamma, rv.y, uv.y), fma_(gamma, rv.z, uv.z), fma_(gamma, rv.w, uv.w)};
+                }
+        // the batch is consumed before its buffer is requested again (see `stage`)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+            asm volatile("" : "+v"(R[2 * k + j][0][0]), "+v"(R[2 * k + j][0][1]), "+v"(R[2 * k + j][1][0]), "+v"(R[2 * k + j][1][1]));
+        if (k + 2 < 4) gld_passes<2>(U[k & 1], c2, 2 * (k + 2), L.voff);
+    }
+}
+
 }  // namespace pnp
 
 // everything from here on follows pywt / skimage product for product: no FMA contraction (exact zeros in the wavelet
@@ -587,13 +630,15 @@ __device__ __forceinline__ void startup_stagger(int stagger_n, int stagger_group
 
 // One whole iteration of one image (`a` ... `out`, `xrec`, `w_out`, `mu_out`: THIS image's arrays; sse_out / sigma_out: this
 // image's slots).  Whole-workgroup collective.
-template <int MODE, bool OUTER, int NOPS>
+// SARAH: 0 = the SVRG forms; 1 = the SARAH form (v_out stored from the epilogue, then c2 folded in: sarah_epilogue); 2 = the same with
+// a second destination out2 of the final store.  A template parameter like the others: the epilogue stays straight-line code.
+template <int MODE, bool OUTER, int NOPS, int SARAH = 0>
 __device__ __forceinline__ void svrg_iter_body(unsigned char* lds_raw, FusedShared& sh, const float* a, const float* b,
                                                const uint32_t* __restrict__ bits, const cx<float>* __restrict__ yh,
                                                const cx<float>* __restrict__ twtab, float scale, float beta, const float* c1,
                                                float gamma, const float* c2, float* oi, float sigma_modifier, float fallback_sigma,
                                                const float* xri, double* __restrict__ sse_out, float* __restrict__ sigma_out,
-                                               float* w_out, float* mu_out) {
+                                               float* w_out, float* mu_out, float* v_out = nullptr, float* out2 = nullptr) {
     constexpr bool DENOISE = MODE == FUSED_FULL;
     cx<float>* ldc = reinterpret_cast<cx<float>*>(lds_raw);
     float* ldf = reinterpret_cast<float*>(lds_raw);
@@ -612,7 +657,12 @@ __device__ __forceinline__ void svrg_iter_body(unsigned char* lds_raw, FusedShar
     PNP_STAMP(0);
     const RLane L(t);
     RImg R;
-    fused_gradient<OUTER, NOPS>(R, a, b, bits, twtab, twl, ldc, sbits, yh, scale, beta, c1, gamma, c2, t, g, l, w_out, mu_out PNP_STAMP_ARG);
+    if constexpr (SARAH != 0) {
+        // phases 1-3 and the first epilogue stage are the gradient-only instantiation's: R = alpha * g + beta * c1 = v_out
+        fused_gradient<false, 1>(R, a, b, bits, twtab, twl, ldc, sbits, yh, scale, beta, c1, 0.f, nullptr, t, g, l, nullptr, nullptr PNP_STAMP_ARG);
+        sarah_epilogue(R, gamma, c2, v_out, t);
+    } else
+        fused_gradient<OUTER, NOPS>(R, a, b, bits, twtab, twl, ldc, sbits, yh, scale, beta, c1, gamma, c2, t, g, l, w_out, mu_out PNP_STAMP_ARG);
     if (MODE == FUSED_GRAD) {
         gst_passes<8>(oi, 0, L.voff, R);
         return;
@@ -691,7 +741,9 @@ __device__ __forceinline__ void svrg_iter_body(unsigned char* lds_raw, FusedShar
                     for (int pass = 0; pass < 8; ++pass) asm volatile("" : "+v"(xa[pass][0][0][0]), "+v"(xa[pass][1][0][0]));
                     gt_load(xb, 1);
                 } else {
-                    asm volatile("s_waitcnt vmcnt(16)" ::: "memory");   // behind xb in the queue: the first half's 16 stores
+                    // behind xb in the queue: the first half's 16 stores (SARAH with out2: 16 more to out2)
+                    if constexpr (SARAH == 2) asm volatile("s_waitcnt vmcnt(32)" ::: "memory");
+                    else asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
 #pragma unroll
                     for (int pass = 0; pass < 8; ++pass) asm volatile("" : "+v"(xb[pass][0][0][0]), "+v"(xb[pass][1][0][0]));
                 }
@@ -714,6 +766,10 @@ __device__ __forceinline__ void svrg_iter_body(unsigned char* lds_raw, FusedShar
                 }
                 if (h2 == 0) { gst<0>(oi + pass * 8192, L.voff, v[0]); gst<1024>(oi + pass * 8192, L.voff, v[1]); }
                 else { gst<512>(oi + pass * 8192, L.voff, v[0]); gst<1536>(oi + pass * 8192, L.voff, v[1]); }
+                if constexpr (SARAH == 2) {                         // the second destination of the final store (w_prev <- z)
+                    if (h2 == 0) { gst<0>(out2 + pass * 8192, L.voff, v[0]); gst<1024>(out2 + pass * 8192, L.voff, v[1]); }
+                    else { gst<512>(out2 + pass * 8192, L.voff, v[0]); gst<1536>(out2 + pass * 8192, L.voff, v[1]); }
+                }
             }
             err += (double)e;
             PNP_STAMP_NW(11 + 2 * h2);
@@ -926,6 +982,56 @@ __global__ __launch_bounds__(FT) void k_svrg_span_pp(float* z, float* w, float* 
     }
 }
 
+// The SARAH form of the one-kernel iteration (pnp_csmri_sarah_step; algorithms/pnp_sarah.py:72-104 with a = w_next, b = w_prev,
+// c1 = v_prev, c2 = z):   v_out = alpha * alpha_vec[b] * Re ifft2(sel o fft2(a - b)) + beta * c1   (stored, R layout),
+// out = prox_TV(c2 + gamma * v_out), out2 = out.  MODE: FUSED_FULL / FUSED_NO_DENOISE (stores c2 + gamma * v_out); OUT2: the second
+// destination is present.  No data term: grad_stoch is affine, the Y terms of the difference cancel.
+template <int MODE, bool OUT2>
+__global__ __launch_bounds__(FT) void k_sarah_iter(const float* a, const float* b, const uint32_t* __restrict__ bitsT,
+                                                   const cx<float>* __restrict__ twtab, float scale,
+                                                   const float* __restrict__ alpha_vec, float beta, const float* c1, float gamma,
+                                                   const float* c2, float* v_out, float* out, float* out2, float sigma_modifier,
+                                                   float fallback_sigma, const float* __restrict__ xrec, double* __restrict__ sse_out,
+                                                   float* __restrict__ sigma_out, int stagger_n, int stagger_groups, int stagger_units) {
+    startup_stagger(stagger_n, stagger_groups, stagger_units);
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    __shared__ FusedShared sh;
+    const int prob = blockIdx.x;
+    const size_t img = (size_t)prob * FN * FN;
+    if (alpha_vec != nullptr) scale *= alpha_vec[prob];
+    svrg_iter_body<MODE, false, 2, OUT2 ? 2 : 1>(lds_raw, sh, a + img, b + img, bitsT + (size_t)prob * FN * 8, nullptr, twtab, scale, beta,
+                                                 c1 + img, gamma, c2 + img, out + img, sigma_modifier, fallback_sigma,
+                                                 xrec != nullptr ? xrec + img : nullptr, sse_out != nullptr ? sse_out + prob : nullptr,
+                                                 sigma_out != nullptr ? sigma_out + prob : nullptr, nullptr, nullptr, v_out + img,
+                                                 OUT2 ? out2 + img : nullptr);
+}
+
+// pnp_csmri_sarah_step_pp: alpha_pp, gamma_pp, sm_pp as in k_svrg_iter_pp, converted expression for expression as there.
+template <int MODE, bool OUT2>
+__global__ __launch_bounds__(FT) void k_sarah_iter_pp(const float* a, const float* b, const uint32_t* __restrict__ bitsT,
+                                                      const cx<float>* __restrict__ twtab, float scale,
+                                                      const float* __restrict__ alpha_vec, float beta, const float* c1, float gamma,
+                                                      const float* c2, float* v_out, float* out, float* out2, float sigma_modifier,
+                                                      float fallback_sigma, const float* __restrict__ xrec, double* __restrict__ sse_out,
+                                                      float* __restrict__ sigma_out, int stagger_n, int stagger_groups, int stagger_units,
+                                                      const double* __restrict__ alpha_pp, const double* __restrict__ gamma_pp,
+                                                      const double* __restrict__ sm_pp) {
+    startup_stagger(stagger_n, stagger_groups, stagger_units);
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    __shared__ FusedShared sh;
+    const int prob = blockIdx.x;
+    const size_t img = (size_t)prob * FN * FN;
+    if (alpha_pp != nullptr) scale = (float)(alpha_pp[prob] * (1.0 / ((double)FN * (double)FN)));
+    if (alpha_vec != nullptr) scale *= alpha_vec[prob];
+    if (gamma_pp != nullptr) gamma = (float)gamma_pp[prob];
+    if (sm_pp != nullptr) sigma_modifier = (float)sm_pp[prob];
+    svrg_iter_body<MODE, false, 2, OUT2 ? 2 : 1>(lds_raw, sh, a + img, b + img, bitsT + (size_t)prob * FN * 8, nullptr, twtab, scale, beta,
+                                                 c1 + img, gamma, c2 + img, out + img, sigma_modifier, fallback_sigma,
+                                                 xrec != nullptr ? xrec + img : nullptr, sse_out != nullptr ? sse_out + prob : nullptr,
+                                                 sigma_out != nullptr ? sigma_out + prob : nullptr, nullptr, nullptr, v_out + img,
+                                                 OUT2 ? out2 + img : nullptr);
+}
+
 // stagger (see startup_stagger): only launches of more than one workgroup per CU pay for it and profit from it
 static int stagger_config(int* num_cu_out, int* groups, int* units) {
     static int num_cu = 0, st_groups = 2, st_units = 40;    // same-box sweep (tools/dev/stagger_sweep.py): 0.588 ms per config-2 step without, 0.575 with (2, 40), slower from (8, 20) on
@@ -1052,6 +1158,44 @@ int csmri_fused_launch(int batch, const void* twtab, const void* a, const void* 
 #undef PNP_FUSED_BY_NOPS
 #undef PNP_FUSED_LAUNCH
 #undef PNP_FUSED_ARGS
+    PNP_CHECK_LAUNCH();
+    return PNP_OK;
+}
+
+// the SARAH form (pnp_csmri_sarah_step[_pp]); mode: FUSED_FULL / FUSED_NO_DENOISE; out2 may be NULL; scale and casts as csmri_fused_launch
+int csmri_sarah_launch(int batch, const void* twtab, const void* a, const void* b, const uint32_t* bitsT, double alpha,
+                       const void* alpha_vec, double beta, const void* c1, double gamma, const void* c2, void* v_out, void* out,
+                       void* out2, int mode, double sigma_modifier, double fallback_sigma, const void* xrec, double* sse_out,
+                       void* sigma_out, void* stream, const double* alpha_pp, const double* gamma_pp, const double* sm_pp) {
+    const float scale = (float)(alpha / ((double)FN * (double)FN));
+    const bool pp = alpha_pp != nullptr || gamma_pp != nullptr || sm_pp != nullptr;
+    hipStream_t s = (hipStream_t)stream;
+    int num_cu = 0, st_groups = 0, st_units = 0;
+    { const int rc = stagger_config(&num_cu, &st_groups, &st_units); if (rc != PNP_OK) return rc; }
+    const int stagger_units = batch > num_cu ? st_units : 0;
+    {   // > 64 KiB of dynamic LDS needs the opt-in, once per device (as fused_lds_optin)
+        static unsigned long long attr_done = 0;
+        int dev = 0;
+        PNP_CHECK_HIP(hipGetDevice(&dev));
+        if (!((attr_done >> (dev & 63)) & 1ull)) {
+#define PNP_SARAH_ATTR(K, ...) PNP_CHECK_HIP(hipFuncSetAttribute((const void*)K<__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F_LDS_BYTES))
+            PNP_SARAH_ATTR(k_sarah_iter, 0, false); PNP_SARAH_ATTR(k_sarah_iter, 0, true); PNP_SARAH_ATTR(k_sarah_iter, 1, false);
+            PNP_SARAH_ATTR(k_sarah_iter_pp, 0, false); PNP_SARAH_ATTR(k_sarah_iter_pp, 0, true); PNP_SARAH_ATTR(k_sarah_iter_pp, 1, false);
+#undef PNP_SARAH_ATTR
+            attr_done |= 1ull << (dev & 63);
+        }
+    }
+#define PNP_SARAH_ARGS (const float*)a, (const float*)b, bitsT, (const cx<float>*)twtab, scale, (const float*)alpha_vec, (float)beta,   \
+                       (const float*)c1, (float)gamma, (const float*)c2, (float*)v_out, (float*)out, (float*)out2, (float)sigma_modifier, \
+                       (float)fallback_sigma, (const float*)xrec, sse_out, (float*)sigma_out, num_cu, st_groups, stagger_units
+#define PNP_SARAH_LAUNCH(...)                                                                                             \
+    do { if (pp) k_sarah_iter_pp<__VA_ARGS__><<<batch, FT, F_LDS_BYTES, s>>>(PNP_SARAH_ARGS, alpha_pp, gamma_pp, sm_pp);    \
+         else k_sarah_iter<__VA_ARGS__><<<batch, FT, F_LDS_BYTES, s>>>(PNP_SARAH_ARGS); } while (0)
+    if (mode != FUSED_FULL) PNP_SARAH_LAUNCH(1, false);
+    else if (out2 != nullptr) PNP_SARAH_LAUNCH(0, true);
+    else PNP_SARAH_LAUNCH(0, false);
+#undef PNP_SARAH_LAUNCH
+#undef PNP_SARAH_ARGS
     PNP_CHECK_LAUNCH();
     return PNP_OK;
 }

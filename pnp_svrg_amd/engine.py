@@ -24,6 +24,9 @@ SarahEngine takes `eta`, `mini_batch_size` and `draw_id` per problem as well (DE
 `pnp_axpbypcz_pp` launch each (`ops.axpbypcz` with a [B] coefficient), its difference of minibatch gradients takes 1 / mb per problem.
 The same launch carries every per-problem combine `g + beta * c1 + gamma * c2` of the Deblur and PR batches and the step of
 SvrgEngine(variant='reference').
+SarahEngine(fused=True) (opt-in) runs an inner iteration as ONE `pnp_csmri_sarah_step` and the outer step as ONE
+`pnp_csmri_svrg_outer_step` on a float32 256 x 256 CsmriBatch, and offers `capture()` / `run_outer(n)`; without it the engine makes
+exactly the calls it always made.
 SvrgEngine takes `T2` per problem as well: a [B] integer array makes problem b refresh mu and w at the steps with
 s % T2[b] == 0 -- one `pnp_refresh_pp` launch behind a full gradient at the steps where any problem refreshes -- and `run_span(n)`
 runs n steps in launches of `pnp_csmri_svrg_span_pp` where the one-kernel iteration holds the TV prox.  A scalar T2 takes exactly
@@ -105,6 +108,30 @@ class LoopEngine:
         if not self.log_objective:
             raise ValueError('objective_log() needs an engine made with log_objective=True')
         return self._ring(self.obj_log).cpu().numpy()
+
+    def _capture_graph(self, body, state):
+        """`body` (the launches of one outer iteration) captured into a hipGraph (torch.cuda.CUDAGraph on ROCm): a warm-up pass on a
+        side stream, then the capture.  `state` (the tensors `body` writes) and the prox's call counter are restored, also when the
+        capture fails.  The one capture site of the engines."""
+        keep = [t.clone() for t in state]
+        t_keep = getattr(self.prox, 't', None)
+        try:
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                body()                                          # warm-up outside capture (lazy module loads)
+            torch.cuda.current_stream().wait_stream(side)
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with ops.collector_held(), torch.cuda.graph(g):     # (no plan may be destroyed, hipFree, while the stream captures)
+                body()
+            torch.cuda.synchronize()
+        finally:
+            for dst, src in zip(state, keep):
+                dst.copy_(src)
+            if t_keep is not None:
+                self.prox.t = t_keep
+        return g
 
     def psnr_trace(self):
         """[prox evaluations][B] PSNR (rounded to 0.01 dB like problems/problem.py:33-35) in chronological order,
@@ -409,26 +436,11 @@ class SvrgEngine(_StochEngine):
         if not (self.s % self.T2 == 0 and self.n_prox == self.s):
             raise ValueError('capture() needs a step count that is a multiple of T2')
         self._set_dev_step(self.s)
-        keep = (self.z.clone(), self.w.clone(), self.mu.clone(), self.sse_log.clone(), self.step_dev.clone())
-        t_keep = getattr(self.prox, 't', None)
-        z_obj = self.z
+        state = (self.z, self.w, self.mu, self.sse_log, self.step_dev)
         try:
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                self._outer_body()                              # warm-up outside capture (lazy module loads)
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with ops.collector_held(), torch.cuda.graph(g):     # (no plan may be destroyed, hipFree, while the stream captures)
-                self._outer_body()
-            torch.cuda.synchronize()
+            g = self._capture_graph(self._outer_body, state)
         finally:
-            self.z = z_obj
-            for dst, src in zip((self.z, self.w, self.mu, self.sse_log, self.step_dev), keep):
-                dst.copy_(src)
-            if t_keep is not None:
-                self.prox.t = t_keep
+            self.z = state[0]
         self.graph = g
         return g
 
@@ -484,19 +496,61 @@ class SarahEngine(_StochEngine):
     """pnp_sarah over a batch (algorithms/pnp_sarah.py:28-104) with the quirks of v1: the outer step
     `w_next = prox(w_prev - eta * grad_full(z))` is logged but never adopted by z, w_next stays fixed through the
     inner loop, and the outer step ignores lr_decay.  One log row per prox: outer rows at s % T2 == 0.
-    eta, mini_batch_size: scalars, or [B] arrays on a batch that takes them per problem; draw_id as in SgdEngine."""
+    eta, mini_batch_size: scalars, or [B] arrays on a batch that takes them per problem; draw_id as in SgdEngine.
+    fused=True (opt-in): the one-kernel forms -- the outer step is ONE pnp_csmri_svrg_outer_step (w_prev, v_prev and
+    w_next are its three outputs), an inner iteration ONE pnp_csmri_sarah_step that updates v_prev, z and w_prev where they lie.
+    Needs a float32 256 x 256 CsmriBatch, a TV or DnCNN prox and log_objective=False; `capture()` / `run_outer(n)` then replay
+    one outer iteration (T2 + 1 log rows) as a hipGraph."""
 
-    def __init__(self, batch, prox, eta, T2, mini_batch_size, lr_decay=1.0, n_log=4096, seed=0, draw_id=None, log_objective=False):
+    def __init__(self, batch, prox, eta, T2, mini_batch_size, lr_decay=1.0, n_log=4096, seed=0, draw_id=None, log_objective=False,
+                 *, fused=False):
         if np.ndim(T2) != 0:
             raise ValueError('SarahEngine takes a scalar T2 (its outer prox logs a row of its own: rows would stop lining up)')
-        super().__init__(batch, prox, eta, mini_batch_size, lr_decay, n_log, seed, draw_id=draw_id, log_objective=log_objective)
+        self.fused = bool(fused)
+        if self.fused:
+            missing = []
+            if getattr(batch, 'kind', None) != 'csmri':
+                missing.append(f'a CsmriBatch (got {getattr(batch, "kind", type(batch).__name__)!r})')
+            else:
+                if batch.dtype != torch.float32:
+                    missing.append(f'float32 (got {batch.dtype})')
+                if (batch.H, batch.W) != (256, 256):
+                    missing.append(f'256 x 256 images (got {batch.H} x {batch.W})')
+            if not hasattr(prox, 'fused_args'):
+                missing.append(f'a prox with fused_args: TVProx or DnCNNProx (got {type(prox).__name__})')
+            if log_objective:
+                missing.append('log_objective=False')
+            if missing:
+                raise ValueError('SarahEngine(fused=True) needs ' + ', '.join(missing))
+        # fused: the draws of a whole outer iteration are ONE launch at the outer step (T2 selector slots, as SvrgEngine)
+        super().__init__(batch, prox, eta, mini_batch_size, lr_decay, n_log, seed, n_slots=T2 if self.fused else None, draw_id=draw_id,
+                         log_objective=log_objective)
         self.T2 = T2
         self.w_prev = torch.empty_like(self.z)
         self.w_next = torch.empty_like(self.z)
         self.v_prev = torch.empty_like(self.z)
-        self.v_next = torch.empty_like(self.z)
+        if not self.fused:
+            self.v_next = torch.empty_like(self.z)
+            return
+        self._hostbits = None
+        dev = batch.xrec.device
+        # the hipGraph form's device-resident counters and scratch row (as SvrgEngine's).  Two counters: the draws are keyed on the
+        # step count, the log on the row count -- an outer iteration appends T2 + 1 rows (log_append_inc: append and count, one launch)
+        self.row_dev = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.step_dev = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._dev_step = 0
+        self.sse_tmp = torch.zeros(batch.B, dtype=torch.float64, device=dev)
+
+    def reset(self):
+        super().reset()
+        if self.fused:
+            self.row_dev.zero_()
+            self.step_dev.zero_()
+            self._dev_step = 0
 
     def step(self, idx_s=None):
+        if self.fused:
+            return self._step_fused(idx_s)
         b, s = self.b, self.s
         if s % self.T2 == 0:
             self.w_prev.copy_(self.z)
@@ -514,6 +568,104 @@ class SarahEngine(_StochEngine):
         self.v_prev, self.v_next = self.v_next, self.v_prev
         self.w_prev.copy_(self.z)
         self.s += 1
+
+    # ---- the one-kernel forms (fused=True)
+    def _step_fused(self, idx_s):
+        b, s = self.b, self.s
+        j, k = s % self.T2, s // self.T2
+        if j == 0:
+            if idx_s is None:
+                b.draw(self.mbs, self._mb_draw, self.seed, s, self.T2, **self._draw_kw)
+            self._fused_outer(self.sse_log[self.n_prox % self.n_log])
+            self.n_prox += 1
+        if idx_s is not None:
+            b.set_host(self.mbs, j, idx_s)
+        elif self.mbs.host[j] is not None:                      # a host-fed outer iteration continued with device draws
+            self._draw_slot(j, s)
+        self._fused_inner(j, self.eta * self.lr_decay ** k, k, self.sse_log[self.n_prox % self.n_log])
+        self.n_prox += 1
+        self.s += 1
+
+    def _fused_outer(self, sse_out):
+        """w_prev = z, v_prev = grad_full(z), w_next = prox(z - eta * v_prev) in one kernel (pnp_csmri_svrg_outer_step with
+        out = w_next); z is not touched (the outer step is logged, never adopted), and eta does not decay here (F6)."""
+        b, px = self.b, self.prox
+        b.plan.svrg_outer_step(self.z, b.bits, b.yh_full, b.inv_m0, self._c('eta', 0, self.eta), self.w_prev, self.v_prev,
+                               out=self.w_next, denoise=px.fused_denoise, xrec=b.xrec, sse=sse_out if px.fused_denoise else None,
+                               **px.fused_args())
+        px.after_fused(self.w_next, b.xrec, sse_out)
+
+    def _fused_inner(self, j, lr, k, sse_out):
+        """v_prev <- v_next, z <- prox(z - lr * v_next), w_prev <- z in one kernel (pnp_csmri_sarah_step), all three in place; with
+        a prox that follows the kernel (DnCNN, the 2-D wavelet prox) the copy to w_prev follows the prox."""
+        b, px = self.b, self.prox
+        if self.mbs.host[j] is not None:                        # host-drawn selector: pack it to bits (a 5 us launch)
+            self._hostbits = b.plan.pack_mask(self.mbs.host[j], out=self._hostbits)
+            bits = self._hostbits
+        else:
+            bits = self.mbs.selbits[j]
+        den = px.fused_denoise
+        b.plan.sarah_step(self.w_next, self.w_prev, bits, alpha=self._c('1/mb', 0, 1.0 / self.mb), beta=1.0, c1=self.v_prev,
+                          gamma=self._c('-lr', k, -lr), c2=self.z, v_out=self.v_prev, out=self.z, out2=self.w_prev if den else None,
+                          denoise=den, xrec=b.xrec, sse=sse_out if den else None, **px.fused_args())
+        if not den:
+            px.after_fused(self.z, b.xrec, sse_out)
+            self.w_prev.copy_(self.z)
+
+    # ---- hipGraph form of the fused path: one OUTER iteration (outer step + T2 inner iterations, T2 + 1 log rows) = one graph launch
+    def _outer_body(self):
+        b = self.b
+        self._fused_outer(self.sse_tmp)
+        ops.log_append_inc(self.sse_tmp, self.sse_log, self.row_dev)
+        b.draw(self.mbs, self._mb_draw, self.seed, 0, self.T2, step_dev=self.step_dev, **self._draw_kw)
+        for j in range(self.T2):
+            self._fused_inner(j, self.eta, 0, self.sse_tmp)     # (graph_ok: lr_decay == 1)
+            ops.log_append_inc(self.sse_tmp, self.sse_log, self.row_dev)
+            ops.counter_add(self.step_dev, 1)
+
+    def graph_ok(self):
+        """Whether one outer iteration of this engine can be captured: the fused path (the streaming path swaps buffers and may get
+        fresh tensors from its prox), constant step size, an in-place prox without host-side per-call state, device draws."""
+        return (self.fused and self.lr_decay == 1.0 and getattr(self.prox, 'inplace', False)
+                and getattr(self.prox, 'denoise_strength', 0.0) == 0.0 and not self.log_objective
+                and all(h is None for h in self.mbs.host))
+
+    def capture(self):
+        """Capture one outer iteration into a hipGraph.  Needs `graph_ok()` and a step count that is a multiple of T2.  State is left
+        untouched, also when the capture fails."""
+        if not self.graph_ok():
+            raise ValueError('this SarahEngine cannot be captured in a hipGraph (needs fused=True, lr_decay == 1, device-drawn '
+                             'minibatches and an in-place prox without host-side per-call state: TVProx with denoise_strength == 0 '
+                             'or DnCNNProx); step it eagerly')
+        if not (self.s % self.T2 == 0 and self.n_prox == self.s + self.s // self.T2):
+            raise ValueError('capture() needs a step count that is a multiple of T2')
+        self._set_dev_step()
+        g = self._capture_graph(self._outer_body, (self.z, self.w_prev, self.w_next, self.v_prev, self.sse_log, self.row_dev, self.step_dev))
+        self.graph = g
+        return g
+
+    def _set_dev_step(self):
+        """The device-resident counters are brought up to date only when a graph is about to read them."""
+        if self._dev_step != self.s:
+            self.step_dev.fill_(self.s)
+            self.row_dev.fill_(self.n_prox % self.n_log)
+            self._dev_step = self.s
+
+    def run_outer(self, n_outer=1):
+        """n_outer outer iterations = n_outer * T2 inner iterations (n_outer * (T2 + 1) log rows) as replays of the captured
+        hipGraph, from a step count that is a multiple of T2 -- the same bits as stepping."""
+        if self.graph is None:
+            self.capture()
+        if not (self.s % self.T2 == 0 and self.n_prox == self.s + self.s // self.T2):
+            raise ValueError('run_outer() needs a step count that is a multiple of T2')
+        self._set_dev_step()
+        for _ in range(n_outer):
+            self.graph.replay()
+            self.s += self.T2
+            self.n_prox += self.T2 + 1
+            if hasattr(self.prox, 't'):
+                self.prox.t += self.T2 + 1
+        self._dev_step = self.s
 
 
 class SagaEngine(_StochEngine):

@@ -243,6 +243,32 @@ class CsmriPlan:
                                        float(fallback_sigma), _p(xrec), _p(sse), _p(sigma_out), _stream()])
         return out, sse, sigma_out
 
+    def sarah_step(self, a, b, bits, alpha=1.0, beta=1.0, c1=None, gamma=0.0, c2=None, v_out=None, out=None, out2=None, *,
+                   alpha_vec=None, denoise=True, sigma_modifier=1.0, fallback_sigma=0.0, xrec=None, sse=None, sigma_out=None):
+        """pnp_csmri_sarah_step: one inner iteration of pnp_sarah in ONE kernel (f32, 256 x 256):
+        v_out = alpha * Re ifft2(bits o fft2(a - b)) + beta*c1 (stored), out = prox_TV(c2 + gamma * v_out), out2 = out.
+        v_out may be c1, out may be c2, out2 may be b; denoise=False stores c2 + gamma * v_out and takes no out2.
+        Returns (out, sse, sigma_out, v_out)."""
+        if self.dtype != torch.float32 or self.H != 256 or self.W != 256:
+            raise ValueError(f'sarah_step: the one-kernel iteration exists for float32 plans of 256 x 256 (this plan: {self.dtype}, '
+                             f'{self.H} x {self.W})')
+        if out2 is not None and not denoise:
+            raise ValueError('sarah_step: out2 needs denoise=True (without the prox the stored image is not the iterate)')
+        assert bits.dtype == torch.int32 and tuple(bits.shape) == (self.B, self.W, self.H // 32)
+        assert c1 is not None and c2 is not None, 'sarah_step: c1 (v_prev) and c2 (z) are required'
+        for t in (a, b, c1, c2, v_out, out, out2, xrec):
+            assert t is None or (t.dtype == self.dtype and t.numel() == self.B * self.H * self.W)
+        out = out if out is not None else torch.empty_like(a)
+        v_out = v_out if v_out is not None else torch.empty_like(a)
+        if any(v_out.data_ptr() == t.data_ptr() for t in (a, b, c2, out, out2) if t is not None):
+            raise ValueError('sarah_step: v_out may alias c1 only (not a, b, c2, out or out2)')
+        sigma_out = sigma_out if sigma_out is not None else torch.empty(self.B, dtype=a.dtype, device=a.device)
+        _route('pnp_csmri_sarah_step', [self._h, _p(a), _p(b), _p(bits), _pp(alpha, self.B), _p(alpha_vec), float(beta), _p(c1),
+                                        _pp(gamma, self.B), _p(c2), _p(v_out), _p(out), _p(out2), 1 if denoise else 0,
+                                        _pp(sigma_modifier, self.B), float(fallback_sigma), _p(xrec), _p(sse), _p(sigma_out),
+                                        _stream()])
+        return out, sse, sigma_out, v_out
+
     def svrg_outer_step(self, z, mask_bits, yh, alpha_vec, lr, w_out, mu_out, out=None, *, denoise=True, sigma_modifier=1.0,
                         fallback_sigma=0.0, xrec=None, sse=None, sigma_out=None):
         """pnp_csmri_svrg_outer_step: the outer refresh of pnp_svrg folded into its first inner iteration, one kernel:

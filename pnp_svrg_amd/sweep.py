@@ -153,7 +153,7 @@ def make_prox(denoiser, **kw):
 def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta, n_inner, mini_batch_size=None, T2=None,
                 hist_size=50, H=256, W=256, dtype=torch.float32, max_batch=128, seeding='generator', variant='svrg', run_seed=1,
                 keep_trace=False, graph=True, kernel='Minimal', lr_decay=1.0, denoiser_kwargs=None, sigma_modifier=None,
-                shared_matrix=False, wide_trials=False, sarah_trials=False, t2_trials=False, objective=False):
+                shared_matrix=False, wide_trials=False, sarah_trials=False, t2_trials=False, objective=False, sarah_fused=False):
     """Runner for `run_sweep` / `grid_search` over any cell of the reference's sweep (script_diff_sampratio_set12.py:23-25,
     41-51, 64-131): problem in {'csmri', 'deblur', 'pr'} x algorithm in {'gd', 'sgd', 'svrg', 'saga', 'sarah'} x denoiser in
     {'tv', 'nlm', factory}; `n_inner` inner iterations (prox evaluations of the stepped iterate) per item, hyper-parameters
@@ -196,6 +196,10 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
     DESIGN 10; such engines step eagerly): result rows gain 'f_final' (f of the last logged iterate) and, with keep_trace=True,
     'f_trace' (one value per 'psnr_trace' entry); trial-batched runs carry it through.  False (default): rows, engines and launches
     are exactly what they were.  Anything but a bool is a ValueError.
+    sarah_fused: opt in to the one-kernel forms of pnp_sarah (SarahEngine(fused=True)): problem='csmri', algorithm='sarah',
+    float32 256 x 256 and the 'tv' denoiser or a DnCNN prox factory -- anything else is a ValueError that names the offender.  Goes
+    together with sarah_trials=True; batches with device-drawn minibatches replay whole outer iterations as hipGraphs.  False
+    (default): engines, launches, rows and messages are exactly what they were.
     Beside `run(items)` the runner offers the pieces of a trial-batched grid (`grid_search(batch_trials=True)`):
     `run.prepare_data(items)` builds a rank's batches WITHOUT engines, `run.run_trials(data, trials, max_batch_trials)` runs a list
     of trials ({'eta', 'mini_batch_size', 'sigma_modifier'} overrides) on them as tiled batches, `run.data_key` says which runners
@@ -212,7 +216,22 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
         raise ValueError(f"seeding='device' is supported for problem='csmri' only (got {problem!r}); use 'generator' or 'legacy'")
     if not isinstance(objective, (bool, np.bool_)):
         raise ValueError(f'objective: True or False, got {objective!r}')
-    obj_kw = {'log_objective': True} if objective else {}       # (off: the engines are made with the arguments they always got)
+    if not isinstance(sarah_fused, (bool, np.bool_)):
+        raise ValueError(f'sarah_fused: True or False, got {sarah_fused!r}')
+    if sarah_fused:
+        if problem != 'csmri':
+            raise ValueError(f"sarah_fused=True is for problem='csmri' (got {problem!r}): the one-kernel iteration is a CSMRI kernel")
+        if algorithm != 'sarah':
+            raise ValueError(f"sarah_fused=True is for algorithm='sarah' (got {algorithm!r})")
+        if dtype != torch.float32 or (H, W) != (256, 256):
+            raise ValueError(f'sarah_fused=True needs float32 images of 256 x 256 (got {dtype}, H = {H}, W = {W})')
+        if not (denoiser == 'tv' or callable(denoiser)):
+            raise ValueError(f"sarah_fused=True needs the 'tv' denoiser or a DnCNN prox factory (got {denoiser!r})")
+        if objective:
+            raise ValueError('sarah_fused=True needs objective=False (the one-kernel forms do not log the objective)')
+    eng_kw = {'log_objective': True} if objective else {}       # (off: the engines are made with the arguments they always got)
+    if sarah_fused:
+        eng_kw = dict(eng_kw, fused=True)                       # (rides with the other opt-in engine keyword)
     if shared_matrix and problem != 'pr':
         raise ValueError(f"shared_matrix=True is for problem='pr' (got {problem!r}): only its problems have a matrix to share")
     mb, dkw = mini_batch_size, dict(denoiser_kwargs or {})
@@ -317,7 +336,7 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
             if algorithm == 'saga' and self.idx_d is not None:
                 kw['idx0'] = self.idx_d[0]
             self.eng = E.make_engine(self.batch, make_prox(denoiser, **dkw), eta, T2, mb, lr_decay=lr_decay, variant=variant,
-                                     algorithm=algorithm, hist_size=hist_size, **kw, **obj_kw)
+                                     algorithm=algorithm, hist_size=hist_size, **kw, **eng_kw)
             self.done = 0
 
         def advance(self, n):
@@ -382,7 +401,7 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
             self.eng = E.make_engine(self.batch, make_prox(denoiser, **pkw), lay['eta'], lay['T2'] if per_t2 else T2,
                                      None if algorithm == 'gd' else lay['mini_batch_size'], lr_decay=lr_decay, variant=variant,
                                      algorithm=algorithm, hist_size=hist_size, seed=base.items[0]['id'] + 1, draw_id=lay['draw_id'],
-                                     **obj_kw)
+                                     **eng_kw)
 
     def _group_chunks(items):
         groups = {}

@@ -12,6 +12,10 @@ this script verifies on the ISA of every k_svrg_iter instantiation that
 
     python tools/check_fused_isa.py [listing.s]        (without argument: compiles csmri_fused.hip with hipcc -S first)
     python tools/check_fused_isa.py --pp [listing.s]   ... and the per-problem loops k_svrg_outer_pp and k_svrg_span_pp as well
+    python tools/check_fused_isa.py --sarah [listing.s]   the SARAH instantiations instead (k_sarah_iter, k_sarah_iter_pp: plain and _pp,
+                                                          denoise on and off, with and without out2), the same rule -- and for every
+                                                          hand-issued store (`s_nop 4` in front of a global_store_dwordx4) the wait
+                                                          state behind it: its data registers may be rewritten by the next instruction
 
 Also prints, per kernel, the spill traffic between workgroup barriers (where the register pressure bites)."""
 import re
@@ -37,9 +41,12 @@ def regs_of(text):
     return out
 
 
-def kernels(txt, pp=False):
-    """(name, body) of every k_svrg_iter instantiation and of k_svrg_outer; pp: also k_svrg_outer_pp and k_svrg_span_pp"""
+def kernels(txt, pp=False, sarah=False):
+    """(name, body) of every k_svrg_iter instantiation and of k_svrg_outer; pp: also k_svrg_outer_pp and k_svrg_span_pp;
+    sarah: the k_sarah_iter and k_sarah_iter_pp instantiations instead"""
     names = ('_ZN3pnp11k_svrg_iter', '_ZN3pnp12k_svrg_outer') + (('_ZN3pnp15k_svrg_outer_pp', '_ZN3pnp14k_svrg_span_pp') if pp else ())
+    if sarah:
+        names = ('_ZN3pnp12k_sarah_iter', '_ZN3pnp15k_sarah_iter_pp')
     lines = txt.split('\n')
     i = 0
     while i < len(lines):
@@ -138,19 +145,40 @@ def check(name, body):
     return errors, n_loads, n_waits, segs
 
 
+def check_stores(name, body):
+    """Every hand-issued store (gst: `s_nop 4`, global_store_dwordx4, `s_nop 1`) keeps the wait state behind it: the hazard
+    recognizer does not pad inside inline asm, and the next instruction may rewrite the store's data registers."""
+    code = [c for c in (raw.split(';')[0].strip() for raw in body) if c and not c.startswith('.')]
+    errors, n = [], 0
+    for i, c in enumerate(code):
+        if c.startswith('global_store_dwordx4') and i > 0 and code[i - 1] == 's_nop 4':
+            n += 1
+            nxt = code[i + 1] if i + 1 < len(code) else ''
+            m = re.match(r's_nop (\d+)$', nxt)
+            if not (m and int(m.group(1)) >= 1):
+                errors.append(f'{name}: hand-issued store `{c}` is followed by `{nxt}`, not by its wait state (s_nop 1)')
+    return errors, n
+
+
 def main():
     args = sys.argv[1:]
     defines = [a for a in args if a.startswith('-D')]          # e.g. -DPNP_FUSED_CLOCK: the diagnostic build
     pp = '--pp' in args                                         # also the per-problem loops: k_svrg_outer_pp, k_svrg_span_pp
+    sarah = '--sarah' in args                                   # the SARAH instantiations instead, with the store rule
     paths = [a for a in args if not a.startswith('-')]
     txt = listing(paths[0] if paths else None, defines)
     bad = []
     nk = 0
-    for name, body in kernels(txt, pp):
+    for name, body in kernels(txt, pp, sarah):
         nk += 1
         errors, n_loads, n_waits, segs = check(name, body)
         spill = ' '.join(f'{i}:{s["sst"]}/{s["sld"]}' for i, s in enumerate(segs) if s['sst'] or s['sld'])
-        print(f'{name[:40]}...: {n_loads} hand-issued loads, {n_waits} vmcnt waits, {len(errors)} violations; scratch stores/loads per barrier segment: {spill}')
+        stores = ''
+        if sarah:
+            st_errors, n_st = check_stores(name, body)
+            errors = errors + st_errors
+            stores = f'{n_st} hand-issued stores, '
+        print(f'{name[:40]}...: {n_loads} hand-issued loads, {stores}{n_waits} vmcnt waits, {len(errors)} violations; scratch stores/loads per barrier segment: {spill}')
         bad += errors
     for e in bad[:40]:
         print('VIOLATION', e)
