@@ -174,6 +174,37 @@ int pnp_csmri_sarah_step(pnp_csmri_plan* plan, const void* a, const void* b, con
                          void* out, void* out2, int denoise, double sigma_modifier, double fallback_sigma, const void* xrec,
                          double* sse_out, void* sigma_out, void* stream);
 
+/* One whole inner iteration of the GD or the SGD loop -- algorithms/pnp_gd.py:24-70, pnp_sgd.py:24-70: gradient with its data
+ * term, step, estimate_sigma, TVDenoiser.denoise, Problem.PSNR -- in one kernel (f32 plans of 256 x 256):
+ *     out = prox_TV( alpha * alpha_vec[b] * Re ifft2( sel o fft2(a) - sel o Y ) + beta * c1 )          (a = c1 = z, beta = 1)
+ * Exactly one of yh and YT carries the data term.  yh (packed by pnp_csmri_pack_y for the selector bitsT, i.e. for the sampling
+ * mask) with bitsT = the mask is the GD step; YT ([batch][W][H] complex f32, Y transposed, as pnp_csmri_grad_sel takes it) with
+ * bitsT = one slot of the drawn selbits is the SGD step: the data term of THAT selector is formed inside the kernel's column
+ * phase, as the streaming column kernel forms it.  out may alias a and c1.  denoise, sigma_modifier, fallback_sigma, xrec,
+ * sse_out, sigma_out as in pnp_csmri_svrg_step.
+ * PNP_ERR_ARG before any device work: a NULL plan, a, bitsT, c1 or out; both or neither of yh and YT; sse_out without xrec; a
+ * plan that is not f32 256 x 256.                                                                                  */
+int pnp_csmri_grad_step(pnp_csmri_plan* plan, const void* a, const uint32_t* bitsT, const void* yh, const void* YT, double alpha,
+                        const void* alpha_vec, double beta, const void* c1, void* out, int denoise, double sigma_modifier,
+                        double fallback_sigma, const void* xrec, double* sse_out, void* sigma_out, void* stream);
+
+/* One whole inner iteration of the SAGA loop -- algorithms/pnp_saga.py:43-79 -- in one kernel (f32 plans of 256 x 256):
+ *     g    = alpha * alpha_vec[b] * Re ifft2( sel o fft2(z) - sel o Y )                  (alpha = 1 / mb, data term from YT)
+ *     old  = table[row[b]][b];  pv = table[prev_row[b]][b]
+ *     s    = sum + g - old
+ *     out  = prox_TV( z - lr * ((g - pv) + s * inv_hist) )
+ *     table[row[b]][b] = g;  sum = s
+ * Per element the statements and their order are pnp_saga_table_update's.  table: [hist][batch][H][W] f32; row, prev_row: int32
+ * [batch] device vectors with entries in [0, hist) (as in pnp_saga_table_update_pp; the kernel cannot check them);
+ * row[b] == prev_row[b] is legal (old and pv are loaded before anything is stored); sum: [batch][H][W].  out may alias z.
+ * denoise == 0 stores the stepped image for a prox that is not this one.
+ * PNP_ERR_ARG before any device work: a NULL plan, z, bitsT, YT, table, row, prev_row, sum or out; hist < 1; sse_out without
+ * xrec; a plan that is not f32 256 x 256; table or sum overlapping z, out, xrec or each other.                        */
+int pnp_csmri_saga_step(pnp_csmri_plan* plan, const void* z, const uint32_t* bitsT, const void* YT, double alpha,
+                        const void* alpha_vec, void* table, const int32_t* row, const int32_t* prev_row, void* sum, double lr,
+                        double inv_hist, int hist, void* out, int denoise, double sigma_modifier, double fallback_sigma,
+                        const void* xrec, double* sse_out, void* sigma_out, void* stream);
+
 /* A whole OUTER iteration of the SVRG loop with the TV prox -- algorithms/pnp_svrg.py:32-95 for T2 inner iterations: the refresh
  * mu = grad_full(z), w = z, then T2 times { minibatch SVRG direction, step, estimate_sigma, TVDenoiser.denoise, PSNR } -- in ONE
  * launch: the workgroup that owns a problem runs pnp_csmri_svrg_outer_step and then T2 - 1 times pnp_csmri_svrg_step (a = z,
@@ -229,6 +260,17 @@ int pnp_csmri_sarah_step_pp(pnp_csmri_plan* plan, const void* a, const void* b, 
                             const double* gamma_pp, const void* c2, void* v_out, void* out, void* out2, int denoise,
                             double sigma_modifier, const double* sigma_modifier_pp, double fallback_sigma, const void* xrec,
                             double* sse_out, void* sigma_out, void* stream);
+/* pnp_csmri_grad_step with alpha_pp, sigma_modifier_pp; pnp_csmri_saga_step with alpha_pp, lr_pp (cast as
+ * pnp_saga_table_update_pp casts it), sigma_modifier_pp.  Problem b equals problem b of the plain call made with its scalars.     */
+int pnp_csmri_grad_step_pp(pnp_csmri_plan* plan, const void* a, const uint32_t* bitsT, const void* yh, const void* YT,
+                           double alpha, const double* alpha_pp, const void* alpha_vec, double beta, const void* c1, void* out,
+                           int denoise, double sigma_modifier, const double* sigma_modifier_pp, double fallback_sigma,
+                           const void* xrec, double* sse_out, void* sigma_out, void* stream);
+int pnp_csmri_saga_step_pp(pnp_csmri_plan* plan, const void* z, const uint32_t* bitsT, const void* YT, double alpha,
+                           const double* alpha_pp, const void* alpha_vec, void* table, const int32_t* row, const int32_t* prev_row,
+                           void* sum, double lr, const double* lr_pp, double inv_hist, int hist, void* out, int denoise,
+                           double sigma_modifier, const double* sigma_modifier_pp, double fallback_sigma, const void* xrec,
+                           double* sse_out, void* sigma_out, void* stream);
 int pnp_csmri_svrg_outer_step_pp(pnp_csmri_plan* plan, const void* z, const uint32_t* mask_bitsT, const void* yh,
                                  const void* alpha_vec, double lr, const double* lr_pp, void* w_out, void* mu_out, void* out,
                                  int denoise, double sigma_modifier, const double* sigma_modifier_pp, double fallback_sigma,

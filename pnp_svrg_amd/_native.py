@@ -35,6 +35,8 @@ SIGNATURES = {
     'pnp_csmri_grad': (_i, [_vp, _vp, _vp, _vp, _vp, _d, _d, _vp, _d, _vp, _vp, _vp]),
     'pnp_csmri_grad_sel': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _vp, _d, _vp, _d, _vp, _vp, _vp]),
     'pnp_csmri_svrg_step': (_i, [_vp, _vp, _vp, _vp, _d, _vp, _d, _vp, _d, _vp, _vp, _i, _d, _d, _vp, _vp, _vp, _vp]),
+    'pnp_csmri_grad_step': (_i, [_vp, _vp, _vp, _vp, _vp, _d, _vp, _d, _vp, _vp, _i, _d, _d, _vp, _vp, _vp, _vp]),
+    'pnp_csmri_saga_step': (_i, [_vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp, _vp, _d, _d, _i, _vp, _i, _d, _d, _vp, _vp, _vp, _vp]),
     'pnp_csmri_sarah_step': (_i, [_vp, _vp, _vp, _vp, _d, _vp, _d, _vp, _d, _vp, _vp, _vp, _vp, _i, _d, _d, _vp, _vp, _vp, _vp]),
     'pnp_csmri_svrg_outer_step': (_i, [_vp, _vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _i, _d, _d, _vp, _vp, _vp, _vp]),
     'pnp_csmri_svrg_outer_iteration': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _d, _i, _d, _d, _vp, _vp, _i, _i, _vp, _vp]),
@@ -83,6 +85,9 @@ SIGNATURES = {
     'pnp_csmri_grad_sel_pp': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _vp, _vp, _d, _vp, _d, _vp, _vp, _vp, _vp]),
     'pnp_csmri_svrg_step_pp': (_i, [_vp, _vp, _vp, _vp, _d, _vp, _vp, _d, _vp, _d, _vp, _vp, _vp, _i, _d, _vp, _d, _vp, _vp, _vp, _vp]),
     'pnp_csmri_sarah_step_pp': (_i, [_vp, _vp, _vp, _vp, _d, _vp, _vp, _d, _vp, _d, _vp, _vp, _vp, _vp, _vp, _i, _d, _vp, _d, _vp, _vp, _vp, _vp]),
+    'pnp_csmri_grad_step_pp': (_i, [_vp, _vp, _vp, _vp, _vp, _d, _vp, _vp, _d, _vp, _vp, _i, _d, _vp, _d, _vp, _vp, _vp, _vp]),
+    'pnp_csmri_saga_step_pp': (_i, [_vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp, _vp, _vp, _d, _vp, _d, _i, _vp, _i, _d, _vp, _d, _vp, _vp,
+                                    _vp, _vp]),
     'pnp_csmri_svrg_outer_step_pp': (_i, [_vp, _vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp, _i, _d, _vp, _d, _vp, _vp, _vp, _vp]),
     'pnp_csmri_svrg_outer_iteration_pp': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _d, _vp, _i, _vp, _d, _vp, _d, _vp, _vp, _i,
                                                _i, _vp, _vp]),

@@ -346,6 +346,11 @@ int csmri_sarah_launch(int batch, const void* twtab, const void* a, const void* 
                        const void* alpha_vec, double beta, const void* c1, double gamma, const void* c2, void* v_out, void* out,
                        void* out2, int mode, double sigma_modifier, double fallback_sigma, const void* xrec, double* sse_out,
                        void* sigma_out, void* stream, const double* alpha_pp, const double* gamma_pp, const double* sm_pp);
+int csmri_minibatch_launch(int batch, const void* twtab, const void* a, const uint32_t* bitsT, const void* YT, double alpha,
+                           const void* alpha_vec, double beta, const void* c1, void* table, const int32_t* row, const int32_t* prev_row,
+                           void* sum, double lr, double inv_hist, void* out, int mode, double sigma_modifier, double fallback_sigma,
+                           const void* xrec, double* sse_out, void* sigma_out, void* stream, const double* alpha_pp, const double* lr_pp,
+                           const double* sm_pp);
 }
 
 namespace {
@@ -477,6 +482,84 @@ extern "C" int pnp_csmri_sarah_step_pp(pnp_csmri_plan* p, const void* a, const v
                                        double* sse_out, void* sigma_out, void* stream) {
     return sarah_step_impl(p, a, b, bitsT, alpha, alpha_pp, alpha_vec, beta, c1, gamma, gamma_pp, c2, v_out, out, out2, denoise,
                            sigma_modifier, sigma_modifier_pp, fallback_sigma, xrec, sse_out, sigma_out, stream);
+}
+
+// ---- one GD or SGD inner iteration in one kernel: out = prox_TV(alpha * alpha_vec[b] * Re ifft2(sel o fft2(a) - sel o Y) + beta * c1).
+// yh (the data term packed for bitsT: the GD step on the mask) takes the existing instantiations with one epilogue operand; YT (the
+// raw data, masked by bitsT inside the kernel: the SGD step on a drawn slot) takes k_grad_step.
+static int grad_step_impl(pnp_csmri_plan* p, const void* a, const uint32_t* bitsT, const void* yh, const void* YT, double alpha,
+                          const double* alpha_pp, const void* alpha_vec, double beta, const void* c1, void* out, int denoise,
+                          double sigma_modifier, const double* sigma_modifier_pp, double fallback_sigma, const void* xrec,
+                          double* sse_out, void* sigma_out, void* stream) {
+    PNP_CHECK_ARG(p && a && bitsT && c1 && out, "null argument");
+    PNP_CHECK_ARG((yh != nullptr) != (YT != nullptr), "pass the packed data term (yh) or the raw data (YT), exactly one of them");
+    PNP_CHECK_ARG(p->dtype == PNP_F32 && p->H == 256 && p->W == 256, "the one-kernel iteration exists for f32 plans of 256 x 256");
+    PNP_CHECK_ARG(!(sse_out && !xrec), "sse_out needs xrec");
+    if (yh != nullptr)
+        return csmri_fused_launch(p->batch, p->twtab, a, nullptr, bitsT, yh, alpha, alpha_vec, beta, c1, 0.0, nullptr, out,
+                                  denoise ? 0 : 1, sigma_modifier, fallback_sigma, xrec, sse_out, sigma_out, stream, nullptr, nullptr,
+                                  alpha_pp, nullptr, sigma_modifier_pp);
+    return csmri_minibatch_launch(p->batch, p->twtab, a, bitsT, YT, alpha, alpha_vec, beta, c1, nullptr, nullptr, nullptr, nullptr, 0.0,
+                                  0.0, out, denoise ? 0 : 1, sigma_modifier, fallback_sigma, xrec, sse_out, sigma_out, stream, alpha_pp,
+                                  nullptr, sigma_modifier_pp);
+}
+
+extern "C" int pnp_csmri_grad_step(pnp_csmri_plan* p, const void* a, const uint32_t* bitsT, const void* yh, const void* YT, double alpha,
+                                   const void* alpha_vec, double beta, const void* c1, void* out, int denoise, double sigma_modifier,
+                                   double fallback_sigma, const void* xrec, double* sse_out, void* sigma_out, void* stream) {
+    return grad_step_impl(p, a, bitsT, yh, YT, alpha, nullptr, alpha_vec, beta, c1, out, denoise, sigma_modifier, nullptr, fallback_sigma,
+                          xrec, sse_out, sigma_out, stream);
+}
+
+extern "C" int pnp_csmri_grad_step_pp(pnp_csmri_plan* p, const void* a, const uint32_t* bitsT, const void* yh, const void* YT,
+                                      double alpha, const double* alpha_pp, const void* alpha_vec, double beta, const void* c1,
+                                      void* out, int denoise, double sigma_modifier, const double* sigma_modifier_pp,
+                                      double fallback_sigma, const void* xrec, double* sse_out, void* sigma_out, void* stream) {
+    return grad_step_impl(p, a, bitsT, yh, YT, alpha, alpha_pp, alpha_vec, beta, c1, out, denoise, sigma_modifier, sigma_modifier_pp,
+                          fallback_sigma, xrec, sse_out, sigma_out, stream);
+}
+
+// ---- one whole SAGA inner iteration in one kernel: minibatch gradient with its data term, table update, step, prox
+static int saga_step_impl(pnp_csmri_plan* p, const void* z, const uint32_t* bitsT, const void* YT, double alpha, const double* alpha_pp,
+                          const void* alpha_vec, void* table, const int32_t* row, const int32_t* prev_row, void* sum, double lr,
+                          const double* lr_pp, double inv_hist, int hist, void* out, int denoise, double sigma_modifier,
+                          const double* sigma_modifier_pp, double fallback_sigma, const void* xrec, double* sse_out, void* sigma_out,
+                          void* stream) {
+    PNP_CHECK_ARG(p && z && bitsT && YT && table && row && prev_row && sum && out, "null argument");
+    PNP_CHECK_ARG(p->dtype == PNP_F32 && p->H == 256 && p->W == 256, "the one-kernel iteration exists for f32 plans of 256 x 256");
+    PNP_CHECK_ARG(!(sse_out && !xrec), "sse_out needs xrec");
+    PNP_CHECK_ARG(hist >= 1, "need hist >= 1");
+    {   // table [hist][batch][H][W] and sum [batch][H][W] are written while z, out and xrec are read or written: no overlap
+        const size_t img = (size_t)p->batch * 256 * 256 * sizeof(float);
+        auto overlap = [](const void* x, size_t nx, const void* y, size_t ny) {
+            const uintptr_t a0 = (uintptr_t)x, b0 = (uintptr_t)y;
+            return x != nullptr && y != nullptr && a0 < b0 + ny && b0 < a0 + nx;
+        };
+        const size_t tb = img * (size_t)hist;
+        PNP_CHECK_ARG(!overlap(table, tb, z, img) && !overlap(table, tb, out, img) && !overlap(table, tb, xrec, img) &&
+                      !overlap(sum, img, z, img) && !overlap(sum, img, out, img) && !overlap(sum, img, xrec, img) &&
+                      !overlap(table, tb, sum, img), "table and sum must not alias z, out, xrec or each other");
+    }
+    return csmri_minibatch_launch(p->batch, p->twtab, z, bitsT, YT, alpha, alpha_vec, 0.0, nullptr, table, row, prev_row, sum, lr, inv_hist,
+                                  out, denoise ? 0 : 1, sigma_modifier, fallback_sigma, xrec, sse_out, sigma_out, stream, alpha_pp, lr_pp,
+                                  sigma_modifier_pp);
+}
+
+extern "C" int pnp_csmri_saga_step(pnp_csmri_plan* p, const void* z, const uint32_t* bitsT, const void* YT, double alpha,
+                                   const void* alpha_vec, void* table, const int32_t* row, const int32_t* prev_row, void* sum, double lr,
+                                   double inv_hist, int hist, void* out, int denoise, double sigma_modifier, double fallback_sigma,
+                                   const void* xrec, double* sse_out, void* sigma_out, void* stream) {
+    return saga_step_impl(p, z, bitsT, YT, alpha, nullptr, alpha_vec, table, row, prev_row, sum, lr, nullptr, inv_hist, hist, out, denoise,
+                          sigma_modifier, nullptr, fallback_sigma, xrec, sse_out, sigma_out, stream);
+}
+
+extern "C" int pnp_csmri_saga_step_pp(pnp_csmri_plan* p, const void* z, const uint32_t* bitsT, const void* YT, double alpha,
+                                      const double* alpha_pp, const void* alpha_vec, void* table, const int32_t* row,
+                                      const int32_t* prev_row, void* sum, double lr, const double* lr_pp, double inv_hist, int hist,
+                                      void* out, int denoise, double sigma_modifier, const double* sigma_modifier_pp,
+                                      double fallback_sigma, const void* xrec, double* sse_out, void* sigma_out, void* stream) {
+    return saga_step_impl(p, z, bitsT, YT, alpha, alpha_pp, alpha_vec, table, row, prev_row, sum, lr, lr_pp, inv_hist, hist, out, denoise,
+                          sigma_modifier, sigma_modifier_pp, fallback_sigma, xrec, sse_out, sigma_out, stream);
 }
 
 // ---- the same with the outer-loop refresh folded in (first inner iteration of an outer iteration)

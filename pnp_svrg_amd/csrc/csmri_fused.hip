@@ -146,10 +146,54 @@ __device__ __forceinline__ void col_load(cx<float> (&v)[16], const cx<float>* ld
     }
 }
 
+// YTERM (the minibatch forms: pnp_csmri_grad_step with YT, pnp_csmri_saga_step): the data term of THIS call's selector is
+// subtracted here, built from the raw data as k_cols builds it (csmri.hip, its YT branch; the weights are k_pack_y's: the
+// selector at (kx, ky) times Y there plus the selector at the mirror point times conj Y there -- the sampling mask is not
+// Hermitian, so this is NOT the mask's packed term times the selector weight).  yta / ytb: rows ca and cb of YT ([W][H]: Y
+// transposed), cb = W - ca, or W / 2 beside ca = 0 for the packed pair.  The loads are plain ones, per column pair, straight
+// into the subtraction (as yhc's): 8 bytes per lane, 16 lanes on 128 contiguous bytes, ytb's in descending order.
+template <bool YTERM = false>
 __device__ __forceinline__ void col_transform(cx<float> (&v)[16], const cx<float>* twl, cx<float>* scr, const uint32_t* sb,
-                                              const ColPair& c, int l, const cx<float>* __restrict__ yhc) {
+                                              const ColPair& c, int l, const cx<float>* __restrict__ yhc,
+                                              const cx<float>* __restrict__ yta = nullptr, const cx<float>* __restrict__ ytb = nullptr) {
     fft256<false>(v, twl, scr, l);                          // along h: element ky = l + 16 r
     auto bit = [&](int slot, int ky) -> float { return (float)((sb[slot * 8 + (ky >> 5)] >> (ky & 31)) & 1u); };
+    if constexpr (YTERM) {
+        if (c.packed) {
+            // (k_cols, blockIdx.x == 0, with YT: slot 0 = kx 0, slot 1 = kx 128)
+            __builtin_amdgcn_wave_barrier();
+#pragma unroll
+            for (int r = 0; r < 16; ++r) scr[l + 16 * r] = v[r];
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int ky = l + 16 * r, km = (FN - ky) & (FN - 1);
+                const cx<float> pk = v[r], pm = scr[km];
+                const cx<float> A = {0.5f * (pk.x + pm.x), 0.5f * (pk.y - pm.y)};
+                const cx<float> B = {0.5f * (pk.y + pm.y), -0.5f * (pk.x - pm.x)};
+                const float a1 = bit(0, ky), a2 = bit(0, km), b1 = bit(1, ky), b2 = bit(1, km);
+                const float wA = 0.5f * (a1 + a2), wB = 0.5f * (b1 + b2);
+                const cx<float> p1 = yta[ky], p2 = yta[km], q1 = ytb[ky], q2 = ytb[km];
+                const cx<float> ya = {0.5f * (a1 * p1.x + a2 * p2.x), 0.5f * (a1 * p1.y - a2 * p2.y)};
+                const cx<float> yb = {0.5f * (b1 * q1.x + b2 * q2.x), 0.5f * (b1 * q1.y - b2 * q2.y)};
+                v[r] = csub(cx<float>{fma_(wA, A.x, -(wB * B.y)), fma_(wA, A.y, wB * B.x)}, cx<float>{ya.x - yb.y, ya.y + yb.x});
+            }
+            __builtin_amdgcn_wave_barrier();
+        } else {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int ky = l + 16 * r, km = (FN - ky) & (FN - 1);
+                const float w1 = bit(0, ky), w2 = bit(1, km);
+                const float wgt = 0.5f * (w1 + w2);
+                const cx<float> y1 = yta[ky], y2 = ytb[km];
+                v[r] = csub(cx<float>{wgt * v[r].x, wgt * v[r].y},
+                            cx<float>{0.5f * (w1 * y1.x + w2 * y2.x), 0.5f * (w1 * y1.y - w2 * y2.y)});
+            }
+        }
+        fft256<true>(v, twl, scr, l);                       // back to h = l + 16 r
+        return;
+    }
     if (c.packed) {
         // the packed column holds two real-input transforms: separate, weight, re-pack (k_cols, blockIdx.x == 0)
         __builtin_amdgcn_wave_barrier();
@@ -332,12 +376,14 @@ __device__ __forceinline__ unsigned cbuf_c_base(int wv, int cl, int q) { return 
 // NOPS: epilogue operand arrays actually present (0, 1: c1 with coefficient beta, 2: c1 and c2) -- known at launch, so the
 // epilogue is straight-line code (with run-time tests hipcc kept both prefetch buffers alive everywhere and spilled them while
 // their loads were in flight)
-template <bool OUTER = false, int NOPS = 2>
+// YTERM: the data term comes from the raw data YT ([W][H] of this image) and this call's selector bits (col_transform<true>);
+// yh is then not read.
+template <bool OUTER = false, int NOPS = 2, bool YTERM = false>
 __device__ __forceinline__ void fused_gradient(RImg& R, const float* a, const float* b,
                                                const uint32_t* __restrict__ bits, const cx<float>* __restrict__ twtab, cx<float>* twl, cx<float>* ldc,
                                                uint32_t (*sbits)[FG][2][16], const cx<float>* __restrict__ yh, float scale, float beta,
                                                const float* c1, float gamma, const float* c2, int t, int g, int l,
-                                               float* w_out, float* mu_out PNP_STAMP_PARAM) {
+                                               float* w_out, float* mu_out, const cx<float>* __restrict__ YT PNP_STAMP_PARAM) {
     cx<float>* scr = ldc + g * F_SCR;
     float* ldf = reinterpret_cast<float*>(ldc);
     const RLane L(t);
@@ -423,9 +469,19 @@ __device__ __forceinline__ void fused_gradient(RImg& R, const float* a, const fl
         col_load(v0, ldc, cp[0], l);
         col_load(v1, ldc, cp[1], l);
         __syncthreads();                                    // every group has its columns: the buffer becomes FFT scratch
-        col_transform(v0, twl, scr, sbits[half][g][0], cp[0], l, yhc[0]);
-        asm volatile("" ::: "memory");                      // one transform's working registers at a time
-        col_transform(v1, twl, scr, sbits[half][g][1], cp[1], l, yhc[1]);
+        if constexpr (YTERM) {
+            // rows ca and cb of YT, from the same indices as cp[] above
+            const int i0 = g, i1 = FG + g;
+            const int ca0 = half == 0 ? i0 : 64 + i0, ca1 = half == 0 ? i1 : 64 + i1;
+            const int cb0 = (half == 0 && i0 == 0) ? 128 : FN - ca0, cb1 = FN - ca1;
+            col_transform<true>(v0, twl, scr, sbits[half][g][0], cp[0], l, nullptr, YT + (size_t)ca0 * FN, YT + (size_t)cb0 * FN);
+            asm volatile("" ::: "memory");
+            col_transform<true>(v1, twl, scr, sbits[half][g][1], cp[1], l, nullptr, YT + (size_t)ca1 * FN, YT + (size_t)cb1 * FN);
+        } else {
+            col_transform(v0, twl, scr, sbits[half][g][0], cp[0], l, yhc[0]);
+            asm volatile("" ::: "memory");                  // one transform's working registers at a time
+            col_transform(v1, twl, scr, sbits[half][g][1], cp[1], l, yhc[1]);
+        }
         __syncthreads();                                    // all FFT scratch use is over: the buffer carries data again
         col_store(v0, ldc, cp[0], l);
         col_store(v1, ldc, cp[1], l);
@@ -594,6 +650,71 @@ __device__ __forceinline__ void sarah_epilogue(RImg& R, float gamma, const float
     }
 }
 
+// SAGA form (pnp_csmri_saga_step), the epilogue.  On entry R = g = alpha * Re ifft2(sel o fft2(z) - sel o Y), left by
+// fused_gradient<false, 0, true>, which has no load in flight when it returns.  Per element the statements and their order are
+// k_saga_update's (vr.hip):   s = sum + g - old;  R <- z - lr * ((g - pv) + s * inv_hist);  slot = g;  sum = s.
+// FOUR operand images are read (old = slot, pv = prev, sum, z) and two written beside R, so a batch is HALF a pass -- the two rows
+// of one column half, 2 pieces of each operand = 8 loads = 32 registers -- and two batches are in flight (the 64 registers of
+// sarah_epilogue's U).  Batch k: pass k >> 1, column half k & 1.  The 4 stores of a batch (2 of g to slot, 2 of s to sum) are
+// issued BEHIND its wait: slot and prev are the same memory when row == prev_row, and every piece is loaded -- old and pv --
+// before the lane that loaded it stores to it.  Order of issue:
+//   L0 L1 | wait(L0) C0 S0 L2 | wait(L1) C1 S1 L3 | ... | wait(L14) C14 S14 | wait(L15) C15 S15
+// and behind a batch in the queue are   L0: L1 = 8;   Lk, 1 <= k <= 14: S(k-1) L(k+1) = 12;   L15: S14 = 4.
+// out may alias z: every piece of z is waited for here, the stores to out are issued in phase 5.
+struct SagaArgs { float* slot; const float* prev; float* sum; float lr, inv_hist; };
+
+template <int IMM0, int IMM1> __device__ __forceinline__ void saga_gld(f4 (&d)[4][2], const SagaArgs& sa, const float* z, int pass, unsigned voff) {
+    const float* src[4] = {sa.slot, sa.prev, sa.sum, z};
+#pragma unroll
+    for (int o = 0; o < 4; ++o) {
+        gld<IMM0>(d[o][0], src[o] + pass * 8192, voff);
+        gld<IMM1>(d[o][1], src[o] + pass * 8192, voff);
+    }
+}
+template <int N> __device__ __forceinline__ void saga_wait(f4 (&d)[4][2]) {
+    asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory");
+#pragma unroll
+    for (int o = 0; o < 4; ++o) asm volatile("" : "+v"(d[o][0]), "+v"(d[o][1]));
+}
+
+__device__ __forceinline__ void saga_epilogue(RImg& R, const SagaArgs& sa, const float* z, int t) {
+    const RLane L(t);
+    f4 U[2][4][2];                                              // [buffer][old, pv, sum, z][row01]
+    saga_gld<0, 1024>(U[0], sa, z, 0, L.voff);
+    saga_gld<512, 1536>(U[1], sa, z, 0, L.voff);
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const int pass = k >> 1, h2 = k & 1;
+        if (k == 0) saga_wait<8>(U[0]);
+        else if (k < 15) saga_wait<12>(U[k & 1]);
+        else saga_wait<4>(U[1]);
+        f4 gq[2], sq[2];
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const f4 gv = R[pass][h2][q], ov = U[k & 1][0][q], pv = U[k & 1][1][q], sm = U[k & 1][2][q], zv = U[k & 1][3][q];
+            const f4 s = sm + gv - ov;
+            R[pass][h2][q] = zv - sa.lr * ((gv - pv) + s * sa.inv_hist);
+            gq[q] = gv;
+            sq[q] = s;
+        }
+        float* slot = sa.slot + pass * 8192;
+        float* sum = sa.sum + pass * 8192;
+        if (h2 == 0) {
+            gst<0>(slot, L.voff, gq[0]); gst<1024>(slot, L.voff, gq[1]);
+            gst<0>(sum, L.voff, sq[0]); gst<1024>(sum, L.voff, sq[1]);
+        } else {
+            gst<512>(slot, L.voff, gq[0]); gst<1536>(slot, L.voff, gq[1]);
+            gst<512>(sum, L.voff, sq[0]); gst<1536>(sum, L.voff, sq[1]);
+        }
+        // the batch is consumed before its buffer is requested again (see `stage`)
+        asm volatile("" : "+v"(R[pass][h2][0]), "+v"(R[pass][h2][1]));
+        if (k + 2 < 16) {
+            if (h2 == 0) saga_gld<0, 1024>(U[0], sa, z, pass + 1, L.voff);
+            else saga_gld<512, 1536>(U[1], sa, z, pass + 1, L.voff);
+        }
+    }
+}
+
 }  // namespace pnp
 
 // everything from here on follows pywt / skimage product for product: no FMA contraction (exact zeros in the wavelet
@@ -631,14 +752,16 @@ __device__ __forceinline__ void startup_stagger(int stagger_n, int stagger_group
 // One whole iteration of one image (`a` ... `out`, `xrec`, `w_out`, `mu_out`: THIS image's arrays; sse_out / sigma_out: this
 // image's slots).  Whole-workgroup collective.
 // SARAH: 0 = the SVRG forms; 1 = the SARAH form (v_out stored from the epilogue, then c2 folded in: sarah_epilogue); 2 = the same with
-// a second destination out2 of the final store.  A template parameter like the others: the epilogue stays straight-line code.
-template <int MODE, bool OUTER, int NOPS, int SARAH = 0>
+// a second destination out2 of the final store; 3 = the SAGA form (the data term from YT, then saga_epilogue on `saga`).  A template
+// parameter like the others: the epilogue stays straight-line code.  YTERM: the data term from YT and the selector (fused_gradient).
+template <int MODE, bool OUTER, int NOPS, int SARAH = 0, bool YTERM = false>
 __device__ __forceinline__ void svrg_iter_body(unsigned char* lds_raw, FusedShared& sh, const float* a, const float* b,
                                                const uint32_t* __restrict__ bits, const cx<float>* __restrict__ yh,
                                                const cx<float>* __restrict__ twtab, float scale, float beta, const float* c1,
                                                float gamma, const float* c2, float* oi, float sigma_modifier, float fallback_sigma,
                                                const float* xri, double* __restrict__ sse_out, float* __restrict__ sigma_out,
-                                               float* w_out, float* mu_out, float* v_out = nullptr, float* out2 = nullptr) {
+                                               float* w_out, float* mu_out, float* v_out = nullptr, float* out2 = nullptr,
+                                               const cx<float>* __restrict__ YT = nullptr, const SagaArgs* saga = nullptr) {
     constexpr bool DENOISE = MODE == FUSED_FULL;
     cx<float>* ldc = reinterpret_cast<cx<float>*>(lds_raw);
     float* ldf = reinterpret_cast<float*>(lds_raw);
@@ -657,12 +780,20 @@ __device__ __forceinline__ void svrg_iter_body(unsigned char* lds_raw, FusedShar
     PNP_STAMP(0);
     const RLane L(t);
     RImg R;
-    if constexpr (SARAH != 0) {
+    if constexpr (SARAH == 3) {
+        // phases 1-3 without an epilogue operand: R = g = alpha * (gradient of this selector with its data term); then the table
+        asm volatile("" : "+s"(YT));
+        fused_gradient<false, 0, true>(R, a, nullptr, bits, twtab, twl, ldc, sbits, nullptr, scale, 0.f, nullptr, 0.f, nullptr, t, g, l, nullptr, nullptr, YT PNP_STAMP_ARG);
+        saga_epilogue(R, *saga, a, t);
+    } else if constexpr (SARAH != 0) {
         // phases 1-3 and the first epilogue stage are the gradient-only instantiation's: R = alpha * g + beta * c1 = v_out
-        fused_gradient<false, 1>(R, a, b, bits, twtab, twl, ldc, sbits, yh, scale, beta, c1, 0.f, nullptr, t, g, l, nullptr, nullptr PNP_STAMP_ARG);
+        fused_gradient<false, 1>(R, a, b, bits, twtab, twl, ldc, sbits, yh, scale, beta, c1, 0.f, nullptr, t, g, l, nullptr, nullptr, nullptr PNP_STAMP_ARG);
         sarah_epilogue(R, gamma, c2, v_out, t);
+    } else if constexpr (YTERM) {
+        asm volatile("" : "+s"(YT));
+        fused_gradient<OUTER, NOPS, true>(R, a, b, bits, twtab, twl, ldc, sbits, nullptr, scale, beta, c1, gamma, c2, t, g, l, w_out, mu_out, YT PNP_STAMP_ARG);
     } else
-        fused_gradient<OUTER, NOPS>(R, a, b, bits, twtab, twl, ldc, sbits, yh, scale, beta, c1, gamma, c2, t, g, l, w_out, mu_out PNP_STAMP_ARG);
+        fused_gradient<OUTER, NOPS>(R, a, b, bits, twtab, twl, ldc, sbits, yh, scale, beta, c1, gamma, c2, t, g, l, w_out, mu_out, nullptr PNP_STAMP_ARG);
     if (MODE == FUSED_GRAD) {
         gst_passes<8>(oi, 0, L.voff, R);
         return;
@@ -1032,6 +1163,63 @@ __global__ __launch_bounds__(FT) void k_sarah_iter_pp(const float* a, const floa
                                                  OUT2 ? out2 + img : nullptr);
 }
 
+// The minibatch form of the GD / SGD inner iteration (pnp_csmri_grad_step with YT; algorithms/pnp_sgd.py:24-70 with a = c1 = z):
+//     out = prox_TV( alpha * alpha_vec[b] * Re ifft2(sel o fft2(a) - sel o Y) + beta * c1 ),
+// the data term of this call's selector formed in the column phase (col_transform<true>).  ONE kernel serves the plain and the _pp
+// entry point: alpha_pp, sm_pp are DOUBLE [batch] arrays or NULL, converted expression for expression as in k_svrg_iter_pp -- with
+// both NULL the scalars the host converted hold, so problem b of a _pp call is problem b of the plain call bit for bit.
+template <int MODE>
+__global__ __launch_bounds__(FT) void k_grad_step(const float* a, const uint32_t* __restrict__ bitsT, const cx<float>* __restrict__ YT,
+                                                  const cx<float>* __restrict__ twtab, float scale, const float* __restrict__ alpha_vec,
+                                                  float beta, const float* c1, float* out, float sigma_modifier, float fallback_sigma,
+                                                  const float* __restrict__ xrec, double* __restrict__ sse_out,
+                                                  float* __restrict__ sigma_out, int stagger_n, int stagger_groups, int stagger_units,
+                                                  const double* __restrict__ alpha_pp, const double* __restrict__ sm_pp) {
+    startup_stagger(stagger_n, stagger_groups, stagger_units);
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    __shared__ FusedShared sh;
+    const int prob = blockIdx.x;
+    const size_t img = (size_t)prob * FN * FN;
+    if (alpha_pp != nullptr) scale = (float)(alpha_pp[prob] * (1.0 / ((double)FN * (double)FN)));
+    if (alpha_vec != nullptr) scale *= alpha_vec[prob];
+    if (sm_pp != nullptr) sigma_modifier = (float)sm_pp[prob];
+    svrg_iter_body<MODE, false, 1, 0, true>(lds_raw, sh, a + img, nullptr, bitsT + (size_t)prob * FN * 8, nullptr, twtab, scale, beta,
+                                            c1 + img, 0.f, nullptr, out + img, sigma_modifier, fallback_sigma,
+                                            xrec != nullptr ? xrec + img : nullptr, sse_out != nullptr ? sse_out + prob : nullptr,
+                                            sigma_out != nullptr ? sigma_out + prob : nullptr, nullptr, nullptr, nullptr, nullptr,
+                                            YT + img);
+}
+
+// One whole SAGA inner iteration (pnp_csmri_saga_step; algorithms/pnp_saga.py:43-79): the minibatch gradient with its data term, the
+// table update and the step (saga_epilogue), then phases 4 and 5.  table: [hist][batch][H][W]; row, prev_row: int32 [batch];
+// sum: [batch][H][W].  alpha_pp, lr_pp, sm_pp: DOUBLE [batch] or NULL, as in k_grad_step; lr is cast as k_saga_update_pp casts it.
+template <int MODE>
+__global__ __launch_bounds__(FT) void k_saga_iter(const float* z, const uint32_t* __restrict__ bitsT, const cx<float>* __restrict__ YT,
+                                                  const cx<float>* __restrict__ twtab, float scale, const float* __restrict__ alpha_vec,
+                                                  float* table, const int32_t* __restrict__ row, const int32_t* __restrict__ prev_row,
+                                                  float* sum, float lr, float inv_hist, float* out, float sigma_modifier,
+                                                  float fallback_sigma, const float* __restrict__ xrec, double* __restrict__ sse_out,
+                                                  float* __restrict__ sigma_out, int stagger_n, int stagger_groups, int stagger_units,
+                                                  const double* __restrict__ alpha_pp, const double* __restrict__ lr_pp,
+                                                  const double* __restrict__ sm_pp) {
+    startup_stagger(stagger_n, stagger_groups, stagger_units);
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    __shared__ FusedShared sh;
+    const int prob = blockIdx.x, batch = gridDim.x;
+    const size_t img = (size_t)prob * FN * FN;
+    if (alpha_pp != nullptr) scale = (float)(alpha_pp[prob] * (1.0 / ((double)FN * (double)FN)));
+    if (alpha_vec != nullptr) scale *= alpha_vec[prob];
+    if (lr_pp != nullptr) lr = (float)lr_pp[prob];
+    if (sm_pp != nullptr) sigma_modifier = (float)sm_pp[prob];
+    SagaArgs sa = {table + ((size_t)row[prob] * batch + prob) * FN * FN, table + ((size_t)prev_row[prob] * batch + prob) * FN * FN,
+                   sum + img, lr, inv_hist};
+    asm volatile("" : "+s"(sa.slot), "+s"(sa.prev), "+s"(sa.sum));
+    svrg_iter_body<MODE, false, 0, 3>(lds_raw, sh, z + img, nullptr, bitsT + (size_t)prob * FN * 8, nullptr, twtab, scale, 0.f, nullptr,
+                                      0.f, nullptr, out + img, sigma_modifier, fallback_sigma, xrec != nullptr ? xrec + img : nullptr,
+                                      sse_out != nullptr ? sse_out + prob : nullptr, sigma_out != nullptr ? sigma_out + prob : nullptr,
+                                      nullptr, nullptr, nullptr, nullptr, YT + img, &sa);
+}
+
 // stagger (see startup_stagger): only launches of more than one workgroup per CU pay for it and profit from it
 static int stagger_config(int* num_cu_out, int* groups, int* units) {
     static int num_cu = 0, st_groups = 2, st_units = 40;    // same-box sweep (tools/dev/stagger_sweep.py): 0.588 ms per config-2 step without, 0.575 with (2, 40), slower from (8, 20) on
@@ -1196,6 +1384,48 @@ int csmri_sarah_launch(int batch, const void* twtab, const void* a, const void* 
     else PNP_SARAH_LAUNCH(0, false);
 #undef PNP_SARAH_LAUNCH
 #undef PNP_SARAH_ARGS
+    PNP_CHECK_LAUNCH();
+    return PNP_OK;
+}
+
+// the minibatch forms (pnp_csmri_grad_step[_pp] with YT, pnp_csmri_saga_step[_pp]); mode: FUSED_FULL / FUSED_NO_DENOISE; scale and
+// casts as csmri_fused_launch.  saga: table != NULL selects k_saga_iter (c1 and beta are then not used)
+int csmri_minibatch_launch(int batch, const void* twtab, const void* a, const uint32_t* bitsT, const void* YT, double alpha,
+                           const void* alpha_vec, double beta, const void* c1, void* table, const int32_t* row, const int32_t* prev_row,
+                           void* sum, double lr, double inv_hist, void* out, int mode, double sigma_modifier, double fallback_sigma,
+                           const void* xrec, double* sse_out, void* sigma_out, void* stream, const double* alpha_pp, const double* lr_pp,
+                           const double* sm_pp) {
+    const float scale = (float)(alpha / ((double)FN * (double)FN));
+    hipStream_t s = (hipStream_t)stream;
+    int num_cu = 0, st_groups = 0, st_units = 0;
+    { const int rc = stagger_config(&num_cu, &st_groups, &st_units); if (rc != PNP_OK) return rc; }
+    const int stagger_units = batch > num_cu ? st_units : 0;
+    {   // > 64 KiB of dynamic LDS needs the opt-in, once per device (as fused_lds_optin)
+        static unsigned long long attr_done = 0;
+        int dev = 0;
+        PNP_CHECK_HIP(hipGetDevice(&dev));
+        if (!((attr_done >> (dev & 63)) & 1ull)) {
+#define PNP_MB_ATTR(K, M) PNP_CHECK_HIP(hipFuncSetAttribute((const void*)K<M>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F_LDS_BYTES))
+            PNP_MB_ATTR(k_grad_step, 0); PNP_MB_ATTR(k_grad_step, 1); PNP_MB_ATTR(k_saga_iter, 0); PNP_MB_ATTR(k_saga_iter, 1);
+#undef PNP_MB_ATTR
+            attr_done |= 1ull << (dev & 63);
+        }
+    }
+    if (table != nullptr) {
+#define PNP_SAGA_ARGS (const float*)a, bitsT, (const cx<float>*)YT, (const cx<float>*)twtab, scale, (const float*)alpha_vec, (float*)table, \
+                      row, prev_row, (float*)sum, (float)lr, (float)inv_hist, (float*)out, (float)sigma_modifier, (float)fallback_sigma,     \
+                      (const float*)xrec, sse_out, (float*)sigma_out, num_cu, st_groups, stagger_units, alpha_pp, lr_pp, sm_pp
+        if (mode == FUSED_FULL) k_saga_iter<0><<<batch, FT, F_LDS_BYTES, s>>>(PNP_SAGA_ARGS);
+        else k_saga_iter<1><<<batch, FT, F_LDS_BYTES, s>>>(PNP_SAGA_ARGS);
+#undef PNP_SAGA_ARGS
+    } else {
+#define PNP_GS_ARGS (const float*)a, bitsT, (const cx<float>*)YT, (const cx<float>*)twtab, scale, (const float*)alpha_vec, (float)beta, \
+                    (const float*)c1, (float*)out, (float)sigma_modifier, (float)fallback_sigma, (const float*)xrec, sse_out,            \
+                    (float*)sigma_out, num_cu, st_groups, stagger_units, alpha_pp, sm_pp
+        if (mode == FUSED_FULL) k_grad_step<0><<<batch, FT, F_LDS_BYTES, s>>>(PNP_GS_ARGS);
+        else k_grad_step<1><<<batch, FT, F_LDS_BYTES, s>>>(PNP_GS_ARGS);
+#undef PNP_GS_ARGS
+    }
     PNP_CHECK_LAUNCH();
     return PNP_OK;
 }

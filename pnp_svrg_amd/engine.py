@@ -31,6 +31,10 @@ SvrgEngine takes `T2` per problem as well: a [B] integer array make
 s % T2[b] == 0 -- one `pnp_refresh_pp` launch behind a full gradient at the steps where any problem refreshes -- and `run_span(n)`
 runs n steps in launches of `pnp_csmri_svrg_span_pp` where the one-kernel iteration holds the TV prox.  A scalar T2 takes exactly
 the calls it always took.
+GdEngine, SgdEngine and SagaEngine take `fused=True` as well (opt-in): an inner iteration is then ONE `pnp_csmri_grad_step`
+(GD: the mask and its packed data term; SGD: the drawn slot and the raw data, the slot's data term formed inside the kernel) or ONE
+`pnp_csmri_saga_step` (gradient, table update, step and prox) on a float32 256 x 256 CsmriBatch, with the coefficients, draws and
+rows of the streaming step; without it the engines make exactly the calls they always made.
 Every engine takes `log_objective=True`: beside the squared errors, a second ring `obj_log` gets the data-fidelity
 objective f(z) of the iterate every logged prox returned (`batch.objective`, row for row with `sse_log`; `objective_log()` reads it
 back) -- the convergence signal on measured data, where there is no ground truth for a PSNR.  Such an engine steps eagerly
@@ -145,11 +149,63 @@ class LoopEngine:
             return np.around(10 * np.log10(1.0 / (sse / self.b.N)), 2)
 
 
-class GdEngine(LoopEngine):
-    """pnp_gd over a batch (algorithms/pnp_gd.py:24-70): z <- prox(z - eta * decay^i * grad_full(z))."""
+def _check_fused(name, batch, prox, log_objective):
+    """What `fused=True` of GdEngine, SgdEngine and SagaEngine needs, every missing piece named."""
+    missing = []
+    if getattr(batch, 'kind', None) != 'csmri':
+        missing.append(f'a CsmriBatch (got {getattr(batch, "kind", type(batch).__name__)!r})')
+    else:
+        if batch.dtype != torch.float32:
+            missing.append(f'float32 (got {batch.dtype})')
+        if (batch.H, batch.W) != (256, 256):
+            missing.append(f'256 x 256 images (got {batch.H} x {batch.W})')
+    if not hasattr(prox, 'fused_args'):
+        missing.append(f'a prox with fused_args: TVProx or DnCNNProx (got {type(prox).__name__})')
+    if log_objective:
+        missing.append('log_objective=False')
+    if missing:
+        raise ValueError(f'{name}(fused=True) needs ' + ', '.join(missing))
+
+
+class _FusedStep:
+    """The one-kernel inner iteration shared by GdEngine, SgdEngine and SagaEngine (fused=True): the selector bits of a slot, and the
+    bookkeeping around the ONE call -- the squared errors go straight to this evaluation's row of the log, a prox that is not inside
+    the kernel (DnCNN, the 2-D wavelet prox) follows it through `after_fused`."""
+    _hostbits = None
+
+    def _slot_bits(self, j):
+        if self.mbs.host[j] is not None:                        # host-drawn selector: pack it to bits (a 5 us launch)
+            self._hostbits = self.b.plan.pack_mask(self.mbs.host[j], out=self._hostbits)
+            return self._hostbits
+        return self.mbs.selbits[j]
+
+    def _one_kernel(self, call, *args, **kw):
+        b, px = self.b, self.prox
+        sse_out = self.sse_log[self.n_prox % self.n_log]
+        den = px.fused_denoise
+        call(*args, out=self.z, denoise=den, xrec=b.xrec, sse=sse_out if den else None, **kw, **px.fused_args())
+        px.after_fused(self.z, b.xrec, sse_out)
+        self.n_prox += 1
+
+
+class GdEngine(_FusedStep, LoopEngine):
+    """pnp_gd over a batch (algorithms/pnp_gd.py:24-70): z <- prox(z - eta * decay^i * grad_full(z)).
+    fused=True (opt-in): a step is ONE pnp_csmri_grad_step on the mask and its packed data term."""
+
+    def __init__(self, batch, prox, eta, lr_decay=1.0, n_log=4096, seed=0, log_objective=False, *, fused=False):
+        self.fused = bool(fused)
+        if self.fused:
+            _check_fused('GdEngine', batch, prox, log_objective)
+        super().__init__(batch, prox, eta, lr_decay, n_log, seed, log_objective=log_objective)
 
     def step(self):
         lr = self.eta * self.lr_decay ** self.s
+        if self.fused:
+            b = self.b
+            self._one_kernel(b.plan.grad_step, self.z, b.bits, yh=b.yh_full, alpha=self._c('-lr', self.s, -lr), alpha_vec=b.inv_m0,
+                             beta=1.0, c1=self.z)
+            self.s += 1
+            return
         self.b.grad_full(self.z, out=self.z, alpha=self._c('-lr', self.s, -lr), beta=1.0, c1=self.z)
         self.z = self._prox(self.z)
         self.s += 1
@@ -204,12 +260,27 @@ class _StochEngine(LoopEngine):
         self.mbs.host[slot] = None
 
 
-class SgdEngine(_StochEngine):
-    """pnp_sgd over a batch (algorithms/pnp_sgd.py:24-70): v = grad_stoch(z, mb) / mini_batch_size."""
+class SgdEngine(_FusedStep, _StochEngine):
+    """pnp_sgd over a batch (algorithms/pnp_sgd.py:24-70): v = grad_stoch(z, mb) / mini_batch_size.
+    fused=True (opt-in): a step is ONE pnp_csmri_grad_step on the drawn slot and the raw data."""
+
+    def __init__(self, batch, prox, eta, mini_batch_size, lr_decay=1.0, n_log=4096, seed=0, n_slots=None, draw_id=None,
+                 log_objective=False, *, fused=False):
+        self.fused = bool(fused)
+        if self.fused:
+            _check_fused('SgdEngine', batch, prox, log_objective)
+        super().__init__(batch, prox, eta, mini_batch_size, lr_decay, n_log, seed, n_slots=n_slots, draw_id=draw_id,
+                         log_objective=log_objective)
 
     def step(self, idx_s=None):
         j = self._minibatch(idx_s, self.s)
         lr = self.eta * self.lr_decay ** self.s
+        if self.fused:
+            b = self.b
+            self._one_kernel(b.plan.grad_step, self.z, self._slot_bits(j), YT=b.YT, alpha=self._c('-lr/mb', self.s, -lr / self.mb),
+                             beta=1.0, c1=self.z)
+            self.s += 1
+            return
         self.b.grad_stoch(self.z, self.mbs, j, out=self.z, alpha=self._c('-lr/mb', self.s, -lr / self.mb), beta=1.0, c1=self.z)
         self.z = self._prox(self.z)
         self.s += 1
@@ -668,15 +739,21 @@ class SarahEngine(_StochEngine):
         self._dev_step = self.s
 
 
-class SagaEngine(_StochEngine):
+class SagaEngine(_FusedStep, _StochEngine):
     """pnp_saga over a batch (algorithms/pnp_saga.py:25-72): a device table [hist][B][H][W] of minibatch
     gradients (all rows start as the first one), its running sum, and ONE fused kernel per step that replaces a
     row, updates the sum, forms v = g - prev + sum/hist and applies the step (`pnp_saga_table_update`).
     The replaced row r of every step is drawn on the host (one value per step for the whole batch; pass `r=` to
-    `step` to impose the reference's `np.random.choice(hist_size, 1)` stream)."""
+    `step` to impose the reference's `np.random.choice(hist_size, 1)` stream).
+    fused=True (opt-in): a step is ONE pnp_csmri_saga_step -- minibatch gradient, table update, step and prox; the rows
+    always go in as the int32 [B] device vectors of the batched update.  The table initialisation is the streaming one."""
 
     def __init__(self, batch, prox, eta, mini_batch_size, hist_size=50, lr_decay=1.0, n_log=4096, seed=0, idx0=None, draw_id=None,
-                 log_objective=False):
+                 log_objective=False, *, fused=False):
+        self.fused = bool(fused)
+        if self.fused:
+            _check_fused('SagaEngine', batch, prox, log_objective)
+        self._row_cache = {}                                    # fused: one row for the whole batch -> its device vector, made once
         super().__init__(batch, prox, eta, mini_batch_size, lr_decay, n_log, seed, draw_id=draw_id, log_objective=log_objective)
         self.hist = hist_size
         self.g = torch.empty_like(self.z)
@@ -697,6 +774,10 @@ class SagaEngine(_StochEngine):
         the previous step's rows is the one that step made."""
         if self._rows is not None and r is self._rows[0]:
             return self._rows[1]
+        if self.fused and np.ndim(r) == 0:
+            if int(r) not in self._row_cache:
+                self._row_cache[int(r)] = torch.full((self.b.B,), int(r), dtype=torch.int32, device=self.z.device)
+            return self._row_cache[int(r)]
         rv = np.ascontiguousarray(np.broadcast_to(np.asarray(r, np.int32), (self.b.B,)))
         return torch.from_numpy(rv).to(self.z.device)
 
@@ -706,6 +787,8 @@ class SagaEngine(_StochEngine):
         j = self._minibatch(idx_s, self.s)
         if r is None:
             r = int(self._rng.integers(self.hist))
+        if self.fused:
+            return self._step_fused(j, r)
         self.b.grad_stoch(self.z, self.mbs, j, out=self.g, alpha=self._c('1/mb', 0, 1.0 / self.mb))
         lr = self.eta * self.lr_decay ** self.s
         if np.ndim(r) == 0 and np.ndim(self.r_prev) == 0 and np.ndim(lr) == 0:
@@ -724,8 +807,32 @@ class SagaEngine(_StochEngine):
         self.s += 1
 
 
+    def _step_fused(self, j, r):
+        """The step in ONE kernel: the rows and coefficients are those of the streaming step (a row for the whole batch as a
+        constant [B] vector)."""
+        b = self.b
+        if np.ndim(r) == 0:
+            r = int(r)
+            bad = not 0 <= r < self.hist
+        else:
+            r = np.broadcast_to(np.asarray(r, np.int64), (b.B,)).copy()
+            bad = r.min() < 0 or r.max() >= self.hist
+        if bad:
+            raise ValueError(f'SAGA row outside the table: rows in [0, {self.hist}), got {np.ravel(r).tolist()}')
+        prev = self._row_vec(self.r_prev)
+        row = self._row_vec(r)
+        if np.ndim(r) != 0:
+            self._rows = (r, row)
+        lr = self.eta * self.lr_decay ** self.s
+        self._one_kernel(b.plan.saga_step, self.z, self._slot_bits(j), b.YT, self.table, row, prev, self.tsum,
+                         self._c('lr', self.s, lr), 1.0 / self.hist, alpha=self._c('1/mb', 0, 1.0 / self.mb))
+        self.r_prev = r
+        self.s += 1
+
+
 def make_engine(batch, prox, eta, T2, mini_batch_size, lr_decay=1.0, variant='svrg', algorithm='svrg', hist_size=50, **kw):
-    """Engine by algorithm name: 'svrg' (default), 'sgd', 'gd', 'sarah', 'saga'."""
+    """Engine by algorithm name: 'svrg' (default), 'sgd', 'gd', 'sarah', 'saga'.  Keywords of the engine (`fused`, `seed`,
+    `draw_id`, `log_objective`, ...) pass through."""
     if algorithm == 'svrg':
         return SvrgEngine(batch, prox, eta, T2, mini_batch_size, lr_decay=lr_decay, variant=variant, **kw)
     if algorithm == 'sarah':

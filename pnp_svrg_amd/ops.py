@@ -269,6 +269,54 @@ class CsmriPlan:
                                         _stream()])
         return out, sse, sigma_out, v_out
 
+    def _one_kernel_plan(self, what):
+        if self.dtype != torch.float32 or self.H != 256 or self.W != 256:
+            raise ValueError(f'{what}: the one-kernel iteration exists for float32 plans of 256 x 256 (this plan: {self.dtype}, '
+                             f'{self.H} x {self.W})')
+
+    def grad_step(self, a, bits, yh=None, YT=None, alpha=1.0, beta=1.0, c1=None, out=None, *, alpha_vec=None, denoise=True,
+                  sigma_modifier=1.0, fallback_sigma=0.0, xrec=None, sse=None, sigma_out=None):
+        """pnp_csmri_grad_step: one GD or SGD inner iteration in ONE kernel (f32, 256 x 256):
+        out = prox_TV(alpha * alpha_vec[b] * Re ifft2(bits o fft2(a) - bits o Y) + beta * c1).  Data term: `yh` (packed for `bits` = the
+        mask: the GD step) or `YT` (complex [B, W, H], masked by `bits` = a drawn slot inside the kernel: the SGD step) -- exactly one.
+        out may be a and c1; denoise=False stores the stepped image.  Returns (out, sse, sigma_out)."""
+        self._one_kernel_plan('grad_step')
+        if (yh is None) == (YT is None):
+            raise ValueError('grad_step: pass the packed data term (yh) or the raw data (YT), exactly one of them')
+        assert bits.dtype == torch.int32 and tuple(bits.shape) == (self.B, self.W, self.H // 32)
+        assert c1 is not None, 'grad_step: c1 is required'
+        for t in (a, c1, out, xrec):
+            assert t is None or (t.dtype == self.dtype and t.numel() == self.B * self.H * self.W)
+        assert YT is None or (YT.dtype == _CDT[self.dtype] and tuple(YT.shape) == (self.B, self.W, self.H))
+        assert yh is None or (yh.dtype == _CDT[self.dtype] and tuple(yh.shape) == (self.B, self.W // 2, self.H))
+        out = out if out is not None else torch.empty_like(a)
+        sigma_out = sigma_out if sigma_out is not None else torch.empty(self.B, dtype=a.dtype, device=a.device)
+        _route('pnp_csmri_grad_step', [self._h, _p(a), _p(bits), _p(yh), _p(YT), _pp(alpha, self.B), _p(alpha_vec), float(beta), _p(c1),
+                                       _p(out), 1 if denoise else 0, _pp(sigma_modifier, self.B), float(fallback_sigma), _p(xrec),
+                                       _p(sse), _p(sigma_out), _stream()])
+        return out, sse, sigma_out
+
+    def saga_step(self, z, bits, YT, table, row, prev_row, tsum, lr, inv_hist, alpha=1.0, out=None, *, alpha_vec=None, denoise=True,
+                  sigma_modifier=1.0, fallback_sigma=0.0, xrec=None, sse=None, sigma_out=None):
+        """pnp_csmri_saga_step: one SAGA inner iteration in ONE kernel (f32, 256 x 256): g = alpha * Re ifft2(bits o fft2(z) - bits o Y);
+        s = tsum + g - table[row[b]][b]; out = prox_TV(z - lr * ((g - table[prev_row[b]][b]) + s * inv_hist)); table[row[b]][b] = g;
+        tsum = s.  table: [hist, B, H, W]; row, prev_row: int32 [B] device tensors; out may be z.  Returns (out, sse, sigma_out)."""
+        self._one_kernel_plan('saga_step')
+        assert bits.dtype == torch.int32 and tuple(bits.shape) == (self.B, self.W, self.H // 32)
+        assert YT.dtype == _CDT[self.dtype] and tuple(YT.shape) == (self.B, self.W, self.H)
+        for t in (z, tsum, out, xrec):
+            assert t is None or (t.dtype == self.dtype and t.numel() == self.B * self.H * self.W)
+        assert table.dtype == self.dtype and table.dim() >= 2 and table.shape[1] == self.B and table.numel() == table.shape[0] * z.numel()
+        for rv in (row, prev_row):
+            assert rv.dtype == torch.int32 and tuple(rv.shape) == (self.B,)
+        out = out if out is not None else torch.empty_like(z)
+        sigma_out = sigma_out if sigma_out is not None else torch.empty(self.B, dtype=z.dtype, device=z.device)
+        _route('pnp_csmri_saga_step', [self._h, _p(z), _p(bits), _p(YT), _pp(alpha, self.B), _p(alpha_vec), _p(table), _p(row),
+                                       _p(prev_row), _p(tsum), _pp(lr, self.B), float(inv_hist), int(table.shape[0]), _p(out),
+                                       1 if denoise else 0, _pp(sigma_modifier, self.B), float(fallback_sigma), _p(xrec), _p(sse),
+                                       _p(sigma_out), _stream()])
+        return out, sse, sigma_out
+
     def svrg_outer_step(self, z, mask_bits, yh, alpha_vec, lr, w_out, mu_out, out=None, *, denoise=True, sigma_modifier=1.0,
                         fallback_sigma=0.0, xrec=None, sse=None, sigma_out=None):
         """pnp_csmri_svrg_outer_step: the outer refresh of pnp_svrg folded into its first inner iteration, one kernel:

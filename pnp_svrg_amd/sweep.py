@@ -153,7 +153,8 @@ def make_prox(denoiser, **kw):
 def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta, n_inner, mini_batch_size=None, T2=None,
                 hist_size=50, H=256, W=256, dtype=torch.float32, max_batch=128, seeding='generator', variant='svrg', run_seed=1,
                 keep_trace=False, graph=True, kernel='Minimal', lr_decay=1.0, denoiser_kwargs=None, sigma_modifier=None,
-                shared_matrix=False, wide_trials=False, sarah_trials=False, t2_trials=False, objective=False, sarah_fused=False):
+                shared_matrix=False, wide_trials=False, sarah_trials=False, t2_trials=False, objective=False, sarah_fused=False,
+                fused_steps=False):
     """Runner for `run_sweep` / `grid_search` over any cell of the reference's sweep (script_diff_sampratio_set12.py:23-25,
     41-51, 64-131): problem in {'csmri', 'deblur', 'pr'} x algorithm in {'gd', 'sgd', 'svrg', 'saga', 'sarah'} x denoiser in
     {'tv', 'nlm', factory}; `n_inner` inner iterations (prox evaluations of the stepped iterate) per item, hyper-parameters
@@ -200,6 +201,11 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
     float32 256 x 256 and the 'tv' denoiser or a DnCNN prox factory -- anything else is a ValueError that names the offender.  Goes
     together with sarah_trials=True; batches with device-drawn minibatches replay whole outer iterations as hipGraphs.  False
     (default): engines, launches, rows and messages are exactly what they were.
+    fused_steps: opt in to the one-kernel inner iterations of pnp_gd, pnp_sgd and pnp_saga (GdEngine / SgdEngine / SagaEngine with
+    fused=True): problem='csmri', algorithm in {'gd', 'sgd', 'saga'}, float32 256 x 256 and the 'tv' denoiser or a
+    DnCNN prox factory -- anything else is a ValueError that names the offender.  Rides through `run(items)` and through
+    trial-batched grids (wide_trials=True for 'saga').  False (default): engines, launches, rows and messages are exactly what they
+    were.
     Beside `run(items)` the runner offers the pieces of a trial-batched grid (`grid_search(batch_trials=True)`):
     `run.prepare_data(items)` builds a rank's batches WITHOUT engines, `run.run_trials(data, trials, max_batch_trials)` runs a list
     of trials ({'eta', 'mini_batch_size', 'sigma_modifier'} overrides) on them as tiled batches, `run.data_key` says which runners
@@ -229,8 +235,21 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
             raise ValueError(f"sarah_fused=True needs the 'tv' denoiser or a DnCNN prox factory (got {denoiser!r})")
         if objective:
             raise ValueError('sarah_fused=True needs objective=False (the one-kernel forms do not log the objective)')
+    if not isinstance(fused_steps, (bool, np.bool_)):
+        raise ValueError(f'fused_steps: True or False, got {fused_steps!r}')
+    if fused_steps:
+        if problem != 'csmri':
+            raise ValueError(f"fused_steps=True is for problem='csmri' (got {problem!r}): the one-kernel iteration is a CSMRI kernel")
+        if algorithm not in ('gd', 'sgd', 'saga'):
+            raise ValueError(f"fused_steps=True is for algorithm in ('gd', 'sgd', 'saga') (got {algorithm!r})")
+        if dtype != torch.float32 or (H, W) != (256, 256):
+            raise ValueError(f'fused_steps=True needs float32 images of 256 x 256 (got {dtype}, H = {H}, W = {W})')
+        if not (denoiser == 'tv' or callable(denoiser)):
+            raise ValueError(f"fused_steps=True needs the 'tv' denoiser or a DnCNN prox factory (got {denoiser!r})")
+        if objective:
+            raise ValueError('fused_steps=True needs objective=False (the one-kernel forms do not log the objective)')
     eng_kw = {'log_objective': True} if objective else {}       # (off: the engines are made with the arguments they always got)
-    if sarah_fused:
+    if sarah_fused or fused_steps:
         eng_kw = dict(eng_kw, fused=True)                       # (rides with the other opt-in engine keyword)
     if shared_matrix and problem != 'pr':
         raise ValueError(f"shared_matrix=True is for problem='pr' (got {problem!r}): only its problems have a matrix to share")

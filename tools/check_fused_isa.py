@@ -16,6 +16,8 @@ this script verifies on the ISA of every k_svrg_iter instantiation that
                                                           denoise on and off, with and without out2), the same rule -- and for every
                                                           hand-issued store (`s_nop 4` in front of a global_store_dwordx4) the wait
                                                           state behind it: its data registers may be rewritten by the next instruction
+    python tools/check_fused_isa.py --steps [listing.s]   the minibatch forms instead (k_grad_step, k_saga_iter: denoise on and off --
+                                                          one kernel serves the plain and the _pp entry point), both rules
 
 Also prints, per kernel, the spill traffic between workgroup barriers (where the register pressure bites)."""
 import re
@@ -41,12 +43,14 @@ def regs_of(text):
     return out
 
 
-def kernels(txt, pp=False, sarah=False):
+def kernels(txt, pp=False, sarah=False, steps=False):
     """(name, body) of every k_svrg_iter instantiation and of k_svrg_outer; pp: also k_svrg_outer_pp and k_svrg_span_pp;
-    sarah: the k_sarah_iter and k_sarah_iter_pp instantiations instead"""
+    sarah: the k_sarah_iter and k_sarah_iter_pp instantiations instead; steps: the k_grad_step and k_saga_iter instantiations instead"""
     names = ('_ZN3pnp11k_svrg_iter', '_ZN3pnp12k_svrg_outer') + (('_ZN3pnp15k_svrg_outer_pp', '_ZN3pnp14k_svrg_span_pp') if pp else ())
     if sarah:
         names = ('_ZN3pnp12k_sarah_iter', '_ZN3pnp15k_sarah_iter_pp')
+    if steps:
+        names = ('_ZN3pnp11k_grad_step', '_ZN3pnp11k_saga_iter')
     lines = txt.split('\n')
     i = 0
     while i < len(lines):
@@ -165,16 +169,17 @@ def main():
     defines = [a for a in args if a.startswith('-D')]          # e.g. -DPNP_FUSED_CLOCK: the diagnostic build
     pp = '--pp' in args                                         # also the per-problem loops: k_svrg_outer_pp, k_svrg_span_pp
     sarah = '--sarah' in args                                   # the SARAH instantiations instead, with the store rule
+    steps = '--steps' in args                                   # the minibatch forms instead, with the store rule
     paths = [a for a in args if not a.startswith('-')]
     txt = listing(paths[0] if paths else None, defines)
     bad = []
     nk = 0
-    for name, body in kernels(txt, pp, sarah):
+    for name, body in kernels(txt, pp, sarah, steps):
         nk += 1
         errors, n_loads, n_waits, segs = check(name, body)
         spill = ' '.join(f'{i}:{s["sst"]}/{s["sld"]}' for i, s in enumerate(segs) if s['sst'] or s['sld'])
         stores = ''
-        if sarah:
+        if sarah or steps:
             st_errors, n_st = check_stores(name, body)
             errors = errors + st_errors
             stores = f'{n_st} hand-issued stores, '
