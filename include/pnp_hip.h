@@ -298,6 +298,66 @@ int pnp_csmri_svrg_span_pp(pnp_csmri_plan* plan, void* z, void* w, void* mu, con
                            double lr, const double* lr_pp, int mini_batch_size, const int32_t* mb_vec, double sigma_modifier,
                            const double* sigma_modifier_pp, double fallback_sigma, const void* xrec, double* sse_log,
                            int log_row0, int n_log, void* sigma_out, void* stream);
+/* A whole OUTER iteration of the SARAH loop with the TV prox -- algorithms/pnp_sarah.py:28-104 for T2 inner iterations -- in ONE
+ * launch: the workgroup that owns a problem runs the outer step, pnp_csmri_svrg_outer_step (w_out = w_prev, mu_out = v_prev,
+ * out = w_next, lr = eta: w_prev = z, v_prev = grad_full(z), w_next = prox_TV(z - eta * v_prev); z is NOT written and eta does not
+ * decay), and then T2 times pnp_csmri_sarah_step (a = w_next, b = w_prev, alpha = 1 / mini_batch_size, beta = 1,
+ * c1 = v_prev, gamma = -lr, c2 = z, v_out = v_prev, out = z, out2 = w_prev) on THAT problem back to back; the results are bit for
+ * bit those of the T2 + 1 separate calls.  z, w_prev and v_prev are updated in place, w_next is an output.
+ *   selbits  [T2][batch][W][H/32]: slot j = the selector of inner iteration j.  Unlike pnp_csmri_svrg_outer_iteration, slot 0 IS
+ *            read: the outer step is no inner iteration, the inner loop runs j = 0 .. T2 - 1 behind it;
+ *   sse_log  [n_log][batch] double, T2 + 1 rows per call: the outer prox writes row log_row0 % n_log, inner iteration j row
+ *            (log_row0 + 1 + j) % n_log;
+ *   sigma_out [batch]: the noise estimate of the last inner iteration.
+ * The _pp form: eta_pp, lr_pp, sigma_modifier_pp double [batch], mb_vec int32 [batch], each nullable; converted as
+ * pnp_csmri_svrg_outer_step_pp (the outer step: -eta_pp[b]) and pnp_csmri_sarah_step_pp (1 / mb_vec[b] taken in double as the host
+ * takes it, -lr_pp[b]) convert them: problem b equals problem b of the plain call made with its scalars.
+ * PNP_ERR_ARG before any device work: a NULL plan, z, w_prev, w_next, v_prev, mask_bitsT, yh, alpha_vec, selbits, xrec, sse_log or
+ * sigma_out; T2 <= 0; n_log < 1; log_row0 < 0; mini_batch_size <= 0 with a NULL mb_vec; a plan that is not f32 256 x 256; z, w_prev,
+ * w_next, v_prev not four distinct buffers.                                                                          */
+int pnp_csmri_sarah_outer_iteration(pnp_csmri_plan* plan, void* z, void* w_prev, void* w_next, void* v_prev,
+                                    const uint32_t* mask_bitsT, const void* yh, const void* alpha_vec, const uint32_t* selbits,
+                                    int T2, double eta, double lr, int mini_batch_size, double sigma_modifier,
+                                    double fallback_sigma, const void* xrec, double* sse_log, int log_row0, int n_log,
+                                    void* sigma_out, void* stream);
+int pnp_csmri_sarah_outer_iteration_pp(pnp_csmri_plan* plan, void* z, void* w_prev, void* w_next, void* v_prev,
+                                       const uint32_t* mask_bitsT, const void* yh, const void* alpha_vec, const uint32_t* selbits,
+                                       int T2, double eta, const double* eta_pp, double lr, const double* lr_pp,
+                                       int mini_batch_size, const int32_t* mb_vec, double sigma_modifier,
+                                       const double* sigma_modifier_pp, double fallback_sigma, const void* xrec, double* sse_log,
+                                       int log_row0, int n_log, void* sigma_out, void* stream);
+/* n_steps consecutive inner iterations of the GD or the SGD loop -- algorithms/pnp_gd.py:24-70, pnp_sgd.py:24-70 -- with the TV prox
+ * in ONE launch, z in place: the workgroup that owns a problem runs n_steps times pnp_csmri_grad_step_pp (a = c1 = out = z) on THAT
+ * problem back to back; the results are bit for bit those of the separate calls.  The arguments are those of
+ * pnp_csmri_grad_step_pp without out and c1 and with sse_out replaced by the span's log.  Exactly one of yh and YT:
+ *   yh (GD):  bitsT [batch][W][H/32] = the mask, the same array at every step;
+ *   YT (SGD): bitsT [n_steps][batch][W][H/32] = drawn selbits, slot i = the selector of step i.
+ *   sse_log  [n_log][batch] double: step i writes row (log_row0 + i) % n_log;  sigma_out [batch]: the last step's estimate.
+ * The kernels hold the prox: denoise must be != 0.
+ * PNP_ERR_ARG before any device work: a NULL plan, z, bitsT, xrec, sse_log or sigma_out; both or neither of yh and YT;
+ * n_steps <= 0; n_log < 1; log_row0 < 0; denoise == 0; a plan that is not f32 256 x 256.                              */
+int pnp_csmri_grad_span(pnp_csmri_plan* plan, void* z, const uint32_t* bitsT, const void* yh, const void* YT, double alpha,
+                        const double* alpha_pp, const void* alpha_vec, double beta, int denoise, double sigma_modifier,
+                        const double* sigma_modifier_pp, double fallback_sigma, const void* xrec, int n_steps, double* sse_log,
+                        int log_row0, int n_log, void* sigma_out, void* stream);
+/* n_steps consecutive inner iterations of the SAGA loop -- algorithms/pnp_saga.py:43-79 -- with the TV prox in ONE launch: the
+ * workgroup that owns a problem runs n_steps times pnp_csmri_saga_step_pp (out = z) on THAT problem back to back; the results are bit
+ * for bit those of the separate calls.  table, sum and z are updated in place (there is no `out`).  The arguments are those of
+ * pnp_csmri_saga_step_pp with
+ *   bitsT     [n_steps][batch][W][H/32]: drawn selbits, slot i = the selector of step i;
+ *   rows      int32 [n_steps][batch]: step i replaces row rows[i][b] of problem b;
+ *   prev_row0 int32 [batch]: the row the step before the span replaced.  Step i takes prev = rows[i - 1][b] (prev_row0[b] at i = 0);
+ *             rows[i][b] == prev is legal.  Entries in [0, hist): the kernel cannot check them (the Python front end checks its host
+ *             copy and raises);
+ *   sse_log, log_row0, n_log, sigma_out as in pnp_csmri_grad_span.  denoise must be != 0.
+ * PNP_ERR_ARG before any device work: a NULL plan, z, bitsT, YT, table, rows, prev_row0, sum, xrec, sse_log or sigma_out;
+ * hist < 1; n_steps <= 0; n_log < 1; log_row0 < 0; denoise == 0; a plan that is not f32 256 x 256; table or sum overlapping z, xrec
+ * or each other.                                                                                                     */
+int pnp_csmri_saga_span(pnp_csmri_plan* plan, void* z, const uint32_t* bitsT, const void* YT, double alpha, const double* alpha_pp,
+                        const void* alpha_vec, void* table, const int32_t* rows, const int32_t* prev_row0, void* sum, double lr,
+                        const double* lr_pp, double inv_hist, int hist, int denoise, double sigma_modifier,
+                        const double* sigma_modifier_pp, double fallback_sigma, const void* xrec, int n_steps, double* sse_log,
+                        int log_row0, int n_log, void* sigma_out, void* stream);
 /* pnp_prox_tv / pnp_prox_wavelet2d with sigma used = sigma_est * (sigma_modifier_pp ? sigma_modifier_pp[b] : sigma_modifier). */
 int pnp_prox_tv_pp(const void* z_in, void* z_out, int H, int W, int batch, int dtype, const void* sigma_in,
                    double sigma_modifier, const double* sigma_modifier_pp, double fallback_sigma, const void* xrec,

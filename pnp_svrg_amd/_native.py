@@ -105,6 +105,14 @@ SIGNATURES = {
     'pnp_csmri_svrg_span_pp': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _d, _vp, _i, _vp, _d, _vp, _d, _vp, _vp, _i,
                                     _i, _vp, _vp]),
     'pnp_refresh_pp': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _sz, _i, _i, _vp]),
+    # one launch per SARAH outer iteration; n-step spans of the GD / SGD / SAGA inner iteration
+    'pnp_csmri_sarah_outer_iteration': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _d, _d, _i, _d, _d, _vp, _vp, _i, _i, _vp,
+                                             _vp]),
+    'pnp_csmri_sarah_outer_iteration_pp': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _d, _vp, _d, _vp, _i, _vp, _d, _vp, _d,
+                                                _vp, _vp, _i, _i, _vp, _vp]),
+    'pnp_csmri_grad_span': (_i, [_vp, _vp, _vp, _vp, _vp, _d, _vp, _vp, _d, _i, _d, _vp, _d, _vp, _i, _vp, _i, _i, _vp, _vp]),
+    'pnp_csmri_saga_span': (_i, [_vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp, _vp, _vp, _d, _vp, _d, _i, _i, _d, _vp, _d, _vp, _i, _vp,
+                                 _i, _i, _vp, _vp]),
     # the data-fidelity objective per problem (csrc/objective.hip): f_out [batch] doubles
     'pnp_csmri_objective': (_i, [_vp, _vp, _vp, _vp, _d, _vp, _vp]),
     'pnp_deblur_objective': (_i, [_vp, _vp, _vp, _d, _vp, _vp]),

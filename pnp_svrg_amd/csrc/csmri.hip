@@ -346,6 +346,16 @@ int csmri_sarah_launch(int batch, const void* twtab, const void* a, const void* 
                        const void* alpha_vec, double beta, const void* c1, double gamma, const void* c2, void* v_out, void* out,
                        void* out2, int mode, double sigma_modifier, double fallback_sigma, const void* xrec, double* sse_out,
                        void* sigma_out, void* stream, const double* alpha_pp, const double* gamma_pp, const double* sm_pp);
+int csmri_sarah_outer_launch(int batch, const void* twtab, void* z, void* w_prev, void* w_next, void* v_prev, const uint32_t* mask_bits,
+                             const void* yh, const void* alpha_vec, const uint32_t* selbits, int T2, double eta, const double* eta_pp,
+                             double lr, const double* lr_pp, int mini_batch_size, const int32_t* mb_vec, double sigma_modifier,
+                             const double* sm_pp, double fallback_sigma, const void* xrec, double* sse_log, int log_row0, int n_log,
+                             void* sigma_out, void* stream);
+int csmri_step_span_launch(int batch, const void* twtab, void* z, const uint32_t* bits, const void* yh, const void* YT, double alpha,
+                           const void* alpha_vec, double beta, void* table, const int32_t* rows, const int32_t* prev_row0, void* sum,
+                           double lr, double inv_hist, int n_steps, double sigma_modifier, double fallback_sigma, const void* xrec,
+                           double* sse_log, int log_row0, int n_log, void* sigma_out, void* stream, const double* alpha_pp,
+                           const double* lr_pp, const double* sm_pp);
 int csmri_minibatch_launch(int batch, const void* twtab, const void* a, const uint32_t* bitsT, const void* YT, double alpha,
                            const void* alpha_vec, double beta, const void* c1, void* table, const int32_t* row, const int32_t* prev_row,
                            void* sum, double lr, double inv_hist, void* out, int mode, double sigma_modifier, double fallback_sigma,
@@ -633,4 +643,84 @@ extern "C" int pnp_csmri_svrg_span_pp(pnp_csmri_plan* p, void* z, void* w, void*
     return csmri_fused_span_launch(p->batch, p->twtab, z, w, mu, mask_bitsT, yh, alpha_vec, selbits, step0, n_steps, T2, t2_vec, lr, lr_pp,
                                    mini_batch_size, mb_vec, sigma_modifier, sigma_modifier_pp, fallback_sigma, xrec, sse_log, log_row0,
                                    n_log, sigma_out, stream);
+}
+
+// ---- a whole SARAH outer iteration (outer step + T2 inner iterations, TV prox, T2 + 1 log rows) in one launch
+static int sarah_outer_impl(pnp_csmri_plan* p, void* z, void* w_prev, void* w_next, void* v_prev, const uint32_t* mask_bitsT,
+                            const void* yh, const void* alpha_vec, const uint32_t* selbits, int T2, double eta, const double* eta_pp,
+                            double lr, const double* lr_pp, int mini_batch_size, const int32_t* mb_vec, double sigma_modifier,
+                            const double* sigma_modifier_pp, double fallback_sigma, const void* xrec, double* sse_log, int log_row0,
+                            int n_log, void* sigma_out, void* stream) {
+    PNP_CHECK_ARG(p && z && w_prev && w_next && v_prev && mask_bitsT && yh && alpha_vec && selbits && xrec && sse_log && sigma_out,
+                  "null argument");
+    PNP_CHECK_ARG(T2 >= 1 && T2 <= INT32_MAX - 1 && (mb_vec != nullptr || mini_batch_size >= 1) && n_log >= 1 && log_row0 >= 0 &&
+                  log_row0 <= INT32_MAX - 1 - T2, "bad T2 / mini_batch_size / log");
+    PNP_CHECK_ARG(p->dtype == PNP_F32 && p->H == 256 && p->W == 256, "the one-kernel iteration exists for f32 plans of 256 x 256");
+    PNP_CHECK_ARG(z != w_prev && z != w_next && z != v_prev && w_prev != w_next && w_prev != v_prev && w_next != v_prev,
+                  "z, w_prev, w_next and v_prev must be buffers of their own");
+    return csmri_sarah_outer_launch(p->batch, p->twtab, z, w_prev, w_next, v_prev, mask_bitsT, yh, alpha_vec, selbits, T2, eta, eta_pp, lr,
+                                    lr_pp, mini_batch_size, mb_vec, sigma_modifier, sigma_modifier_pp, fallback_sigma, xrec, sse_log,
+                                    log_row0, n_log, sigma_out, stream);
+}
+
+extern "C" int pnp_csmri_sarah_outer_iteration(pnp_csmri_plan* p, void* z, void* w_prev, void* w_next, void* v_prev,
+                                               const uint32_t* mask_bitsT, const void* yh, const void* alpha_vec, const uint32_t* selbits,
+                                               int T2, double eta, double lr, int mini_batch_size, double sigma_modifier,
+                                               double fallback_sigma, const void* xrec, double* sse_log, int log_row0, int n_log,
+                                               void* sigma_out, void* stream) {
+    PNP_CHECK_ARG(mini_batch_size >= 1, "bad T2 / mini_batch_size / log");
+    return sarah_outer_impl(p, z, w_prev, w_next, v_prev, mask_bitsT, yh, alpha_vec, selbits, T2, eta, nullptr, lr, nullptr,
+                            mini_batch_size, nullptr, sigma_modifier, nullptr, fallback_sigma, xrec, sse_log, log_row0, n_log, sigma_out,
+                            stream);
+}
+
+extern "C" int pnp_csmri_sarah_outer_iteration_pp(pnp_csmri_plan* p, void* z, void* w_prev, void* w_next, void* v_prev,
+                                                  const uint32_t* mask_bitsT, const void* yh, const void* alpha_vec,
+                                                  const uint32_t* selbits, int T2, double eta, const double* eta_pp, double lr,
+                                                  const double* lr_pp, int mini_batch_size, const int32_t* mb_vec, double sigma_modifier,
+                                                  const double* sigma_modifier_pp, double fallback_sigma, const void* xrec,
+                                                  double* sse_log, int log_row0, int n_log, void* sigma_out, void* stream) {
+    return sarah_outer_impl(p, z, w_prev, w_next, v_prev, mask_bitsT, yh, alpha_vec, selbits, T2, eta, eta_pp, lr, lr_pp, mini_batch_size,
+                            mb_vec, sigma_modifier, sigma_modifier_pp, fallback_sigma, xrec, sse_log, log_row0, n_log, sigma_out, stream);
+}
+
+// ---- n_steps GD or SGD inner iterations in one launch, z in place (yh: the GD form on the mask; YT: the SGD form on n_steps drawn slots)
+extern "C" int pnp_csmri_grad_span(pnp_csmri_plan* p, void* z, const uint32_t* bitsT, const void* yh, const void* YT, double alpha,
+                                   const double* alpha_pp, const void* alpha_vec, double beta, int denoise, double sigma_modifier,
+                                   const double* sigma_modifier_pp, double fallback_sigma, const void* xrec, int n_steps, double* sse_log,
+                                   int log_row0, int n_log, void* sigma_out, void* stream) {
+    PNP_CHECK_ARG(p && z && bitsT && xrec && sse_log && sigma_out, "null argument");
+    PNP_CHECK_ARG((yh != nullptr) != (YT != nullptr), "pass the packed data term (yh) or the raw data (YT), exactly one of them");
+    PNP_CHECK_ARG(n_steps >= 1 && n_log >= 1 && log_row0 >= 0 && log_row0 <= INT32_MAX - n_steps, "bad n_steps / log");
+    PNP_CHECK_ARG(denoise != 0, "the span kernels hold the TV prox: denoise must be != 0");
+    PNP_CHECK_ARG(p->dtype == PNP_F32 && p->H == 256 && p->W == 256, "the one-kernel iteration exists for f32 plans of 256 x 256");
+    return csmri_step_span_launch(p->batch, p->twtab, z, bitsT, yh, YT, alpha, alpha_vec, beta, nullptr, nullptr, nullptr, nullptr, 0.0, 0.0,
+                                  n_steps, sigma_modifier, fallback_sigma, xrec, sse_log, log_row0, n_log, sigma_out, stream, alpha_pp,
+                                  nullptr, sigma_modifier_pp);
+}
+
+// ---- n_steps SAGA inner iterations in one launch; table, sum and z in place
+extern "C" int pnp_csmri_saga_span(pnp_csmri_plan* p, void* z, const uint32_t* bitsT, const void* YT, double alpha, const double* alpha_pp,
+                                   const void* alpha_vec, void* table, const int32_t* rows, const int32_t* prev_row0, void* sum, double lr,
+                                   const double* lr_pp, double inv_hist, int hist, int denoise, double sigma_modifier,
+                                   const double* sigma_modifier_pp, double fallback_sigma, const void* xrec, int n_steps, double* sse_log,
+                                   int log_row0, int n_log, void* sigma_out, void* stream) {
+    PNP_CHECK_ARG(p && z && bitsT && YT && table && rows && prev_row0 && sum && xrec && sse_log && sigma_out, "null argument");
+    PNP_CHECK_ARG(hist >= 1, "need hist >= 1");
+    PNP_CHECK_ARG(n_steps >= 1 && n_log >= 1 && log_row0 >= 0 && log_row0 <= INT32_MAX - n_steps, "bad n_steps / log");
+    PNP_CHECK_ARG(denoise != 0, "the span kernels hold the TV prox: denoise must be != 0");
+    PNP_CHECK_ARG(p->dtype == PNP_F32 && p->H == 256 && p->W == 256, "the one-kernel iteration exists for f32 plans of 256 x 256");
+    {   // as pnp_csmri_saga_step: table [hist][batch][H][W] and sum [batch][H][W] are written while z and xrec are read or written
+        const size_t img = (size_t)p->batch * 256 * 256 * sizeof(float);
+        auto overlap = [](const void* x, size_t nx, const void* y, size_t ny) {
+            const uintptr_t a0 = (uintptr_t)x, b0 = (uintptr_t)y;
+            return x != nullptr && y != nullptr && a0 < b0 + ny && b0 < a0 + nx;
+        };
+        const size_t tb = img * (size_t)hist;
+        PNP_CHECK_ARG(!overlap(table, tb, z, img) && !overlap(table, tb, xrec, img) && !overlap(sum, img, z, img) &&
+                      !overlap(sum, img, xrec, img) && !overlap(table, tb, sum, img), "table and sum must not alias z, xrec or each other");
+    }
+    return csmri_step_span_launch(p->batch, p->twtab, z, bitsT, nullptr, YT, alpha, alpha_vec, 0.0, table, rows, prev_row0, sum, lr, inv_hist,
+                                  n_steps, sigma_modifier, fallback_sigma, xrec, sse_log, log_row0, n_log, sigma_out, stream, alpha_pp, lr_pp,
+                                  sigma_modifier_pp);
 }

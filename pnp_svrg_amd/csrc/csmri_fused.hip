@@ -754,7 +754,10 @@ __device__ __forceinline__ void startup_stagger(int stagger_n, int stagger_group
 // SARAH: 0 = the SVRG forms; 1 = the SARAH form (v_out stored from the epilogue, then c2 folded in: sarah_epilogue); 2 = the same with
 // a second destination out2 of the final store; 3 = the SAGA form (the data term from YT, then saga_epilogue on `saga`).  A template
 // parameter like the others: the epilogue stays straight-line code.  YTERM: the data term from YT and the selector (fused_gradient).
-template <int MODE, bool OUTER, int NOPS, int SARAH = 0, bool YTERM = false>
+// TAG: nothing in the body reads it.  It gives a caller an instantiation of its own where the body had exactly ONE kernel as its caller
+// (k_grad_step<0>, k_saga_iter<0>): the lambdas of the last phase are inlined differently once they have a second call site, and that
+// kernel's register allocation changed with it (tools/hip_listing.py --against, --per-kernel).
+template <int MODE, bool OUTER, int NOPS, int SARAH = 0, bool YTERM = false, int TAG = 0>
 __device__ __forceinline__ void svrg_iter_body(unsigned char* lds_raw, FusedShared& sh, const float* a, const float* b,
                                                const uint32_t* __restrict__ bits, const cx<float>* __restrict__ yh,
                                                const cx<float>* __restrict__ twtab, float scale, float beta, const float* c1,
@@ -1220,6 +1223,143 @@ __global__ __launch_bounds__(FT) void k_saga_iter(const float* z, const uint32_t
                                       nullptr, nullptr, nullptr, nullptr, YT + img, &sa);
 }
 
+// A whole OUTER iteration of pnp_sarah with the TV prox in one launch (algorithms/pnp_sarah.py:28-104 for T2 inner iterations): the
+// workgroup that owns an image runs the outer step -- w_prev = z, v_prev = grad_full(z), w_next = prox(z - eta * v_prev), the folded
+// body of k_svrg_outer's first iteration with out = w_next, so z is NOT written and eta does not decay -- and then the T2
+// inner iterations of THAT image back to back, each the body of k_sarah_iter<FUSED_FULL, true>.  Between two iterations of one image
+// the data goes through memory, exactly as in k_svrg_outer.  Unlike k_svrg_outer the outer step is no inner iteration: slot 0 of
+// selbits IS read, the inner loop runs j = 0 .. T2 - 1 behind the outer step, and T2 + 1 log rows are written -- the outer prox to row
+// log_row0 % n_log, inner iteration j to row (log_row0 + 1 + j) % n_log.  selbits: [T2][batch][W][H/32].
+// ONE kernel serves the plain and the _pp entry point: eta_pp, lr_pp, sm_pp are DOUBLE [batch] arrays, mb_vec int32 [batch], each
+// may be NULL (the scalar then holds).  The conversions are those of the calls this launch replaces, expression for expression:
+// the outer step's gamma = (float)(-eta) (k_svrg_iter_pp, OUTER) and scale = 2^-16 * alpha_vec[b] (k_svrg_outer); the inner
+// iterations' alpha = 1 / mb in double (IEEE division, as the host forms it), scale = (float)(alpha * 2^-16) and gamma = (float)(-lr)
+// (k_sarah_iter_pp), sigma_modifier by one cast.
+__global__ __launch_bounds__(FT) void k_sarah_outer(float* z, float* w_prev, float* w_next, float* v_prev,
+                                                    const uint32_t* __restrict__ mask_bits, const cx<float>* __restrict__ yh,
+                                                    const float* __restrict__ alpha_vec, const uint32_t* __restrict__ selbits, int T2,
+                                                    double eta, const double* __restrict__ eta_pp, double lr,
+                                                    const double* __restrict__ lr_pp, int mini_batch_size,
+                                                    const int32_t* __restrict__ mb_vec, const cx<float>* __restrict__ twtab,
+                                                    float sigma_modifier, const double* __restrict__ sm_pp, float fallback_sigma,
+                                                    const float* __restrict__ xrec, double* __restrict__ sse_log, int log_row0, int n_log,
+                                                    float* __restrict__ sigma_out) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    __shared__ FusedShared sh;
+    const int prob = blockIdx.x, batch = gridDim.x;
+    if (eta_pp != nullptr) eta = eta_pp[prob];
+    if (lr_pp != nullptr) lr = lr_pp[prob];
+    if (mb_vec != nullptr) mini_batch_size = mb_vec[prob];
+    if (sm_pp != nullptr) sigma_modifier = (float)sm_pp[prob];
+    const double alpha = 1.0 / (double)mini_batch_size;
+    const float scale_inner = (float)(alpha * (1.0 / ((double)FN * (double)FN)));
+    const float gamma_outer = (float)(-eta), gamma_inner = (float)(-lr);
+    const size_t img = (size_t)prob * FN * FN;
+    const float inv_n = 1.0f / ((float)FN * (float)FN);
+    float* zi = z + img;
+    // the outer step (pnp_csmri_svrg_outer_step with out = w_next, w_out = w_prev, mu_out = v_prev)
+    svrg_iter_body<FUSED_FULL, true, 0>(lds_raw, sh, zi, nullptr, mask_bits + (size_t)prob * FN * 8, yh + (size_t)prob * (FN / 2) * FN, twtab,
+                                        inv_n * alpha_vec[prob], 1.0f, zi, gamma_outer, nullptr, w_next + img, sigma_modifier, fallback_sigma,
+                                        xrec + img, sse_log + (size_t)(log_row0 % n_log) * batch + prob, sigma_out + prob, w_prev + img,
+                                        v_prev + img);
+#pragma unroll 1
+    for (int j = 0; j < T2; ++j) {
+        // this iteration reads what the last one wrote (same lanes, same addresses): stores done, no stale line in the L1
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        __syncthreads();
+        svrg_iter_body<FUSED_FULL, false, 2, 2>(lds_raw, sh, w_next + img, w_prev + img, selbits + ((size_t)j * batch + prob) * FN * 8, nullptr,
+                                                twtab, scale_inner, 1.0f, v_prev + img, gamma_inner, zi, zi, sigma_modifier, fallback_sigma,
+                                                xrec + img, sse_log + (size_t)((log_row0 + 1 + j) % n_log) * batch + prob, sigma_out + prob,
+                                                nullptr, nullptr, v_prev + img, w_prev + img);
+    }
+}
+
+// n_steps consecutive GD or SGD inner iterations of every problem in one launch, z in place (pnp_csmri_grad_span;
+// algorithms/pnp_gd.py:24-70 / pnp_sgd.py:24-70 with a = c1 = out = z): step i is the body of the per-iteration kernel it replaces --
+// YTERM = false (GD): k_svrg_iter<FUSED_FULL, false, 1> on the packed data term yh and the SAME selector bits ([batch][W][H/32], the
+// mask) at every step; YTERM = true (SGD): k_grad_step<FUSED_FULL> on the raw data YT and slot i of bits ([n_steps][batch][W][H/32]).
+// (The SGD body and k_saga_span's are instantiations of their own, TAG = 1: see svrg_iter_body.)
+// Between two steps the data goes through memory as in k_svrg_outer.  alpha_pp, sm_pp: DOUBLE [batch] or NULL, converted expression
+// for expression as in k_grad_step, so ONE kernel serves the plain and the per-problem call.  sse_log row (log_row0 + i) % n_log.
+template <bool YTERM>
+__global__ __launch_bounds__(FT) void k_grad_span(float* z, const uint32_t* __restrict__ bits, const cx<float>* __restrict__ yh,
+                                                  const cx<float>* __restrict__ YT, const cx<float>* __restrict__ twtab, float scale,
+                                                  const float* __restrict__ alpha_vec, float beta, int n_steps, float sigma_modifier,
+                                                  float fallback_sigma, const float* __restrict__ xrec, double* __restrict__ sse_log,
+                                                  int log_row0, int n_log, float* __restrict__ sigma_out,
+                                                  const double* __restrict__ alpha_pp, const double* __restrict__ sm_pp) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    __shared__ FusedShared sh;
+    const int prob = blockIdx.x, batch = gridDim.x;
+    const size_t img = (size_t)prob * FN * FN;
+    if (alpha_pp != nullptr) scale = (float)(alpha_pp[prob] * (1.0 / ((double)FN * (double)FN)));
+    if (alpha_vec != nullptr) scale *= alpha_vec[prob];
+    if (sm_pp != nullptr) sigma_modifier = (float)sm_pp[prob];
+    float* zi = z + img;
+#pragma unroll 1
+    for (int i = 0; i < n_steps; ++i) {
+        if (i > 0) {
+            // this step reads what the last one wrote (same lanes, same addresses): stores done, no stale line in the L1
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            __syncthreads();
+        }
+        double* sse_row = sse_log + (size_t)((log_row0 + i) % n_log) * batch + prob;
+        if constexpr (YTERM)
+            svrg_iter_body<FUSED_FULL, false, 1, 0, true, 1>(lds_raw, sh, zi, nullptr, bits + ((size_t)i * batch + prob) * FN * 8, nullptr,
+                                                             twtab, scale, beta, zi, 0.f, nullptr, zi, sigma_modifier, fallback_sigma,
+                                                             xrec + img, sse_row, sigma_out + prob, nullptr, nullptr, nullptr, nullptr,
+                                                             YT + img);
+        else
+            svrg_iter_body<FUSED_FULL, false, 1>(lds_raw, sh, zi, nullptr, bits + (size_t)prob * FN * 8, yh + (size_t)prob * (FN / 2) * FN,
+                                                 twtab, scale, beta, zi, 0.f, nullptr, zi, sigma_modifier, fallback_sigma, xrec + img,
+                                                 sse_row, sigma_out + prob, nullptr, nullptr);
+    }
+}
+
+// n_steps consecutive SAGA inner iterations of every problem in one launch (pnp_csmri_saga_span; algorithms/pnp_saga.py:43-79): step i
+// is the body of k_saga_iter<FUSED_FULL> on slot i of bits ([n_steps][batch][W][H/32]) with row = rows[i][b] and
+// prev = rows[i - 1][b] (prev_row0[b] at i = 0); rows: int32 [n_steps][batch], prev_row0: int32 [batch], plain wave-uniform loads.
+// row == prev is legal as it is there.  table, sum and z are updated where they lie; between two steps the data goes through memory as
+// in k_svrg_outer.  alpha_pp, lr_pp, sm_pp: DOUBLE [batch] or NULL, converted as in k_saga_iter.  sse_log row (log_row0 + i) % n_log.
+__global__ __launch_bounds__(FT) void k_saga_span(float* z, const uint32_t* __restrict__ bits, const cx<float>* __restrict__ YT,
+                                                  const cx<float>* __restrict__ twtab, float scale, const float* __restrict__ alpha_vec,
+                                                  float* table, const int32_t* __restrict__ rows, const int32_t* __restrict__ prev_row0,
+                                                  float* sum, float lr, float inv_hist, int n_steps, float sigma_modifier,
+                                                  float fallback_sigma, const float* __restrict__ xrec, double* __restrict__ sse_log,
+                                                  int log_row0, int n_log, float* __restrict__ sigma_out,
+                                                  const double* __restrict__ alpha_pp, const double* __restrict__ lr_pp,
+                                                  const double* __restrict__ sm_pp) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    __shared__ FusedShared sh;
+    const int prob = blockIdx.x, batch = gridDim.x;
+    const size_t img = (size_t)prob * FN * FN;
+    if (alpha_pp != nullptr) scale = (float)(alpha_pp[prob] * (1.0 / ((double)FN * (double)FN)));
+    if (alpha_vec != nullptr) scale *= alpha_vec[prob];
+    if (lr_pp != nullptr) lr = (float)lr_pp[prob];
+    if (sm_pp != nullptr) sigma_modifier = (float)sm_pp[prob];
+    float* zi = z + img;
+    int prev = prev_row0[prob];
+#pragma unroll 1
+    for (int i = 0; i < n_steps; ++i) {
+        if (i > 0) {
+            // this step reads what the last one wrote (same lanes, same addresses): stores done, no stale line in the L1
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            __syncthreads();
+        }
+        const int row = rows[(size_t)i * batch + prob];
+        SagaArgs sa = {table + ((size_t)row * batch + prob) * FN * FN, table + ((size_t)prev * batch + prob) * FN * FN, sum + img, lr, inv_hist};
+        asm volatile("" : "+s"(sa.slot), "+s"(sa.prev), "+s"(sa.sum));
+        svrg_iter_body<FUSED_FULL, false, 0, 3, false, 1>(lds_raw, sh, zi, nullptr, bits + ((size_t)i * batch + prob) * FN * 8, nullptr, twtab,
+                                                          scale, 0.f, nullptr, 0.f, nullptr, zi, sigma_modifier, fallback_sigma, xrec + img,
+                                                          sse_log + (size_t)((log_row0 + i) % n_log) * batch + prob, sigma_out + prob,
+                                                          nullptr, nullptr, nullptr, nullptr, YT + img, &sa);
+        prev = row;
+    }
+}
+
 // stagger (see startup_stagger): only launches of more than one workgroup per CU pay for it and profit from it
 static int stagger_config(int* num_cu_out, int* groups, int* units) {
     static int num_cu = 0, st_groups = 2, st_units = 40;    // same-box sweep (tools/dev/stagger_sweep.py): 0.588 ms per config-2 step without, 0.575 with (2, 40), slower from (8, 20) on
@@ -1260,6 +1400,10 @@ static int fused_lds_optin() {
         PNP_CHECK_HIP(hipFuncSetAttribute((const void*)k_svrg_outer, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F_LDS_BYTES));
         PNP_CHECK_HIP(hipFuncSetAttribute((const void*)k_svrg_outer_pp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F_LDS_BYTES));
         PNP_CHECK_HIP(hipFuncSetAttribute((const void*)k_svrg_span_pp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F_LDS_BYTES));
+        PNP_CHECK_HIP(hipFuncSetAttribute((const void*)k_sarah_outer, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F_LDS_BYTES));
+        PNP_CHECK_HIP(hipFuncSetAttribute((const void*)k_grad_span<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F_LDS_BYTES));
+        PNP_CHECK_HIP(hipFuncSetAttribute((const void*)k_grad_span<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F_LDS_BYTES));
+        PNP_CHECK_HIP(hipFuncSetAttribute((const void*)k_saga_span, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F_LDS_BYTES));
         attr_done |= 1ull << (dev & 63);
     }
     return PNP_OK;
@@ -1305,6 +1449,49 @@ int csmri_fused_span_launch(int batch, const void* twtab, void* z, void* w, void
                                                                    mini_batch_size, mb_vec, (const cx<float>*)twtab, (float)sigma_modifier,
                                                                    sm_pp, (float)fallback_sigma, (const float*)xrec, sse_log, log_row0,
                                                                    n_log, (float*)sigma_out);
+    PNP_CHECK_LAUNCH();
+    return PNP_OK;
+}
+
+// one launch = one SARAH outer iteration (k_sarah_outer): the coefficients are made in the kernel, from the doubles the host holds
+int csmri_sarah_outer_launch(int batch, const void* twtab, void* z, void* w_prev, void* w_next, void* v_prev, const uint32_t* mask_bits,
+                             const void* yh, const void* alpha_vec, const uint32_t* selbits, int T2, double eta, const double* eta_pp,
+                             double lr, const double* lr_pp, int mini_batch_size, const int32_t* mb_vec, double sigma_modifier,
+                             const double* sm_pp, double fallback_sigma, const void* xrec, double* sse_log, int log_row0, int n_log,
+                             void* sigma_out, void* stream) {
+    { const int rc = fused_lds_optin(); if (rc != PNP_OK) return rc; }
+    k_sarah_outer<<<batch, FT, F_LDS_BYTES, (hipStream_t)stream>>>((float*)z, (float*)w_prev, (float*)w_next, (float*)v_prev, mask_bits,
+                                                                  (const cx<float>*)yh, (const float*)alpha_vec, selbits, T2, eta, eta_pp, lr,
+                                                                  lr_pp, mini_batch_size, mb_vec, (const cx<float>*)twtab,
+                                                                  (float)sigma_modifier, sm_pp, (float)fallback_sigma, (const float*)xrec,
+                                                                  sse_log, log_row0, n_log, (float*)sigma_out);
+    PNP_CHECK_LAUNCH();
+    return PNP_OK;
+}
+
+// one launch = n_steps GD / SGD (table == NULL; YT != NULL selects the SGD form) or SAGA inner iterations of every problem, z in place
+// (k_grad_span, k_saga_span); scale and casts as csmri_minibatch_launch
+int csmri_step_span_launch(int batch, const void* twtab, void* z, const uint32_t* bits, const void* yh, const void* YT, double alpha,
+                           const void* alpha_vec, double beta, void* table, const int32_t* rows, const int32_t* prev_row0, void* sum,
+                           double lr, double inv_hist, int n_steps, double sigma_modifier, double fallback_sigma, const void* xrec,
+                           double* sse_log, int log_row0, int n_log, void* sigma_out, void* stream, const double* alpha_pp,
+                           const double* lr_pp, const double* sm_pp) {
+    const float scale = (float)(alpha / ((double)FN * (double)FN));
+    hipStream_t s = (hipStream_t)stream;
+    { const int rc = fused_lds_optin(); if (rc != PNP_OK) return rc; }
+    if (table != nullptr) {
+        k_saga_span<<<batch, FT, F_LDS_BYTES, s>>>((float*)z, bits, (const cx<float>*)YT, (const cx<float>*)twtab, scale, (const float*)alpha_vec,
+                                                  (float*)table, rows, prev_row0, (float*)sum, (float)lr, (float)inv_hist, n_steps,
+                                                  (float)sigma_modifier, (float)fallback_sigma, (const float*)xrec, sse_log, log_row0, n_log,
+                                                  (float*)sigma_out, alpha_pp, lr_pp, sm_pp);
+    } else {
+#define PNP_GSPAN_ARGS (float*)z, bits, (const cx<float>*)yh, (const cx<float>*)YT, (const cx<float>*)twtab, scale, (const float*)alpha_vec,   \
+                       (float)beta, n_steps, (float)sigma_modifier, (float)fallback_sigma, (const float*)xrec, sse_log, log_row0, n_log,     \
+                       (float*)sigma_out, alpha_pp, sm_pp
+        if (YT != nullptr) k_grad_span<true><<<batch, FT, F_LDS_BYTES, s>>>(PNP_GSPAN_ARGS);
+        else k_grad_span<false><<<batch, FT, F_LDS_BYTES, s>>>(PNP_GSPAN_ARGS);
+#undef PNP_GSPAN_ARGS
+    }
     PNP_CHECK_LAUNCH();
     return PNP_OK;
 }

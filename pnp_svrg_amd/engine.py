@@ -35,6 +35,9 @@ GdEngine, SgdEngine and SagaEngine take `fused=True` as well (opt-in, DESIGN 9.6
 (GD: the mask and its packed data term; SGD: the drawn slot and the raw data, the slot's data term formed inside the kernel) or ONE
 `pnp_csmri_saga_step` (gradient, table update, step and prox) on a float32 256 x 256 CsmriBatch, with the coefficients, draws and
 rows of the streaming step; without it the engines make exactly the calls they always made.
+The one-launch forms (opt-in): SarahEngine.run_outer(n, one_launch=True) runs every outer iteration as ONE draw launch plus
+ONE `pnp_csmri_sarah_outer_iteration`; GdEngine, SgdEngine and SagaEngine offer `run_span(n)`, launches of at most AHEAD steps of
+`pnp_csmri_grad_span` / `pnp_csmri_saga_span` -- the same bits as stepping; without them the engines make exactly the calls they made.
 Every engine takes `log_objective=True`: beside the squared errors, a second ring `obj_log` gets the data-fidelity
 objective f(z) of the iterate every logged prox returned (`batch.objective`, row for row with `sse_log`; `objective_log()` reads it
 back) -- the convergence signal on measured data, where there is no ground truth for a PSNR.  Such an engine steps eagerly
@@ -179,6 +182,20 @@ class _FusedStep:
             return self._hostbits
         return self.mbs.selbits[j]
 
+    def span_kernel_ok(self):
+        """Whether `run_span` can run its steps as launches of a span kernel (pnp_csmri_grad_span / pnp_csmri_saga_span): the
+        one-kernel iteration with the prox inside it (TV, no host-side per-call state), device-drawn minibatches, no objective log
+        and a constant step size (the coefficients of a launch are those of its first step)."""
+        mbs = getattr(self, 'mbs', None)
+        return (self.fused and getattr(self.prox, 'fused_denoise', False) and getattr(self.prox, 'denoise_strength', 0.0) == 0.0
+                and (mbs is None or all(h is None for h in mbs.host)) and not self.log_objective and self.lr_decay == 1.0)
+
+    def _span_done(self, m):
+        """The bookkeeping of m steps run inside one launch."""
+        self.s += m
+        self.n_prox += m
+        self.prox.t += m
+
     def _one_kernel(self, call, *args, **kw):
         b, px = self.b, self.prox
         sse_out = self.sse_log[self.n_prox % self.n_log]
@@ -191,6 +208,8 @@ class _FusedStep:
 class GdEngine(_FusedStep, LoopEngine):
     """pnp_gd over a batch (algorithms/pnp_gd.py:24-70): z <- prox(z - eta * decay^i * grad_full(z)).
     fused=True (opt-in): a step is ONE pnp_csmri_grad_step on the mask and its packed data term."""
+
+    AHEAD = 16                                                  # steps per span launch (the draw window of the stochastic engines)
 
     def __init__(self, batch, prox, eta, lr_decay=1.0, n_log=4096, seed=0, log_objective=False, *, fused=False):
         self.fused = bool(fused)
@@ -209,6 +228,23 @@ class GdEngine(_FusedStep, LoopEngine):
         self.b.grad_full(self.z, out=self.z, alpha=self._c('-lr', self.s, -lr), beta=1.0, c1=self.z)
         self.z = self._prox(self.z)
         self.s += 1
+
+    def run_span(self, n):
+        """n inner iterations.  Where `span_kernel_ok()` holds they run in launches of at most AHEAD steps, ONE pnp_csmri_grad_span
+        each, in which the workgroup that owns a problem runs its steps back to back -- the same bits as stepping; otherwise n
+        eager steps."""
+        if not self.span_kernel_ok():
+            for _ in range(n):
+                self.step()
+            return
+        b, px = self.b, self.prox
+        while n > 0:
+            m = min(n, self.AHEAD)
+            lr = self.eta * self.lr_decay ** self.s             # (span_kernel_ok: lr_decay == 1)
+            b.plan.grad_span(self.z, b.bits, m, b.xrec, self.sse_log, self.n_prox % self.n_log, px.sig, yh=b.yh_full,
+                             alpha=self._c('-lr', self.s, -lr), alpha_vec=b.inv_m0, beta=1.0, sigma_modifier=px.sigma_modifier)
+            self._span_done(m)
+            n -= m
 
 
 class _StochEngine(LoopEngine):
@@ -284,6 +320,25 @@ class SgdEngine(_FusedStep, _StochEngine):
         self.b.grad_stoch(self.z, self.mbs, j, out=self.z, alpha=self._c('-lr/mb', self.s, -lr / self.mb), beta=1.0, c1=self.z)
         self.z = self._prox(self.z)
         self.s += 1
+
+    def run_span(self, n):
+        """n inner iterations.  Where `span_kernel_ok()` holds they run in launches of at most AHEAD steps -- one draw of m steps from
+        the absolute step id plus ONE pnp_csmri_grad_span each, in which the workgroup that owns a problem runs its steps back to
+        back -- the same bits as stepping; otherwise n eager steps."""
+        if not self.span_kernel_ok():
+            for _ in range(n):
+                self.step()
+            return
+        b, px = self.b, self.prox
+        while n > 0:
+            m = min(n, self.AHEAD)
+            b.draw(self.mbs, self._mb_draw, self.seed, self.s, m, **self._draw_kw)
+            self._drawn_base = None                             # (a later eager step redraws its own window)
+            lr = self.eta * self.lr_decay ** self.s             # (span_kernel_ok: lr_decay == 1)
+            b.plan.grad_span(self.z, self.mbs.selbits, m, b.xrec, self.sse_log, self.n_prox % self.n_log, px.sig, YT=b.YT,
+                             alpha=self._c('-lr/mb', self.s, -lr / self.mb), beta=1.0, sigma_modifier=px.sigma_modifier)
+            self._span_done(m)
+            n -= m
 
 
 class SvrgEngine(_StochEngine):
@@ -722,9 +777,50 @@ class SarahEngine(_StochEngine):
             self.row_dev.fill_(self.n_prox % self.n_log)
             self._dev_step = self.s
 
-    def run_outer(self, n_outer=1):
-        """n_outer outer iterations = n_outer * T2 inner iterations (n_outer * (T2 + 1) log rows) as replays of the captured
-        hipGraph, from a step count that is a multiple of T2 -- the same bits as stepping."""
+    def outer_kernel_ok(self):
+        """Whether whole outer iterations can run as ONE launch each (pnp_csmri_sarah_outer_iteration): the one-kernel forms with the
+        prox inside the kernel (TV, no host-side per-call state), device-drawn minibatches, no objective log."""
+        return not self._outer_kernel_missing()
+
+    def _outer_kernel_missing(self):
+        missing = []
+        if not self.fused:
+            missing.append('fused=True')
+        if not getattr(self.prox, 'fused_denoise', False):
+            missing.append(f'a prox that runs inside the kernel: TVProx (got {type(self.prox).__name__})')
+        elif getattr(self.prox, 'denoise_strength', 0.0) != 0.0:
+            missing.append('denoise_strength == 0')
+        if not all(h is None for h in self.mbs.host):
+            missing.append('device-drawn minibatches (a slot holds a host-fed one)')
+        if self.log_objective:
+            missing.append('log_objective=False')
+        return missing
+
+    def run_outer(self, n_outer=1, one_launch=False):
+        """n_outer outer iterations = n_outer * T2 inner iterations (n_outer * (T2 + 1) log rows), from a step count that is a
+        multiple of T2 -- the same bits as stepping.  Default: replays of the captured hipGraph.  one_launch=True (opt-in, needs
+        `outer_kernel_ok()`): every outer iteration is ONE draw launch + ONE pnp_csmri_sarah_outer_iteration, in which the
+        workgroup that owns a problem runs the outer step (eta, no decay: F6) and its T2 inner iterations (eta * lr_decay ** k) back
+        to back."""
+        if one_launch:
+            missing = self._outer_kernel_missing()
+            if not (self.s % self.T2 == 0 and self.n_prox == self.s + self.s // self.T2):
+                missing.append(f'a step count that is a multiple of T2 (s = {self.s}, T2 = {self.T2})')
+            if missing:
+                raise ValueError('run_outer(one_launch=True) needs ' + ', '.join(missing))
+            b, px = self.b, self.prox
+            for _ in range(n_outer):
+                k = self.s // self.T2
+                b.draw(self.mbs, self._mb_draw, self.seed, self.s, self.T2, **self._draw_kw)
+                lr = self.eta * self.lr_decay ** k
+                b.plan.sarah_outer_iteration(self.z, self.w_prev, self.w_next, self.v_prev, b.bits, b.yh_full, b.inv_m0,
+                                             self.mbs.selbits, self.T2, self._c('eta', 0, self.eta), self._c('lr', k, lr),
+                                             self._mb_draw, b.xrec, self.sse_log, self.n_prox % self.n_log, px.sig,
+                                             sigma_modifier=px.sigma_modifier)
+                self.s += self.T2
+                self.n_prox += self.T2 + 1
+                px.t += self.T2 + 1
+            return
         if self.graph is None:
             self.capture()
         if not (self.s % self.T2 == 0 and self.n_prox == self.s + self.s // self.T2):
@@ -828,6 +924,46 @@ class SagaEngine(_FusedStep, _StochEngine):
                          self._c('lr', self.s, lr), 1.0 / self.hist, alpha=self._c('1/mb', 0, 1.0 / self.mb))
         self.r_prev = r
         self.s += 1
+
+    def run_span(self, n, r=None):
+        """n inner iterations.  r: the rows they replace -- None (n values from the engine's own stream, in the order `step()` takes
+        them), [n] (one per step for the whole batch) or [n][B] (one per step and problem).  Where `span_kernel_ok()` holds they run
+        in launches of at most AHEAD steps -- one draw of m steps from the absolute step id plus ONE pnp_csmri_saga_span each, in
+        which the workgroup that owns a problem runs its steps back to back -- the same bits as stepping, with r_prev left as
+        stepping leaves it; otherwise n eager steps."""
+        if r is None:
+            r = [int(self._rng.integers(self.hist)) for _ in range(n)]
+        r = np.asarray(r)
+        if r.shape not in ((n,), (n, self.b.B)):
+            raise ValueError(f'run_span: r holds one row per step ([{n}]) or per step and problem ([{n}][{self.b.B}]), got shape {r.shape}')
+        if not self.span_kernel_ok():
+            for i in range(n):
+                self.step(r=r[i] if r.ndim == 2 else int(r[i]))
+            return
+        if n < 1:
+            return
+        b, px = self.b, self.prox
+        if r.min() < 0 or r.max() >= self.hist:
+            raise ValueError(f'SAGA row outside the table: rows in [0, {self.hist}), got {np.ravel(r).tolist()}')
+        rows = np.ascontiguousarray(np.broadcast_to(r.reshape(n, -1), (n, b.B)), np.int32)
+        rows_dev = torch.from_numpy(rows).to(self.z.device)
+        prev, i0 = self._row_vec(self.r_prev), 0
+        while i0 < n:
+            m = min(n - i0, self.AHEAD)
+            b.draw(self.mbs, self._mb_draw, self.seed, self.s, m, **self._draw_kw)
+            self._drawn_base = None                             # (a later eager step redraws its own window)
+            lr = self.eta * self.lr_decay ** self.s             # (span_kernel_ok: lr_decay == 1)
+            b.plan.saga_span(self.z, self.mbs.selbits, b.YT, self.table, rows_dev[i0:i0 + m], prev, self.tsum, self._c('lr', self.s, lr),
+                             1.0 / self.hist, m, b.xrec, self.sse_log, self.n_prox % self.n_log, px.sig,
+                             alpha=self._c('1/mb', 0, 1.0 / self.mb), sigma_modifier=px.sigma_modifier)
+            self._span_done(m)
+            i0 += m
+            prev = rows_dev[i0 - 1]
+        if r.ndim == 1:                                         # as the last step leaves them: a row for the whole batch ...
+            self.r_prev = int(r[-1])
+        else:                                                   # ... or the rows of its batched update with their device vector
+            self.r_prev = r[-1].astype(np.int64)
+            self._rows = (self.r_prev, rows_dev[n - 1])
 
 
 def make_engine(batch, prox, eta, T2, mini_batch_size, lr_decay=1.0, variant='svrg', algorithm='svrg', hist_size=50, **kw):

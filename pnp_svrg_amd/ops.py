@@ -361,6 +361,70 @@ class CsmriPlan:
         N.call('pnp_csmri_svrg_span_pp', *args, float(fallback_sigma), _p(xrec), _p(sse_log), int(log_row0), int(sse_log.shape[0]),
                _p(sigma_out), _stream())
 
+    def _span_log(self, what, sse_log, sigma_out, *images):
+        """What the one-launch forms share: a float32 256 x 256 plan, whole-batch images, the [n_log, B] float64 log ring."""
+        self._one_kernel_plan(what)
+        for t in images:
+            assert t.dtype == self.dtype and t.numel() == self.B * self.H * self.W
+        assert sse_log.dtype == torch.float64 and sse_log.dim() == 2 and sse_log.shape[1] == self.B and sse_log.is_contiguous()
+        assert sigma_out.dtype == self.dtype and sigma_out.numel() == self.B
+
+    def sarah_outer_iteration(self, z, w_prev, w_next, v_prev, mask_bits, yh, alpha_vec, selbits, T2, eta, lr, mini_batch_size, xrec,
+                              sse_log, log_row0, sigma_out, *, sigma_modifier=1.0, fallback_sigma=0.0):
+        """pnp_csmri_sarah_outer_iteration: the outer step of pnp_sarah (w_prev = z, v_prev = grad_full(z), w_next = prox_TV(z - eta *
+        v_prev); z not written) + T2 inner iterations with the TV prox in ONE launch (z, w_prev, v_prev in place; w_next out).  T2 + 1
+        log rows from log_row0 on.  eta, lr, mini_batch_size, sigma_modifier: scalars, or [B] device tensors (float64; int32 for
+        mini_batch_size) -> the _pp entry point."""
+        self._span_log('sarah_outer_iteration', sse_log, sigma_out, z, w_prev, w_next, v_prev, xrec)
+        assert mask_bits.dtype == torch.int32 and tuple(mask_bits.shape) == (self.B, self.W, self.H // 32)
+        assert selbits.dtype == torch.int32 and tuple(selbits.shape) == (T2, self.B, self.W, self.H // 32)
+        if len({t.data_ptr() for t in (z, w_prev, w_next, v_prev)}) != 4:
+            raise ValueError('sarah_outer_iteration: z, w_prev, w_next and v_prev must be buffers of their own')
+        _route('pnp_csmri_sarah_outer_iteration',
+               [self._h, _p(z), _p(w_prev), _p(w_next), _p(v_prev), _p(mask_bits), _p(yh), _p(alpha_vec), _p(selbits), int(T2),
+                _pp(eta, self.B), _pp(lr, self.B), _pp(mini_batch_size, self.B, torch.int32), _pp(sigma_modifier, self.B),
+                float(fallback_sigma), _p(xrec), _p(sse_log), int(log_row0), int(sse_log.shape[0]), _p(sigma_out), _stream()])
+
+    def grad_span(self, z, bits, n_steps, xrec, sse_log, log_row0, sigma_out, *, yh=None, YT=None, alpha=1.0, beta=1.0, alpha_vec=None,
+                  sigma_modifier=1.0, fallback_sigma=0.0):
+        """pnp_csmri_grad_span: n_steps GD or SGD inner iterations with the TV prox in ONE launch, z in place.  yh with bits = the mask
+        [B, W, H/32] (GD, the same at every step) or YT with bits = drawn selbits [>= n_steps, B, W, H/32], slot i = step i (SGD) --
+        exactly one.  alpha, sigma_modifier: scalars or [B] float64 device tensors.  n_steps log rows from log_row0 on."""
+        self._span_log('grad_span', sse_log, sigma_out, z, xrec)
+        if (yh is None) == (YT is None):
+            raise ValueError('grad_span: pass the packed data term (yh) or the raw data (YT), exactly one of them')
+        assert bits.dtype == torch.int32
+        if yh is not None:
+            assert tuple(bits.shape) == (self.B, self.W, self.H // 32)
+            assert yh.dtype == _CDT[self.dtype] and tuple(yh.shape) == (self.B, self.W // 2, self.H)
+        else:
+            assert bits.dim() == 4 and bits.shape[0] >= n_steps and tuple(bits.shape[1:]) == (self.B, self.W, self.H // 32)
+            assert YT.dtype == _CDT[self.dtype] and tuple(YT.shape) == (self.B, self.W, self.H)
+        assert alpha_vec is None or (alpha_vec.dtype == self.dtype and alpha_vec.numel() == self.B)
+        a, sm = _pp(alpha, self.B), _pp(sigma_modifier, self.B)  # (scalar, array or NULL): the entry point has the _pp form only
+        N.call('pnp_csmri_grad_span', self._h, _p(z), _p(bits), _p(yh), _p(YT), a[0], _p(a[1]), _p(alpha_vec), float(beta), 1, sm[0],
+               _p(sm[1]), float(fallback_sigma), _p(xrec), int(n_steps), _p(sse_log), int(log_row0), int(sse_log.shape[0]),
+               _p(sigma_out), _stream())
+
+    def saga_span(self, z, bits, YT, table, rows, prev_row0, tsum, lr, inv_hist, n_steps, xrec, sse_log, log_row0, sigma_out, *,
+                  alpha=1.0, alpha_vec=None, sigma_modifier=1.0, fallback_sigma=0.0):
+        """pnp_csmri_saga_span: n_steps SAGA inner iterations with the TV prox in ONE launch; table, tsum and z in place.  bits: drawn
+        selbits [>= n_steps, B, W, H/32], slot i = step i; rows: int32 [n_steps, B] device tensor (step i replaces rows[i][b]);
+        prev_row0: int32 [B] (the row the step before the span replaced).  Row values must lie in [0, hist): the caller checks its
+        host copy.  alpha, lr, sigma_modifier: scalars or [B] float64 device tensors."""
+        self._span_log('saga_span', sse_log, sigma_out, z, tsum, xrec)
+        assert bits.dtype == torch.int32 and bits.dim() == 4 and bits.shape[0] >= n_steps
+        assert tuple(bits.shape[1:]) == (self.B, self.W, self.H // 32)
+        assert YT.dtype == _CDT[self.dtype] and tuple(YT.shape) == (self.B, self.W, self.H)
+        assert table.dtype == self.dtype and table.dim() >= 2 and table.shape[1] == self.B and table.numel() == table.shape[0] * z.numel()
+        assert rows.dtype == torch.int32 and tuple(rows.shape) == (n_steps, self.B)
+        assert prev_row0.dtype == torch.int32 and tuple(prev_row0.shape) == (self.B,)
+        assert alpha_vec is None or (alpha_vec.dtype == self.dtype and alpha_vec.numel() == self.B)
+        a, l, sm = _pp(alpha, self.B), _pp(lr, self.B), _pp(sigma_modifier, self.B)
+        N.call('pnp_csmri_saga_span', self._h, _p(z), _p(bits), _p(YT), a[0], _p(a[1]), _p(alpha_vec), _p(table), _p(rows), _p(prev_row0),
+               _p(tsum), l[0], _p(l[1]), float(inv_hist), int(table.shape[0]), 1, sm[0], _p(sm[1]), float(fallback_sigma), _p(xrec),
+               int(n_steps), _p(sse_log), int(log_row0), int(sse_log.shape[0]), _p(sigma_out), _stream())
+
 
 class DncnnPlan:
     """pnp_dncnn_plan_*: DnCNN-17 prox for B images of H x W (fp32 network on the f32 matrix cores).

@@ -154,7 +154,7 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
                 hist_size=50, H=256, W=256, dtype=torch.float32, max_batch=128, seeding='generator', variant='svrg', run_seed=1,
                 keep_trace=False, graph=True, kernel='Minimal', lr_decay=1.0, denoiser_kwargs=None, sigma_modifier=None,
                 shared_matrix=False, wide_trials=False, sarah_trials=False, t2_trials=False, objective=False, sarah_fused=False,
-                fused_steps=False):
+                fused_steps=False, one_launch=False):
     """Runner for `run_sweep` / `grid_search` over any cell of the reference's sweep (script_diff_sampratio_set12.py:23-25,
     41-51, 64-131): problem in {'csmri', 'deblur', 'pr'} x algorithm in {'gd', 'sgd', 'svrg', 'saga', 'sarah'} x denoiser in
     {'tv', 'nlm', factory}; `n_inner` inner iterations (prox evaluations of the stepped iterate) per item, hyper-parameters
@@ -206,6 +206,11 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
     DnCNN prox factory -- anything else is a ValueError that names the offender.  Rides through `run(items)` and through
     trial-batched grids (wide_trials=True for 'saga').  False (default): engines, launches, rows and messages are exactly what they
     were.
+    one_launch: opt in to the one-launch forms of those engines; needs sarah_fused=True or fused_steps=True (ValueError
+    otherwise).  With sarah_fused, batches with device-drawn minibatches run whole outer iterations as ONE
+    pnp_csmri_sarah_outer_iteration each (`run_outer(n, one_launch=True)`, where the engine's `outer_kernel_ok()` holds and the step
+    counts are multiples of T2); with fused_steps they advance by `run_span(n)`.  The same bits as without it.  False (default):
+    engines, launches, rows and messages are exactly what they were.
     Beside `run(items)` the runner offers the pieces of a trial-batched grid (`grid_search(batch_trials=True)`):
     `run.prepare_data(items)` builds a rank's batches WITHOUT engines, `run.run_trials(data, trials, max_batch_trials)` runs a list
     of trials ({'eta', 'mini_batch_size', 'sigma_modifier'} overrides) on them as tiled batches, `run.data_key` says which runners
@@ -248,6 +253,11 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
             raise ValueError(f"fused_steps=True needs the 'tv' denoiser or a DnCNN prox factory (got {denoiser!r})")
         if objective:
             raise ValueError('fused_steps=True needs objective=False (the one-kernel forms do not log the objective)')
+    if not isinstance(one_launch, (bool, np.bool_)):
+        raise ValueError(f'one_launch: True or False, got {one_launch!r}')
+    if one_launch and not (sarah_fused or fused_steps):
+        raise ValueError('one_launch=True needs sarah_fused=True or fused_steps=True (the one-launch forms are those of the one-kernel '
+                         'iterations)')
     eng_kw = {'log_objective': True} if objective else {}       # (off: the engines are made with the arguments they always got)
     if sarah_fused or fused_steps:
         eng_kw = dict(eng_kw, fused=True)                       # (rides with the other opt-in engine keyword)
@@ -364,6 +374,15 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
                 eng.run_span(n)
                 self.done += n
                 return
+            if one_launch and idx_d is None:                    # the one-launch forms (device-drawn minibatches only)
+                if fused_steps:
+                    eng.run_span(n)
+                    self.done += n
+                    return
+                if n % T2 == 0 and eng.s % T2 == 0 and eng.outer_kernel_ok():
+                    eng.run_outer(n // T2, one_launch=True)
+                    self.done += n
+                    return
             # device-drawn minibatches: whole outer iterations replay as hipGraphs (bit-identical to stepping; a rank's share
             # of a sweep is a small batch, where the ~25 launches of an inner iteration are a tenth of its time) -- when the
             # engine can be captured at all (an NLM prox ping-pongs between buffers and cannot: eager steps)
