@@ -358,6 +358,23 @@ int pnp_csmri_saga_span(pnp_csmri_plan* plan, void* z, const uint32_t* bitsT, co
                         const double* lr_pp, double inv_hist, int hist, int denoise, double sigma_modifier,
                         const double* sigma_modifier_pp, double fallback_sigma, const void* xrec, int n_steps, double* sse_log,
                         int log_row0, int n_log, void* sigma_out, void* stream);
+/* pnp_csmri_saga_step_pp and pnp_csmri_saga_span with the divisor of the running sum per problem: problem b multiplies its sum by
+ * inv_hist_pp ? inv_hist_pp[b] : inv_hist ([batch] doubles on the device, 1 / hist[b], cast to float as the scalar is cast and read
+ * once per workgroup).  `hist` is the row count of the table, the largest history length of the batch; problem b names rows below its
+ * own history length only (row, prev_row, rows, prev_row0: the caller checks its host copy), so the rows beyond it are never touched.
+ * Problem b equals, bit for bit, problem b of the plain call made with its own divisor.  Errors as the calls they extend.       */
+int pnp_csmri_saga_step_hist_pp(pnp_csmri_plan* plan, const void* z, const uint32_t* bitsT, const void* YT, double alpha,
+                                const double* alpha_pp, const void* alpha_vec, void* table, const int32_t* row,
+                                const int32_t* prev_row, void* sum, double lr, const double* lr_pp, double inv_hist,
+                                const double* inv_hist_pp, int hist, void* out, int denoise, double sigma_modifier,
+                                const double* sigma_modifier_pp, double fallback_sigma, const void* xrec, double* sse_out,
+                                void* sigma_out, void* stream);
+int pnp_csmri_saga_span_hist(pnp_csmri_plan* plan, void* z, const uint32_t* bitsT, const void* YT, double alpha,
+                             const double* alpha_pp, const void* alpha_vec, void* table, const int32_t* rows,
+                             const int32_t* prev_row0, void* sum, double lr, const double* lr_pp, double inv_hist,
+                             const double* inv_hist_pp, int hist, int denoise, double sigma_modifier,
+                             const double* sigma_modifier_pp, double fallback_sigma, const void* xrec, int n_steps, double* sse_log,
+                             int log_row0, int n_log, void* sigma_out, void* stream);
 /* pnp_prox_tv / pnp_prox_wavelet2d with sigma used = sigma_est * (sigma_modifier_pp ? sigma_modifier_pp[b] : sigma_modifier). */
 int pnp_prox_tv_pp(const void* z_in, void* z_out, int H, int W, int batch, int dtype, const void* sigma_in,
                    double sigma_modifier, const double* sigma_modifier_pp, double fallback_sigma, const void* xrec,
@@ -637,6 +654,13 @@ int pnp_saga_table_update(void* z, const void* g, void* slot, const void* prev, 
 int pnp_saga_table_update_pp(void* z, const void* g, void* table, const int32_t* row, const int32_t* prev_row, void* sum,
                              double lr, const double* lr_pp, double inv_hist, int hist, int batch, int N, int dtype,
                              void* stream);
+/* pnp_saga_table_update_pp with the divisor per problem: problem b steps with inv_hist_pp ? inv_hist_pp[b] : inv_hist ([batch] doubles
+ * on the device, 1 / hist[b], cast to `dtype` as the scalar is cast).  table [hist][batch][N] with hist the LARGEST history length of
+ * the batch; row[b], prev_row[b] lie below problem b's own history length (the caller checks them), so rows beyond it are never read
+ * or written.  Everything else, the PNP_ERR_ARG cases included, is pnp_saga_table_update_pp's; a NULL inv_hist_pp equals it.      */
+int pnp_saga_table_update_hist_pp(void* z, const void* g, void* table, const int32_t* row, const int32_t* prev_row, void* sum,
+                                  double lr, const double* lr_pp, double inv_hist, const double* inv_hist_pp, int hist, int batch,
+                                  int N, int dtype, void* stream);
 
 /* ------------------------------------------------------------------ elementwise
  * out = a*x + b*y + c*w   (y, w may be NULL); n = total element count.

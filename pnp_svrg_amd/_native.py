@@ -113,6 +113,12 @@ SIGNATURES = {
     'pnp_csmri_grad_span': (_i, [_vp, _vp, _vp, _vp, _vp, _d, _vp, _vp, _d, _i, _d, _vp, _d, _vp, _i, _vp, _i, _i, _vp, _vp]),
     'pnp_csmri_saga_span': (_i, [_vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp, _vp, _vp, _d, _vp, _d, _i, _i, _d, _vp, _d, _vp, _i, _vp,
                                  _i, _i, _vp, _vp]),
+    # per-problem hist_size for pnp_saga: the divisor of the running sum as a nullable [batch] double array
+    'pnp_saga_table_update_hist_pp': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _d, _vp, _d, _vp, _i, _i, _i, _i, _vp]),
+    'pnp_csmri_saga_step_hist_pp': (_i, [_vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp, _vp, _vp, _d, _vp, _d, _vp, _i, _vp, _i, _d, _vp, _d,
+                                         _vp, _vp, _vp, _vp]),
+    'pnp_csmri_saga_span_hist': (_i, [_vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp, _vp, _vp, _d, _vp, _d, _vp, _i, _i, _d, _vp, _d, _vp, _i,
+                                      _vp, _i, _i, _vp, _vp]),
     # the data-fidelity objective per problem (csrc/objective.hip): f_out [batch] doubles
     'pnp_csmri_objective': (_i, [_vp, _vp, _vp, _vp, _d, _vp, _vp]),
     'pnp_deblur_objective': (_i, [_vp, _vp, _vp, _d, _vp, _vp]),

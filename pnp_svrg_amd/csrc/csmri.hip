@@ -361,6 +361,11 @@ int csmri_minibatch_launch(int batch, const void* twtab, const void* a, const ui
                            void* sum, double lr, double inv_hist, void* out, int mode, double sigma_modifier, double fallback_sigma,
                            const void* xrec, double* sse_out, void* sigma_out, void* stream, const double* alpha_pp, const double* lr_pp,
                            const double* sm_pp);
+int csmri_saga_hist_launch(int batch, const void* twtab, const void* a, const uint32_t* bitsT, const void* YT, double alpha,
+                           const void* alpha_vec, void* table, const int32_t* row, const int32_t* prev_row, void* sum, double lr,
+                           double inv_hist, void* out, int mode, double sigma_modifier, double fallback_sigma, const void* xrec,
+                           double* sse_out, void* sigma_out, void* stream, const double* alpha_pp, const double* lr_pp, const double* sm_pp,
+                           const double* inv_hist_pp, int n_steps, int log_row0, int n_log);
 }
 
 namespace {
@@ -534,7 +539,7 @@ static int saga_step_impl(pnp_csmri_plan* p, const void* z, const uint32_t* bits
                           const void* alpha_vec, void* table, const int32_t* row, const int32_t* prev_row, void* sum, double lr,
                           const double* lr_pp, double inv_hist, int hist, void* out, int denoise, double sigma_modifier,
                           const double* sigma_modifier_pp, double fallback_sigma, const void* xrec, double* sse_out, void* sigma_out,
-                          void* stream) {
+                          void* stream, bool hist_form = false, const double* inv_hist_pp = nullptr) {
     PNP_CHECK_ARG(p && z && bitsT && YT && table && row && prev_row && sum && out, "null argument");
     PNP_CHECK_ARG(p->dtype == PNP_F32 && p->H == 256 && p->W == 256, "the one-kernel iteration exists for f32 plans of 256 x 256");
     PNP_CHECK_ARG(!(sse_out && !xrec), "sse_out needs xrec");
@@ -550,6 +555,10 @@ static int saga_step_impl(pnp_csmri_plan* p, const void* z, const uint32_t* bits
                       !overlap(sum, img, z, img) && !overlap(sum, img, out, img) && !overlap(sum, img, xrec, img) &&
                       !overlap(table, tb, sum, img), "table and sum must not alias z, out, xrec or each other");
     }
+    if (hist_form)                                              // the kernels that take the divisor per problem (NULL: the scalar)
+        return csmri_saga_hist_launch(p->batch, p->twtab, z, bitsT, YT, alpha, alpha_vec, table, row, prev_row, sum, lr, inv_hist, out,
+                                      denoise ? 0 : 1, sigma_modifier, fallback_sigma, xrec, sse_out, sigma_out, stream, alpha_pp, lr_pp,
+                                      sigma_modifier_pp, inv_hist_pp, 0, 0, 1);
     return csmri_minibatch_launch(p->batch, p->twtab, z, bitsT, YT, alpha, alpha_vec, 0.0, nullptr, table, row, prev_row, sum, lr, inv_hist,
                                   out, denoise ? 0 : 1, sigma_modifier, fallback_sigma, xrec, sse_out, sigma_out, stream, alpha_pp, lr_pp,
                                   sigma_modifier_pp);
@@ -570,6 +579,17 @@ extern "C" int pnp_csmri_saga_step_pp(pnp_csmri_plan* p, const void* z, const ui
                                       double fallback_sigma, const void* xrec, double* sse_out, void* sigma_out, void* stream) {
     return saga_step_impl(p, z, bitsT, YT, alpha, alpha_pp, alpha_vec, table, row, prev_row, sum, lr, lr_pp, inv_hist, hist, out, denoise,
                           sigma_modifier, sigma_modifier_pp, fallback_sigma, xrec, sse_out, sigma_out, stream);
+}
+
+// ---- pnp_csmri_saga_step_pp with the divisor per problem: inv_hist_pp double [batch], NULL = the scalar; hist = the table's row count
+extern "C" int pnp_csmri_saga_step_hist_pp(pnp_csmri_plan* p, const void* z, const uint32_t* bitsT, const void* YT, double alpha,
+                                           const double* alpha_pp, const void* alpha_vec, void* table, const int32_t* row,
+                                           const int32_t* prev_row, void* sum, double lr, const double* lr_pp, double inv_hist,
+                                           const double* inv_hist_pp, int hist, void* out, int denoise, double sigma_modifier,
+                                           const double* sigma_modifier_pp, double fallback_sigma, const void* xrec, double* sse_out,
+                                           void* sigma_out, void* stream) {
+    return saga_step_impl(p, z, bitsT, YT, alpha, alpha_pp, alpha_vec, table, row, prev_row, sum, lr, lr_pp, inv_hist, hist, out, denoise,
+                          sigma_modifier, sigma_modifier_pp, fallback_sigma, xrec, sse_out, sigma_out, stream, true, inv_hist_pp);
 }
 
 // ---- the same with the outer-loop refresh folded in (first inner iteration of an outer iteration)
@@ -700,11 +720,11 @@ extern "C" int pnp_csmri_grad_span(pnp_csmri_plan* p, void* z, const uint32_t* b
 }
 
 // ---- n_steps SAGA inner iterations in one launch; table, sum and z in place
-extern "C" int pnp_csmri_saga_span(pnp_csmri_plan* p, void* z, const uint32_t* bitsT, const void* YT, double alpha, const double* alpha_pp,
-                                   const void* alpha_vec, void* table, const int32_t* rows, const int32_t* prev_row0, void* sum, double lr,
-                                   const double* lr_pp, double inv_hist, int hist, int denoise, double sigma_modifier,
-                                   const double* sigma_modifier_pp, double fallback_sigma, const void* xrec, int n_steps, double* sse_log,
-                                   int log_row0, int n_log, void* sigma_out, void* stream) {
+static int saga_span_impl(pnp_csmri_plan* p, void* z, const uint32_t* bitsT, const void* YT, double alpha, const double* alpha_pp,
+                          const void* alpha_vec, void* table, const int32_t* rows, const int32_t* prev_row0, void* sum, double lr,
+                          const double* lr_pp, double inv_hist, int hist, int denoise, double sigma_modifier,
+                          const double* sigma_modifier_pp, double fallback_sigma, const void* xrec, int n_steps, double* sse_log,
+                          int log_row0, int n_log, void* sigma_out, void* stream, bool hist_form, const double* inv_hist_pp) {
     PNP_CHECK_ARG(p && z && bitsT && YT && table && rows && prev_row0 && sum && xrec && sse_log && sigma_out, "null argument");
     PNP_CHECK_ARG(hist >= 1, "need hist >= 1");
     PNP_CHECK_ARG(n_steps >= 1 && n_log >= 1 && log_row0 >= 0 && log_row0 <= INT32_MAX - n_steps, "bad n_steps / log");
@@ -720,7 +740,33 @@ extern "C" int pnp_csmri_saga_span(pnp_csmri_plan* p, void* z, const uint32_t* b
         PNP_CHECK_ARG(!overlap(table, tb, z, img) && !overlap(table, tb, xrec, img) && !overlap(sum, img, z, img) &&
                       !overlap(sum, img, xrec, img) && !overlap(table, tb, sum, img), "table and sum must not alias z, xrec or each other");
     }
+    if (hist_form)                                              // the kernel that takes the divisor per problem (NULL: the scalar)
+        return csmri_saga_hist_launch(p->batch, p->twtab, z, bitsT, YT, alpha, alpha_vec, table, rows, prev_row0, sum, lr, inv_hist, z, 0,
+                                      sigma_modifier, fallback_sigma, xrec, sse_log, sigma_out, stream, alpha_pp, lr_pp, sigma_modifier_pp,
+                                      inv_hist_pp, n_steps, log_row0, n_log);
     return csmri_step_span_launch(p->batch, p->twtab, z, bitsT, nullptr, YT, alpha, alpha_vec, 0.0, table, rows, prev_row0, sum, lr, inv_hist,
                                   n_steps, sigma_modifier, fallback_sigma, xrec, sse_log, log_row0, n_log, sigma_out, stream, alpha_pp, lr_pp,
                                   sigma_modifier_pp);
+}
+
+extern "C" int pnp_csmri_saga_span(pnp_csmri_plan* p, void* z, const uint32_t* bitsT, const void* YT, double alpha, const double* alpha_pp,
+                                   const void* alpha_vec, void* table, const int32_t* rows, const int32_t* prev_row0, void* sum, double lr,
+                                   const double* lr_pp, double inv_hist, int hist, int denoise, double sigma_modifier,
+                                   const double* sigma_modifier_pp, double fallback_sigma, const void* xrec, int n_steps, double* sse_log,
+                                   int log_row0, int n_log, void* sigma_out, void* stream) {
+    return saga_span_impl(p, z, bitsT, YT, alpha, alpha_pp, alpha_vec, table, rows, prev_row0, sum, lr, lr_pp, inv_hist, hist, denoise,
+                          sigma_modifier, sigma_modifier_pp, fallback_sigma, xrec, n_steps, sse_log, log_row0, n_log, sigma_out, stream,
+                          false, nullptr);
+}
+
+// ---- pnp_csmri_saga_span with the divisor per problem: inv_hist_pp double [batch], NULL = the scalar; hist = the table's row count
+extern "C" int pnp_csmri_saga_span_hist(pnp_csmri_plan* p, void* z, const uint32_t* bitsT, const void* YT, double alpha,
+                                        const double* alpha_pp, const void* alpha_vec, void* table, const int32_t* rows,
+                                        const int32_t* prev_row0, void* sum, double lr, const double* lr_pp, double inv_hist,
+                                        const double* inv_hist_pp, int hist, int denoise, double sigma_modifier,
+                                        const double* sigma_modifier_pp, double fallback_sigma, const void* xrec, int n_steps,
+                                        double* sse_log, int log_row0, int n_log, void* sigma_out, void* stream) {
+    return saga_span_impl(p, z, bitsT, YT, alpha, alpha_pp, alpha_vec, table, rows, prev_row0, sum, lr, lr_pp, inv_hist, hist, denoise,
+                          sigma_modifier, sigma_modifier_pp, fallback_sigma, xrec, n_steps, sse_log, log_row0, n_log, sigma_out, stream,
+                          true, inv_hist_pp);
 }

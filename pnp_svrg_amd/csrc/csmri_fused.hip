@@ -1360,6 +1360,80 @@ __global__ __launch_bounds__(FT) void k_saga_span(float* z, const uint32_t* __re
     }
 }
 
+// k_saga_iter and k_saga_span with the divisor of the running sum per problem (pnp_csmri_saga_step_hist_pp, pnp_csmri_saga_span_hist;
+// DESIGN 9.8): inv_hist_pp, DOUBLE [batch] or NULL, is read beside lr_pp -- once per workgroup, in the span before the step loop -- and
+// cast as the scalar is cast; the same SagaArgs go to the same saga_epilogue.  Kernels of their own with bodies of their own (TAG = 2,
+// 3: see svrg_iter_body), so that k_saga_iter and k_saga_span keep their code; the span kernel is a template (launched as <3>) only
+// to be emitted behind every existing kernel: a plain kernel here would renumber their long-branch labels in the listing.  table is [max hist][batch][H][W]; problem b names rows
+// below its own history length only (the caller checks them).
+template <int MODE>
+__global__ __launch_bounds__(FT) void k_saga_iter_hist(const float* z, const uint32_t* __restrict__ bitsT, const cx<float>* __restrict__ YT,
+                                                       const cx<float>* __restrict__ twtab, float scale, const float* __restrict__ alpha_vec,
+                                                       float* table, const int32_t* __restrict__ row, const int32_t* __restrict__ prev_row,
+                                                       float* sum, float lr, float inv_hist, float* out, float sigma_modifier,
+                                                       float fallback_sigma, const float* __restrict__ xrec, double* __restrict__ sse_out,
+                                                       float* __restrict__ sigma_out, int stagger_n, int stagger_groups, int stagger_units,
+                                                       const double* __restrict__ alpha_pp, const double* __restrict__ lr_pp,
+                                                       const double* __restrict__ sm_pp, const double* __restrict__ inv_hist_pp) {
+    startup_stagger(stagger_n, stagger_groups, stagger_units);
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    __shared__ FusedShared sh;
+    const int prob = blockIdx.x, batch = gridDim.x;
+    const size_t img = (size_t)prob * FN * FN;
+    if (alpha_pp != nullptr) scale = (float)(alpha_pp[prob] * (1.0 / ((double)FN * (double)FN)));
+    if (alpha_vec != nullptr) scale *= alpha_vec[prob];
+    if (lr_pp != nullptr) lr = (float)lr_pp[prob];
+    if (inv_hist_pp != nullptr) inv_hist = (float)inv_hist_pp[prob];
+    if (sm_pp != nullptr) sigma_modifier = (float)sm_pp[prob];
+    SagaArgs sa = {table + ((size_t)row[prob] * batch + prob) * FN * FN, table + ((size_t)prev_row[prob] * batch + prob) * FN * FN,
+                   sum + img, lr, inv_hist};
+    asm volatile("" : "+s"(sa.slot), "+s"(sa.prev), "+s"(sa.sum));
+    svrg_iter_body<MODE, false, 0, 3, false, 2>(lds_raw, sh, z + img, nullptr, bitsT + (size_t)prob * FN * 8, nullptr, twtab, scale, 0.f,
+                                                nullptr, 0.f, nullptr, out + img, sigma_modifier, fallback_sigma,
+                                                xrec != nullptr ? xrec + img : nullptr, sse_out != nullptr ? sse_out + prob : nullptr,
+                                                sigma_out != nullptr ? sigma_out + prob : nullptr, nullptr, nullptr, nullptr, nullptr,
+                                                YT + img, &sa);
+}
+
+template <int TAG>
+__global__ __launch_bounds__(FT) void k_saga_span_hist(float* z, const uint32_t* __restrict__ bits, const cx<float>* __restrict__ YT,
+                                                       const cx<float>* __restrict__ twtab, float scale, const float* __restrict__ alpha_vec,
+                                                       float* table, const int32_t* __restrict__ rows, const int32_t* __restrict__ prev_row0,
+                                                       float* sum, float lr, float inv_hist, int n_steps, float sigma_modifier,
+                                                       float fallback_sigma, const float* __restrict__ xrec, double* __restrict__ sse_log,
+                                                       int log_row0, int n_log, float* __restrict__ sigma_out,
+                                                       const double* __restrict__ alpha_pp, const double* __restrict__ lr_pp,
+                                                       const double* __restrict__ sm_pp, const double* __restrict__ inv_hist_pp) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    __shared__ FusedShared sh;
+    const int prob = blockIdx.x, batch = gridDim.x;
+    const size_t img = (size_t)prob * FN * FN;
+    if (alpha_pp != nullptr) scale = (float)(alpha_pp[prob] * (1.0 / ((double)FN * (double)FN)));
+    if (alpha_vec != nullptr) scale *= alpha_vec[prob];
+    if (lr_pp != nullptr) lr = (float)lr_pp[prob];
+    if (inv_hist_pp != nullptr) inv_hist = (float)inv_hist_pp[prob];
+    if (sm_pp != nullptr) sigma_modifier = (float)sm_pp[prob];
+    float* zi = z + img;
+    int prev = prev_row0[prob];
+#pragma unroll 1
+    for (int i = 0; i < n_steps; ++i) {
+        if (i > 0) {
+            // this step reads what the last one wrote (same lanes, same addresses): stores done, no stale line in the L1
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            __syncthreads();
+        }
+        const int row = rows[(size_t)i * batch + prob];
+        SagaArgs sa = {table + ((size_t)row * batch + prob) * FN * FN, table + ((size_t)prev * batch + prob) * FN * FN, sum + img, lr, inv_hist};
+        asm volatile("" : "+s"(sa.slot), "+s"(sa.prev), "+s"(sa.sum));
+        svrg_iter_body<FUSED_FULL, false, 0, 3, false, TAG>(lds_raw, sh, zi, nullptr, bits + ((size_t)i * batch + prob) * FN * 8, nullptr, twtab,
+                                                          scale, 0.f, nullptr, 0.f, nullptr, zi, sigma_modifier, fallback_sigma, xrec + img,
+                                                          sse_log + (size_t)((log_row0 + i) % n_log) * batch + prob, sigma_out + prob,
+                                                          nullptr, nullptr, nullptr, nullptr, YT + img, &sa);
+        prev = row;
+    }
+}
+
 // stagger (see startup_stagger): only launches of more than one workgroup per CU pay for it and profit from it
 static int stagger_config(int* num_cu_out, int* groups, int* units) {
     static int num_cu = 0, st_groups = 2, st_units = 40;    // same-box sweep (tools/dev/stagger_sweep.py): 0.588 ms per config-2 step without, 0.575 with (2, 40), slower from (8, 20) on
@@ -1612,6 +1686,48 @@ int csmri_minibatch_launch(int batch, const void* twtab, const void* a, const ui
         if (mode == FUSED_FULL) k_grad_step<0><<<batch, FT, F_LDS_BYTES, s>>>(PNP_GS_ARGS);
         else k_grad_step<1><<<batch, FT, F_LDS_BYTES, s>>>(PNP_GS_ARGS);
 #undef PNP_GS_ARGS
+    }
+    PNP_CHECK_LAUNCH();
+    return PNP_OK;
+}
+
+// the SAGA forms with a per-problem divisor (pnp_csmri_saga_step_hist_pp, pnp_csmri_saga_span_hist): k_saga_iter_hist with the stagger,
+// scale and casts of csmri_minibatch_launch; n_steps > 0 selects k_saga_span_hist (row = rows [n_steps][batch], prev_row = prev_row0,
+// sse_out = the log ring, a = z in place and `out`, `mode` not used) as csmri_step_span_launch launches k_saga_span
+int csmri_saga_hist_launch(int batch, const void* twtab, const void* a, const uint32_t* bitsT, const void* YT, double alpha,
+                           const void* alpha_vec, void* table, const int32_t* row, const int32_t* prev_row, void* sum, double lr,
+                           double inv_hist, void* out, int mode, double sigma_modifier, double fallback_sigma, const void* xrec,
+                           double* sse_out, void* sigma_out, void* stream, const double* alpha_pp, const double* lr_pp, const double* sm_pp,
+                           const double* inv_hist_pp, int n_steps, int log_row0, int n_log) {
+    const float scale = (float)(alpha / ((double)FN * (double)FN));
+    hipStream_t s = (hipStream_t)stream;
+    int num_cu = 0, st_groups = 0, st_units = 0;
+    { const int rc = stagger_config(&num_cu, &st_groups, &st_units); if (rc != PNP_OK) return rc; }
+    const int stagger_units = batch > num_cu ? st_units : 0;
+    {   // > 64 KiB of dynamic LDS needs the opt-in, once per device (as fused_lds_optin)
+        static unsigned long long attr_done = 0;
+        int dev = 0;
+        PNP_CHECK_HIP(hipGetDevice(&dev));
+        if (!((attr_done >> (dev & 63)) & 1ull)) {
+            PNP_CHECK_HIP(hipFuncSetAttribute((const void*)k_saga_iter_hist<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F_LDS_BYTES));
+            PNP_CHECK_HIP(hipFuncSetAttribute((const void*)k_saga_iter_hist<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F_LDS_BYTES));
+            PNP_CHECK_HIP(hipFuncSetAttribute((const void*)k_saga_span_hist<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F_LDS_BYTES));
+            attr_done |= 1ull << (dev & 63);
+        }
+    }
+    if (n_steps > 0) {
+        k_saga_span_hist<3><<<batch, FT, F_LDS_BYTES, s>>>((float*)const_cast<void*>(a), bitsT, (const cx<float>*)YT, (const cx<float>*)twtab, scale,
+                                                       (const float*)alpha_vec, (float*)table, row, prev_row, (float*)sum, (float)lr,
+                                                       (float)inv_hist, n_steps, (float)sigma_modifier, (float)fallback_sigma,
+                                                       (const float*)xrec, sse_out, log_row0, n_log, (float*)sigma_out, alpha_pp, lr_pp, sm_pp,
+                                                       inv_hist_pp);
+    } else {
+#define PNP_SAGA_ARGS (const float*)a, bitsT, (const cx<float>*)YT, (const cx<float>*)twtab, scale, (const float*)alpha_vec, (float*)table, \
+                      row, prev_row, (float*)sum, (float)lr, (float)inv_hist, (float*)out, (float)sigma_modifier, (float)fallback_sigma,     \
+                      (const float*)xrec, sse_out, (float*)sigma_out, num_cu, st_groups, stagger_units, alpha_pp, lr_pp, sm_pp, inv_hist_pp
+        if (mode == FUSED_FULL) k_saga_iter_hist<0><<<batch, FT, F_LDS_BYTES, s>>>(PNP_SAGA_ARGS);
+        else k_saga_iter_hist<1><<<batch, FT, F_LDS_BYTES, s>>>(PNP_SAGA_ARGS);
+#undef PNP_SAGA_ARGS
     }
     PNP_CHECK_LAUNCH();
     return PNP_OK;

@@ -95,6 +95,41 @@ __global__ __launch_bounds__(256) void k_saga_update_pp(T* z, const T* __restric
     }
 }
 
+// k_saga_update_pp with the divisor per problem as well (pnp_saga_table_update_hist_pp): problem b divides its running sum by its OWN
+// history length, inv_hist_pp[b] = 1 / hist[b] in double, cast as the scalar is cast and loaded once per workgroup; a problem only names
+// rows below its own hist[b] (row[b], prev_row[b]: the caller checks them), so the rows of the dense table beyond them are never
+// touched.  Everything else is k_saga_update_pp's, statement for statement, row[b] == prev_row[b] included.
+template <typename T>
+__global__ __launch_bounds__(256) void k_saga_update_hist_pp(T* z, const T* __restrict__ g, T* table, const int32_t* __restrict__ row,
+                                                             const int32_t* __restrict__ prev_row, T* sum, T lr,
+                                                             const double* __restrict__ lr_pp, T inv_hist,
+                                                             const double* __restrict__ inv_hist_pp, int batch, int N) {
+    using V = typename SagaVec<T>::type;
+    constexpr int NV = (int)(sizeof(V) / sizeof(T));
+    const int b = blockIdx.y;
+    if (lr_pp != nullptr) lr = (T)lr_pp[b];
+    if (inv_hist_pp != nullptr) inv_hist = (T)inv_hist_pp[b];
+    const size_t pb = (size_t)b * N;
+    T* slot = table + ((size_t)row[b] * batch + b) * N;
+    const T* prev = table + ((size_t)prev_row[b] * batch + b) * N;
+    for (int i = (blockIdx.x * blockDim.x + threadIdx.x) * NV; i < N; i += gridDim.x * blockDim.x * NV) {
+        const V gv = *(const V*)(g + pb + i), ov = *(const V*)(slot + i), pv = *(const V*)(prev + i);
+        V sv = *(const V*)(sum + pb + i), zv = *(const V*)(z + pb + i);
+        const T* ga = (const T*)&gv; const T* oa = (const T*)&ov; const T* pa = (const T*)&pv;
+        T* sa = (T*)&sv; T* za = (T*)&zv;
+#pragma unroll
+        for (int k = 0; k < NV; ++k) {
+            const T gi = ga[k], old = oa[k], pvk = pa[k];
+            const T s = sa[k] + gi - old;
+            za[k] -= lr * ((gi - pvk) + s * inv_hist);
+            sa[k] = s;
+        }
+        *(V*)(z + pb + i) = zv;
+        *(V*)(slot + i) = gv;
+        *(V*)(sum + pb + i) = sv;
+    }
+}
+
 }  // namespace pnp
 
 using namespace pnp;
@@ -173,6 +208,26 @@ extern "C" int pnp_saga_table_update_pp(void* z, const void* g, void* table, con
     else
         k_saga_update_pp<double><<<grid, 256, 0, (hipStream_t)stream>>>((double*)z, (const double*)g, (double*)table, row, prev_row,
                                                                           (double*)sum, lr, lr_pp, inv_hist, batch, N);
+    PNP_CHECK_LAUNCH();
+    return PNP_OK;
+}
+
+extern "C" int pnp_saga_table_update_hist_pp(void* z, const void* g, void* table, const int32_t* row, const int32_t* prev_row, void* sum,
+                                             double lr, const double* lr_pp, double inv_hist, const double* inv_hist_pp, int hist,
+                                             int batch, int N, int dtype, void* stream) {
+    PNP_CHECK_ARG(z && g && table && row && prev_row && sum, "null argument");
+    PNP_CHECK_ARG(hist >= 1 && batch >= 1 && batch <= 65535 && N >= 4 && N % 4 == 0, "need hist >= 1, 1 <= batch <= 65535 and N a multiple of 4");
+    PNP_CHECK_ARG(dtype == PNP_F32 || dtype == PNP_F64, "bad dtype");
+    PNP_CHECK_ARG((((uintptr_t)z | (uintptr_t)g | (uintptr_t)table | (uintptr_t)sum) & 15) == 0, "z, g, table and sum must be 16-byte aligned");
+    const int nv = dtype == PNP_F32 ? 4 : 2, per = (N / nv + 255) / 256;
+    const dim3 grid(per < 256 ? per : 256, batch);
+    if (dtype == PNP_F32)
+        k_saga_update_hist_pp<float><<<grid, 256, 0, (hipStream_t)stream>>>((float*)z, (const float*)g, (float*)table, row, prev_row,
+                                                                              (float*)sum, (float)lr, lr_pp, (float)inv_hist, inv_hist_pp,
+                                                                              batch, N);
+    else
+        k_saga_update_hist_pp<double><<<grid, 256, 0, (hipStream_t)stream>>>((double*)z, (const double*)g, (double*)table, row, prev_row,
+                                                                               (double*)sum, lr, lr_pp, inv_hist, inv_hist_pp, batch, N);
     PNP_CHECK_LAUNCH();
     return PNP_OK;
 }

@@ -842,24 +842,52 @@ class SagaEngine(_FusedStep, _StochEngine):
     The replaced row r of every step is drawn on the host (one value per step for the whole batch; pass `r=` to
     `step` to impose the reference's `np.random.choice(hist_size, 1)` stream).
     fused=True (opt-in): a step is ONE pnp_csmri_saga_step -- minibatch gradient, table update, step and prox; the rows
-    always go in as the int32 [B] device vectors of the batched update.  The table initialisation is the streaming one."""
+    always go in as the int32 [B] device vectors of the batched update.  The table initialisation is the streaming one.
+    hist_size: an int, or a [B] integer array on a batch that takes per-problem values: problem b then walks, bit for bit,
+    the trajectory a scalar engine with hist_size[b] walks on the same seed, draw_id, minibatches and rows.  The table is dense,
+    [max(hist_size)][B][H][W], and problem b only ever touches its rows [0, hist_size[b]); its running sum starts at hist_size[b] * g
+    and is divided by hist_size[b] (`pnp_saga_table_update_hist_pp`, `pnp_csmri_saga_step_hist_pp`, `pnp_csmri_saga_span_hist`: every
+    step is one batched launch).  With r=None the rows come from one generator per DISTINCT value h of the vector, each the scalar
+    engine's `default_rng(seed + 977)` drawing `integers(h)` once per step: problem b takes the draw of the generator of its own
+    value, which is what a scalar engine with hist_size = h draws."""
 
     def __init__(self, batch, prox, eta, mini_batch_size, hist_size=50, lr_decay=1.0, n_log=4096, seed=0, idx0=None, draw_id=None,
                  log_objective=False, *, fused=False):
         self.fused = bool(fused)
         if self.fused:
             _check_fused('SagaEngine', batch, prox, log_objective)
+        hv = None
+        if np.ndim(hist_size) != 0:                             # per-problem hist_size: checked on the host (the kernels cannot)
+            hv = np.asarray(hist_size)
+            if not batch.per_problem:
+                raise ValueError(f'per-problem hist_size needs a batch that takes per-problem values (got {batch.kind!r})')
+            if hv.shape != (batch.B,) or not np.issubdtype(hv.dtype, np.integer):
+                raise ValueError(f'per-problem hist_size: {batch.B} integers, got shape {hv.shape} of {hv.dtype}')
+            bad = np.flatnonzero((hv < 1) | (hv > np.iinfo(np.int32).max))
+            if bad.size:
+                raise ValueError(f'per-problem hist_size: entries must be >= 1 (problem {int(bad[0])}: hist_size {int(hv[bad[0]])})')
+            hv = np.ascontiguousarray(hv, np.int64)
         self._row_cache = {}                                    # fused: one row for the whole batch -> its device vector, made once
         super().__init__(batch, prox, eta, mini_batch_size, lr_decay, n_log, seed, draw_id=draw_id, log_objective=log_objective)
-        self.hist = hist_size
+        self.hist = hist_size if hv is None else int(hv.max())  # the table's row count
+        self.hist_pp = hv                                       # per-problem history lengths (None: one for the batch)
         self.g = torch.empty_like(self.z)
         self._rng = np.random.default_rng(seed + 977)
+        self._inv_hist_pp = None
+        if hv is not None:                                      # one row stream per distinct value, each the scalar engine's
+            self._rngs = {int(h): np.random.default_rng(seed + 977) for h in np.unique(hv)}
+            # the divisors as the scalar path forms them (1.0 / hist_size in Python floats), uploaded once
+            self._inv_hist_pp = torch.from_numpy(np.array([1.0 / int(h) for h in hv], np.float64)).to(self.z.device)
         self._rows = None                                       # (host rows, their int32 device vector) of the last batched update
         # pnp_saga.py:25-31: one minibatch gradient at Xinit fills the whole table
         j = self._minibatch(idx0, 0xFFFFFFFF)
         batch.grad_stoch(self.z, self.mbs, j, out=self.g, alpha=self._c('1/mb', 0, 1.0 / self.mb))
-        self.table = self.g.unsqueeze(0).repeat(hist_size, 1, 1, 1).contiguous()
-        self.tsum = ops.axpbypcz(float(hist_size), self.g, out=torch.empty_like(self.g))
+        if hv is None:
+            self.table = self.g.unsqueeze(0).repeat(hist_size, 1, 1, 1).contiguous()
+            self.tsum = ops.axpbypcz(float(hist_size), self.g, out=torch.empty_like(self.g))
+        else:                                                   # dense over max(hist_size); tsum[b] = float(hist_size[b]) * g[b]
+            self.table = self.g.unsqueeze(0).repeat(self.hist, 1, 1, 1).contiguous()
+            self.tsum = ops.axpbypcz(torch.from_numpy(hv.astype(np.float64)).to(self.z.device), self.g, out=torch.empty_like(self.g))
         self.r_prev = 0
 
     def reset(self):
@@ -877,10 +905,27 @@ class SagaEngine(_FusedStep, _StochEngine):
         rv = np.ascontiguousarray(np.broadcast_to(np.asarray(r, np.int32), (self.b.B,)))
         return torch.from_numpy(rv).to(self.z.device)
 
+    def _draw_rows_pp(self, n):
+        """Per-problem hist_size: the rows of the next n steps, int64 [n][B] -- per step one draw from the generator of every distinct
+        value, problem b taking that of its own."""
+        draws = {h: [int(g.integers(h)) for _ in range(n)] for h, g in self._rngs.items()}
+        return np.array([draws[int(h)] for h in self.hist_pp], np.int64).T.reshape(n, self.b.B)
+
+    def _check_rows_pp(self, r):
+        """Per-problem hist_size: rows (a scalar, [B], or [n][B]) as int64 against every problem's own bound [0, hist_size[b])."""
+        r = np.broadcast_to(np.asarray(r, np.int64), np.shape(r)[:-1] + (self.b.B,) if np.ndim(r) else (self.b.B,)).copy()
+        bad = np.argwhere((r < 0) | (r >= self.hist_pp))
+        if bad.size:
+            b = int(bad[0][-1])
+            raise ValueError(f'SAGA row outside the table of problem {b}: rows in [0, {int(self.hist_pp[b])}), got {int(r[tuple(bad[0])])}')
+        return r
+
     def step(self, idx_s=None, r=None):
         """r: the table row this step replaces -- one value for the whole batch, or one per problem (legacy-seeded sweeps:
         every item follows its own np.random stream, and with masks of different sizes the streams drift apart)."""
         j = self._minibatch(idx_s, self.s)
+        if self.hist_pp is not None:
+            return self._step_hist_pp(j, self._draw_rows_pp(1)[0] if r is None else r)
         if r is None:
             r = int(self._rng.integers(self.hist))
         if self.fused:
@@ -902,6 +947,27 @@ class SagaEngine(_FusedStep, _StochEngine):
         self.z = self._prox(self.z)
         self.s += 1
 
+    def _step_hist_pp(self, j, r):
+        """`step()` with a per-problem hist_size: the rows checked against every problem's own bound, then ONE batched launch with the
+        divisor vector -- pnp_saga_table_update_hist_pp behind the minibatch gradient, or the one-kernel step."""
+        b = self.b
+        r = self._check_rows_pp(r)
+        prev = self._row_vec(self.r_prev)
+        self._rows = (r, self._row_vec(r))
+        lr = self.eta * self.lr_decay ** self.s
+        if self.fused:
+            self._one_kernel(b.plan.saga_step, self.z, self._slot_bits(j), b.YT, self.table, self._rows[1], prev, self.tsum,
+                             self._c('lr', self.s, lr), 1.0 / self.hist, alpha=self._c('1/mb', 0, 1.0 / self.mb),
+                             inv_hist_pp=self._inv_hist_pp)
+            self.r_prev = r
+            self.s += 1
+            return
+        b.grad_stoch(self.z, self.mbs, j, out=self.g, alpha=self._c('1/mb', 0, 1.0 / self.mb))
+        ops.saga_table_update_pp(self.z, self.g, self.table, self._rows[1], prev, self.tsum, self._c('lr', self.s, lr), 1.0 / self.hist,
+                                 inv_hist_pp=self._inv_hist_pp)
+        self.r_prev = r
+        self.z = self._prox(self.z)
+        self.s += 1
 
     def _step_fused(self, j, r):
         """The step in ONE kernel: the rows and coefficients are those of the streaming step (a row for the whole batch as a
@@ -932,7 +998,7 @@ class SagaEngine(_FusedStep, _StochEngine):
         which the workgroup that owns a problem runs its steps back to back -- the same bits as stepping, with r_prev left as
         stepping leaves it; otherwise n eager steps."""
         if r is None:
-            r = [int(self._rng.integers(self.hist)) for _ in range(n)]
+            r = self._draw_rows_pp(n) if self.hist_pp is not None else [int(self._rng.integers(self.hist)) for _ in range(n)]
         r = np.asarray(r)
         if r.shape not in ((n,), (n, self.b.B)):
             raise ValueError(f'run_span: r holds one row per step ([{n}]) or per step and problem ([{n}][{self.b.B}]), got shape {r.shape}')
@@ -943,7 +1009,11 @@ class SagaEngine(_FusedStep, _StochEngine):
         if n < 1:
             return
         b, px = self.b, self.prox
-        if r.min() < 0 or r.max() >= self.hist:
+        kw = {}
+        if self.hist_pp is not None:                            # every problem's own bound; the rows are then always [n][B]
+            r = self._check_rows_pp(r.reshape(n, -1))
+            kw = dict(inv_hist_pp=self._inv_hist_pp)
+        elif r.min() < 0 or r.max() >= self.hist:
             raise ValueError(f'SAGA row outside the table: rows in [0, {self.hist}), got {np.ravel(r).tolist()}')
         rows = np.ascontiguousarray(np.broadcast_to(r.reshape(n, -1), (n, b.B)), np.int32)
         rows_dev = torch.from_numpy(rows).to(self.z.device)
@@ -955,7 +1025,7 @@ class SagaEngine(_FusedStep, _StochEngine):
             lr = self.eta * self.lr_decay ** self.s             # (span_kernel_ok: lr_decay == 1)
             b.plan.saga_span(self.z, self.mbs.selbits, b.YT, self.table, rows_dev[i0:i0 + m], prev, self.tsum, self._c('lr', self.s, lr),
                              1.0 / self.hist, m, b.xrec, self.sse_log, self.n_prox % self.n_log, px.sig,
-                             alpha=self._c('1/mb', 0, 1.0 / self.mb), sigma_modifier=px.sigma_modifier)
+                             alpha=self._c('1/mb', 0, 1.0 / self.mb), sigma_modifier=px.sigma_modifier, **kw)
             self._span_done(m)
             i0 += m
             prev = rows_dev[i0 - 1]

@@ -297,10 +297,12 @@ class CsmriPlan:
         return out, sse, sigma_out
 
     def saga_step(self, z, bits, YT, table, row, prev_row, tsum, lr, inv_hist, alpha=1.0, out=None, *, alpha_vec=None, denoise=True,
-                  sigma_modifier=1.0, fallback_sigma=0.0, xrec=None, sse=None, sigma_out=None):
+                  sigma_modifier=1.0, fallback_sigma=0.0, xrec=None, sse=None, sigma_out=None, inv_hist_pp=None):
         """pnp_csmri_saga_step: one SAGA inner iteration in ONE kernel (f32, 256 x 256): g = alpha * Re ifft2(bits o fft2(z) - bits o Y);
         s = tsum + g - table[row[b]][b]; out = prox_TV(z - lr * ((g - table[prev_row[b]][b]) + s * inv_hist)); table[row[b]][b] = g;
-        tsum = s.  table: [hist, B, H, W]; row, prev_row: int32 [B] device tensors; out may be z.  Returns (out, sse, sigma_out)."""
+        tsum = s.  table: [hist, B, H, W]; row, prev_row: int32 [B] device tensors; out may be z.  Returns (out, sse, sigma_out).
+        inv_hist_pp: a float64 [B] device tensor of per-problem divisors 1 / hist[b] -> pnp_csmri_saga_step_hist_pp (table: [max hist, B,
+        H, W]); None: the calls above, unchanged."""
         self._one_kernel_plan('saga_step')
         assert bits.dtype == torch.int32 and tuple(bits.shape) == (self.B, self.W, self.H // 32)
         assert YT.dtype == _CDT[self.dtype] and tuple(YT.shape) == (self.B, self.W, self.H)
@@ -311,6 +313,13 @@ class CsmriPlan:
             assert rv.dtype == torch.int32 and tuple(rv.shape) == (self.B,)
         out = out if out is not None else torch.empty_like(z)
         sigma_out = sigma_out if sigma_out is not None else torch.empty(self.B, dtype=z.dtype, device=z.device)
+        if inv_hist_pp is not None:                             # (scalar, array or NULL) pairs: the entry point has the _pp form only
+            a, l, sm, ih = _pp(alpha, self.B), _pp(lr, self.B), _pp(sigma_modifier, self.B), _pp(inv_hist_pp, self.B)
+            assert ih[1] is not None, 'inv_hist_pp: a [B] float64 device tensor'
+            N.call('pnp_csmri_saga_step_hist_pp', self._h, _p(z), _p(bits), _p(YT), a[0], _p(a[1]), _p(alpha_vec), _p(table), _p(row),
+                   _p(prev_row), _p(tsum), l[0], _p(l[1]), float(inv_hist), _p(ih[1]), int(table.shape[0]), _p(out), 1 if denoise else 0,
+                   sm[0], _p(sm[1]), float(fallback_sigma), _p(xrec), _p(sse), _p(sigma_out), _stream())
+            return out, sse, sigma_out
         _route('pnp_csmri_saga_step', [self._h, _p(z), _p(bits), _p(YT), _pp(alpha, self.B), _p(alpha_vec), _p(table), _p(row),
                                        _p(prev_row), _p(tsum), _pp(lr, self.B), float(inv_hist), int(table.shape[0]), _p(out),
                                        1 if denoise else 0, _pp(sigma_modifier, self.B), float(fallback_sigma), _p(xrec), _p(sse),
@@ -407,11 +416,12 @@ class CsmriPlan:
                _p(sigma_out), _stream())
 
     def saga_span(self, z, bits, YT, table, rows, prev_row0, tsum, lr, inv_hist, n_steps, xrec, sse_log, log_row0, sigma_out, *,
-                  alpha=1.0, alpha_vec=None, sigma_modifier=1.0, fallback_sigma=0.0):
+                  alpha=1.0, alpha_vec=None, sigma_modifier=1.0, fallback_sigma=0.0, inv_hist_pp=None):
         """pnp_csmri_saga_span: n_steps SAGA inner iterations with the TV prox in ONE launch; table, tsum and z in place.  bits: drawn
         selbits [>= n_steps, B, W, H/32], slot i = step i; rows: int32 [n_steps, B] device tensor (step i replaces rows[i][b]);
         prev_row0: int32 [B] (the row the step before the span replaced).  Row values must lie in [0, hist): the caller checks its
-        host copy.  alpha, lr, sigma_modifier: scalars or [B] float64 device tensors."""
+        host copy.  alpha, lr, sigma_modifier: scalars or [B] float64 device tensors.  inv_hist_pp: a float64 [B] device tensor of
+        per-problem divisors 1 / hist[b] -> pnp_csmri_saga_span_hist (table: [max hist, B, H, W]); None: the call above, unchanged."""
         self._span_log('saga_span', sse_log, sigma_out, z, tsum, xrec)
         assert bits.dtype == torch.int32 and bits.dim() == 4 and bits.shape[0] >= n_steps
         assert tuple(bits.shape[1:]) == (self.B, self.W, self.H // 32)
@@ -421,6 +431,14 @@ class CsmriPlan:
         assert prev_row0.dtype == torch.int32 and tuple(prev_row0.shape) == (self.B,)
         assert alpha_vec is None or (alpha_vec.dtype == self.dtype and alpha_vec.numel() == self.B)
         a, l, sm = _pp(alpha, self.B), _pp(lr, self.B), _pp(sigma_modifier, self.B)
+        if inv_hist_pp is not None:
+            ih = _pp(inv_hist_pp, self.B)
+            assert ih[1] is not None, 'inv_hist_pp: a [B] float64 device tensor'
+            N.call('pnp_csmri_saga_span_hist', self._h, _p(z), _p(bits), _p(YT), a[0], _p(a[1]), _p(alpha_vec), _p(table), _p(rows),
+                   _p(prev_row0), _p(tsum), l[0], _p(l[1]), float(inv_hist), _p(ih[1]), int(table.shape[0]), 1, sm[0], _p(sm[1]),
+                   float(fallback_sigma), _p(xrec), int(n_steps), _p(sse_log), int(log_row0), int(sse_log.shape[0]), _p(sigma_out),
+                   _stream())
+            return
         N.call('pnp_csmri_saga_span', self._h, _p(z), _p(bits), _p(YT), a[0], _p(a[1]), _p(alpha_vec), _p(table), _p(rows), _p(prev_row0),
                _p(tsum), l[0], _p(l[1]), float(inv_hist), int(table.shape[0]), 1, sm[0], _p(sm[1]), float(fallback_sigma), _p(xrec),
                int(n_steps), _p(sse_log), int(log_row0), int(sse_log.shape[0]), _p(sigma_out), _stream())
@@ -898,10 +916,11 @@ def saga_table_update(z, g, slot, prev, tsum, lr, inv_hist):
            _DT[z.dtype], _stream())
 
 
-def saga_table_update_pp(z, g, table, row, prev_row, tsum, lr, inv_hist):
+def saga_table_update_pp(z, g, table, row, prev_row, tsum, lr, inv_hist, inv_hist_pp=None):
     """pnp_saga_table_update_pp: one SAGA step of a whole batch in ONE launch.  z, g, tsum [B, ...]; table [hist, B, ...]; row, prev_row:
     int32 [B] device tensors (problem b replaces table[row[b], b]; its previous step wrote table[prev_row[b], b]); lr: a scalar, or
-    a float64 [B] device tensor."""
+    a float64 [B] device tensor.  inv_hist_pp: a float64 [B] device tensor of per-problem divisors 1 / hist[b] ->
+    pnp_saga_table_update_hist_pp (table [max hist, B, ...]); None: the call above, unchanged."""
     require_gpu()
     B, hist = z.shape[0], table.shape[0]
     n = z.numel() // B
@@ -911,6 +930,12 @@ def saga_table_update_pp(z, g, table, row, prev_row, tsum, lr, inv_hist):
     for t in (row, prev_row):
         assert t.dtype == torch.int32 and tuple(t.shape) == (B,)
     lr = _pp(lr, B)
+    if inv_hist_pp is not None:
+        ih = _pp(inv_hist_pp, B)
+        assert ih[1] is not None, 'inv_hist_pp: a [B] float64 device tensor'
+        N.call('pnp_saga_table_update_hist_pp', _p(z), _p(g), _p(table), _p(row), _p(prev_row), _p(tsum), lr[0], _p(lr[1]), float(inv_hist),
+               _p(ih[1]), int(hist), int(B), int(n), _DT[z.dtype], _stream())
+        return
     N.call('pnp_saga_table_update_pp', _p(z), _p(g), _p(table), _p(row), _p(prev_row), _p(tsum), lr[0], _p(lr[1]), float(inv_hist),
            int(hist), int(B), int(n), _DT[z.dtype], _stream())
 

@@ -154,7 +154,7 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
                 hist_size=50, H=256, W=256, dtype=torch.float32, max_batch=128, seeding='generator', variant='svrg', run_seed=1,
                 keep_trace=False, graph=True, kernel='Minimal', lr_decay=1.0, denoiser_kwargs=None, sigma_modifier=None,
                 shared_matrix=False, wide_trials=False, sarah_trials=False, t2_trials=False, objective=False, sarah_fused=False,
-                fused_steps=False, one_launch=False):
+                fused_steps=False, one_launch=False, hist_trials=False):
     """Runner for `run_sweep` / `grid_search` over any cell of the reference's sweep (script_diff_sampratio_set12.py:23-25,
     41-51, 64-131): problem in {'csmri', 'deblur', 'pr'} x algorithm in {'gd', 'sgd', 'svrg', 'saga', 'sarah'} x denoiser in
     {'tv', 'nlm', factory}; `n_inner` inner iterations (prox evaluations of the stepped iterate) per item, hyper-parameters
@@ -211,6 +211,10 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
     pnp_csmri_sarah_outer_iteration each (`run_outer(n, one_launch=True)`, where the engine's `outer_kernel_ok()` holds and the step
     counts are multiples of T2); with fused_steps they advance by `run_span(n)`.  The same bits as without it.  False (default):
     engines, launches, rows and messages are exactly what they were.
+    hist_trials: opt in to 'hist_size' as a per-problem trial key of a trial-batched grid, algorithm='saga' only (ValueError
+    for another algorithm once a trial names 'hist_size'), on the batches batch_trials already takes for saga: a slab whose trials name
+    'hist_size' runs on a SagaEngine with a [B] hist_size, its table dense over the largest value.  Without it `check_trials` refuses
+    the key as it always has.  `run(items)` itself is unchanged by it.
     Beside `run(items)` the runner offers the pieces of a trial-batched grid (`grid_search(batch_trials=True)`):
     `run.prepare_data(items)` builds a rank's batches WITHOUT engines, `run.run_trials(data, trials, max_batch_trials)` runs a list
     of trials ({'eta', 'mini_batch_size', 'sigma_modifier'} overrides) on them as tiled batches, `run.data_key` says which runners
@@ -431,15 +435,17 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
                 base.tiles = {nt: base.batch.tile(nt)}           # (one tiled copy at a time: slabs of one size reuse it)
             self.batch = base.tiles[nt]
             per_t2 = t2_trials and any('T2' in tr for tr in trials)
-            lay = trial_layout(n, trials, {'eta': eta, 'mini_batch_size': mb, 'sigma_modifier': dkw.get('sigma_modifier', 1.0), 'T2': T2},
-                               keys=PER_PROBLEM_KEYS + ('T2',) if per_t2 else PER_PROBLEM_KEYS)
+            per_hist = hist_trials and any('hist_size' in tr for tr in trials)
+            lay = trial_layout(n, trials, {'eta': eta, 'mini_batch_size': mb, 'sigma_modifier': dkw.get('sigma_modifier', 1.0), 'T2': T2,
+                                           'hist_size': hist_size},
+                               keys=PER_PROBLEM_KEYS + (('T2',) if per_t2 else ()) + (('hist_size',) if per_hist else ()))
             pkw = dict(dkw)
             if any('sigma_modifier' in tr for tr in trials):
                 pkw['sigma_modifier'] = lay['sigma_modifier']
             self.eng = E.make_engine(self.batch, make_prox(denoiser, **pkw), lay['eta'], lay['T2'] if per_t2 else T2,
                                      None if algorithm == 'gd' else lay['mini_batch_size'], lr_decay=lr_decay, variant=variant,
-                                     algorithm=algorithm, hist_size=hist_size, seed=base.items[0]['id'] + 1, draw_id=lay['draw_id'],
-                                     **eng_kw)
+                                     algorithm=algorithm, hist_size=lay['hist_size'] if per_hist else hist_size,
+                                     seed=base.items[0]['id'] + 1, draw_id=lay['draw_id'], **eng_kw)
 
     def _group_chunks(items):
         groups = {}
@@ -459,6 +465,11 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
                 raise ValueError(f"batch_trials: trial key 'T2' has no per-problem form for algorithm {algorithm!r} (t2_trials: 'svrg' "
                                  'only; SarahEngine logs its outer prox in a row of its own, the others have no T2)')
             keys = PER_PROBLEM_KEYS + ('T2',)
+        if hist_trials and any('hist_size' in tr for tr in trials):
+            if algorithm != 'saga':
+                raise ValueError(f"batch_trials: trial key 'hist_size' has no per-problem form for algorithm {algorithm!r} (hist_trials: "
+                                 "'saga' only; the others keep no gradient table)")
+            keys = keys + ('hist_size',)
         if problem == 'pr' and not shared_matrix:
             raise ValueError(f"batch_trials: problem {problem!r} is not supported (only 'csmri') unless its trials share the "
                              'matrix: pass shared_matrix=True to make_runner')
@@ -488,14 +499,16 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
     def run_trials(data, trials, max_batch_trials=1024, max_table_bytes=MAX_TABLE_BYTES):
         """trials: dicts of per-problem overrides -> [results of run(items) per trial], on `data` = prepare_data(items): every
         chunk runs its trials in slabs of at most max_batch_trials problems (at least one trial); a pnp_saga slab also keeps its
-        gradient table (hist_size * problems * H * W elements) within max_table_bytes, again with at least one trial."""
+        gradient table (hist_size * problems * H * W elements) within max_table_bytes, again with at least one trial; with
+        hist_trials the table of a slab is dense over its largest hist_size, so the cap takes the largest value the trials name."""
         check_trials(trials)
         out = [[] for _ in trials]
         for base in data:
             n = len(base.items)
             cap = None
             if algorithm == 'saga':
-                cap = table_trial_cap(n, hist_size, H * W, torch.empty((), dtype=dtype).element_size(), max_table_bytes)
+                h_max = max([int(tr.get('hist_size', hist_size)) for tr in trials]) if hist_trials else hist_size
+                cap = table_trial_cap(n, h_max, H * W, torch.empty((), dtype=dtype).element_size(), max_table_bytes)
             for t0, t1 in trial_slabs(len(trials), n, max_batch_trials, cap):
                 slab = _TrialSlab(base, trials[t0:t1])
                 slab.advance(n_inner)
@@ -597,8 +610,8 @@ PER_PROBLEM_KEYS = ('eta', 'mini_batch_size', 'sigma_modifier')
 
 def group_trials(trials, per_problem_keys=PER_PROBLEM_KEYS):
     """Trials (dicts, grid order) -> [(structural params, [trial indices])]: trials that agree in every key that is not per
-    problem (by default T2 included: it changes the schedule; `per_problem_keys` with 'T2' among them groups across it)
-    form a group, groups and members in order of first appearance."""
+    problem (by default T2 and hist_size included: they change the schedule and the table; `per_problem_keys` with 'T2' or 'hist_size'
+    among them groups across it) form a group, groups and members in order of first appearance."""
     groups = {}
     for t, tr in enumerate(trials):
         key = tuple((k, tr[k]) for k in tr if k not in per_problem_keys)
@@ -628,7 +641,7 @@ def trial_slabs(n_trials, n_items, max_batch_trials, max_trials=None):
 def trial_layout(n_items, trials, defaults, keys=PER_PROBLEM_KEYS):
     """Per-problem vectors of a slab of len(trials) trials over n_items items: problem b = t * n_items + i carries trial t's
     value of every per-problem key (`defaults` where the trial names none) and draw_id[b] = i.  keys: the per-problem keys to lay
-    out; with 'T2' among them the layout holds an int32 'T2' vector as well."""
+    out; with 'T2' or 'hist_size' among them the layout holds an int32 vector of that name as well."""
     nt = len(trials)
     lay = {'draw_id': np.tile(np.arange(n_items, dtype=np.int64), nt)}
     for k in keys:
@@ -636,12 +649,12 @@ def trial_layout(n_items, trials, defaults, keys=PER_PROBLEM_KEYS):
             lay[k] = None
             continue
         vals = np.repeat(np.array([tr.get(k, defaults.get(k)) for tr in trials]), n_items)
-        lay[k] = vals.astype(np.int32 if k in ('mini_batch_size', 'T2') else np.float64)
+        lay[k] = vals.astype(np.int32 if k in ('mini_batch_size', 'T2', 'hist_size') else np.float64)
     return lay
 
 
 def grid_search(items, make_runner, grid, group=None, *, batch_trials=False, max_batch_trials=1024, max_table_bytes=MAX_TABLE_BYTES,
-                batch_T2=False, score='psnr'):
+                batch_T2=False, score='psnr', batch_hist=False):
     """The sweep the reference scripts run (process_img, script_diff_sampratio_set12.py:103-131): for every work item
     search the hyper-parameters and keep the best trial.  `make_runner(**params)` returns a runner as `run_sweep`
     takes; each rank runs every trial on ITS shard of the items (one batched engine per trial), the reduction over
@@ -656,6 +669,9 @@ def grid_search(items, make_runner, grid, group=None, *, batch_trials=False, max
     also take pnp_sarah on csmri, on deblur with wide_trials=True and on pr with shared_matrix=True.
     batch_T2=True (with batch_trials=True; runners made with t2_trials=True, pnp_svrg only -- ValueError otherwise): 'T2' is a
     per-problem key too, so trials that differ in T2 share a batch instead of splitting the grid.  Off by default.
+    batch_hist=True (with batch_trials=True; runners made with hist_trials=True, pnp_saga only -- ValueError otherwise): 'hist_size' is
+    a per-problem key too, so trials that differ in hist_size share a batch whose gradient table is dense over the largest of them
+    (DESIGN 9.8).  Off by default.
     The rows returned are those of batch_trials=False.
     score: 'psnr' (default) keeps the trial with the smallest PSNR loss, as always; 'objective' keeps the trial with the smallest
     'f_final' -- the selection for measured data, where there is no ground truth -- and needs runners made with objective=True
@@ -675,9 +691,11 @@ def grid_search(items, make_runner, grid, group=None, *, batch_trials=False, max
     per_trial = []
     if batch_T2 and not batch_trials:
         raise ValueError('batch_T2 groups the trials of a trial-batched grid: it needs batch_trials=True')
+    if batch_hist and not batch_trials:
+        raise ValueError('batch_hist groups the trials of a trial-batched grid: it needs batch_trials=True')
     if batch_trials:
         per_trial, data = [None] * len(trials), {}
-        keys = PER_PROBLEM_KEYS + ('T2',) if batch_T2 else PER_PROBLEM_KEYS
+        keys = PER_PROBLEM_KEYS + (('T2',) if batch_T2 else ()) + (('hist_size',) if batch_hist else ())
         for _, idx in group_trials(trials, keys):
             run = check_runner(make_runner(**trials[idx[0]]))
             if not hasattr(run, 'run_trials'):

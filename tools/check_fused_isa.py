@@ -20,6 +20,8 @@ this script verifies on the ISA of every k_svrg_iter instantiation that
                                                           one kernel serves the plain and the _pp entry point), both rules
     python tools/check_fused_isa.py --spans [listing.s]   the one-launch forms instead (k_sarah_outer, k_grad_span: GD and SGD,
                                                           k_saga_span -- each serves its plain and its _pp entry point), both rules
+    python tools/check_fused_isa.py --hist [listing.s]    the SAGA forms with a per-problem divisor instead (k_saga_iter_hist: denoise on
+                                                          and off, k_saga_span_hist), both rules
 
 Also prints, per kernel, the spill traffic between workgroup barriers (where the register pressure bites)."""
 import re
@@ -45,10 +47,11 @@ def regs_of(text):
     return out
 
 
-def kernels(txt, pp=False, sarah=False, steps=False, spans=False):
+def kernels(txt, pp=False, sarah=False, steps=False, spans=False, hist=False):
     """(name, body) of every k_svrg_iter instantiation and of k_svrg_outer; pp: also k_svrg_outer_pp and k_svrg_span_pp;
     sarah: the k_sarah_iter and k_sarah_iter_pp instantiations instead; steps: the k_grad_step and k_saga_iter instantiations instead;
-    spans: k_sarah_outer, the k_grad_span instantiations and k_saga_span instead"""
+    spans: k_sarah_outer, the k_grad_span instantiations and k_saga_span instead; hist: the k_saga_iter_hist instantiations and
+    k_saga_span_hist instead"""
     names = ('_ZN3pnp11k_svrg_iter', '_ZN3pnp12k_svrg_outer') + (('_ZN3pnp15k_svrg_outer_pp', '_ZN3pnp14k_svrg_span_pp') if pp else ())
     if sarah:
         names = ('_ZN3pnp12k_sarah_iter', '_ZN3pnp15k_sarah_iter_pp')
@@ -56,6 +59,8 @@ def kernels(txt, pp=False, sarah=False, steps=False, spans=False):
         names = ('_ZN3pnp11k_grad_step', '_ZN3pnp11k_saga_iter')
     if spans:
         names = ('_ZN3pnp13k_sarah_outer', '_ZN3pnp11k_grad_span', '_ZN3pnp11k_saga_span')
+    if hist:
+        names = ('_ZN3pnp16k_saga_iter_hist', '_ZN3pnp16k_saga_span_hist')
     lines = txt.split('\n')
     i = 0
     while i < len(lines):
@@ -176,16 +181,17 @@ def main():
     sarah = '--sarah' in args                                   # the SARAH instantiations instead, with the store rule
     steps = '--steps' in args                                   # the minibatch forms instead, with the store rule
     spans = '--spans' in args                                   # the one-launch forms instead, with the store rule
+    hist = '--hist' in args                                     # the per-problem-divisor SAGA forms instead, with the store rule
     paths = [a for a in args if not a.startswith('-')]
     txt = listing(paths[0] if paths else None, defines)
     bad = []
     nk = 0
-    for name, body in kernels(txt, pp, sarah, steps, spans):
+    for name, body in kernels(txt, pp, sarah, steps, spans, hist):
         nk += 1
         errors, n_loads, n_waits, segs = check(name, body)
         spill = ' '.join(f'{i}:{s["sst"]}/{s["sld"]}' for i, s in enumerate(segs) if s['sst'] or s['sld'])
         stores = ''
-        if sarah or steps or spans:
+        if sarah or steps or spans or hist:
             st_errors, n_st = check_stores(name, body)
             errors = errors + st_errors
             stores = f'{n_st} hand-issued stores, '
