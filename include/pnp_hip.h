@@ -413,6 +413,33 @@ int pnp_deblur_grad_pp(pnp_deblur_plan* plan, const void* z, const void* Y, cons
                        const double* scale_pp, void* out, void* stream);
 int pnp_deblur_grad_mb_pp(pnp_deblur_plan* plan, const void* z, const void* Y, const void* mbd, double scale,
                           const double* scale_pp, void* out, void* stream);
+/* Mixed-scale plans (a sampling-ratio sweep as one batch; csrc/deblur_mixed.hip): every problem has a down-sampler and
+ * a measurement count M_b of its own.  The plan owns n_sets distinct down-samplers -- the five arrays of pnp_deblur_plan_create
+ * concatenated over the sets, all HOST pointers: M_set [n_sets]; the tap rows of set s are rows [g_off[s], g_off[s+1]) of
+ * g_idx / g_w (M_set[s] rows, or none for the identity set, M_set[s] == H*W); its CSR entries are [nz_off[s], nz_off[s+1]) of
+ * a_col / a_val; a_rowptr holds H*W + 1 entries for every set WITH tables, in set order, each counting from 0.  Problem b works
+ * on set set_of[b] and M_vec[b] must be that set's M.  Mmax = max M_b.  Y, sel, the forward output and the plan's scratch are
+ * [batch][Mmax]: entries m >= M_b of a row are padding that no call reads into a result; the forward pass and the generator write
+ * them as zero.  Destroy with pnp_deblur_plan_destroy.  PNP_ERR_ARG before any device work: a NULL array, set_of out of range,
+ * M_vec[b] != M of its set, M_s outside [1, H*W], tables that point outside the image or the set's measurements.  The other
+ * pnp_deblur_* calls refuse a mixed plan, and the _mixed calls a plan of pnp_deblur_plan_create (PNP_ERR_ARG).
+ * pnp_deblur_generate takes either.
+ * The calls below scale problem b by scale_pp ? scale_pp[b] : scale, as the _pp forms do; the blurs are those of the uniform
+ * plan over the whole batch and the tap / CSR sums keep the order of the uniform kernels, so a problem WITH a down-sampler equals,
+ * bit for bit, the same problem in a uniform batch of its scale, wherever it sits and whatever its neighbours are (an identity
+ * problem takes "- Y" behind the blur's rounding instead of inside its epilogue: equal to rounding).  No allocation, no
+ * synchronisation: capturable.  pnp_deblur_objective_mixed: f_out[b] = (scale / M_b) * sum over m < M_b of (S_b B z - Y)^2
+ * (the host passes scale = 1/2), sums as pnp_deblur_objective's.                                                           */
+int pnp_deblur_plan_create_mixed(pnp_deblur_plan** plan, int H, int W, int batch, int dtype, const void* Bk, int n_sets,
+                                 const int32_t* M_set, const int32_t* g_off, const int32_t* g_idx, const void* g_w,
+                                 const int32_t* nz_off, const int32_t* a_rowptr, const int32_t* a_col, const void* a_val,
+                                 const int32_t* set_of, const int32_t* M_vec);
+int pnp_deblur_grad_mixed(pnp_deblur_plan* plan, const void* z, const void* Y, const uint8_t* sel, double scale,
+                          const double* scale_pp, void* out, void* stream);
+int pnp_deblur_grad_mb_mixed(pnp_deblur_plan* plan, const void* z, const void* Y, const void* mbd, double scale,
+                             const double* scale_pp, void* out, void* stream);
+int pnp_deblur_forward_mixed(pnp_deblur_plan* plan, const void* x, void* out, void* stream);
+int pnp_deblur_objective_mixed(pnp_deblur_plan* plan, const void* z, const void* Y, double scale, double* f_out, void* stream);
 
 /* ------------------------------------------------------------------ phase retrieval
  * Replaces problems/PR.py:75-87.  A [M][N] row-major, w [N], y [M] (device, `dtype`).
@@ -472,7 +499,10 @@ int pnp_pr_grad_shared_pp(const void* A, const void* Y, const void* W, const voi
  * outputs do not depend on the batch size or on its index in the batch.
  *
  * pnp_deblur_generate (problems/DeblurSR.py:38-57 per item) on an existing plan (identity or bilinear): xrec [batch][H*W] =
- * images[image_idx[b]]; Y [batch][M] = S B xrec (the plan's forward pass) + sigma * n; xinit [batch][H*W]; sigma [batch] double.  */
+ * images[image_idx[b]]; Y [batch][M] = S B xrec (the plan's forward pass) + sigma * n; xinit [batch][H*W]; sigma [batch] double.
+ * On a mixed-scale plan (pnp_deblur_plan_create_mixed) Y is [batch][Mmax]: Y_b = S_b B xrec_b + sigma_b * n over m < M_b with
+ * sigma_b from ||Y0_b|| over its M_b entries, zeros in the padding; the noise is keyed by the item's id and m, so an item's
+ * Y[:M_b], xinit and sigma equal, bit for bit, those a uniform plan of its scale generates, whatever its neighbours.          */
 int pnp_deblur_generate(pnp_deblur_plan* plan, const void* images, int n_images, const int32_t* image_idx,
                         const double* snr_fac, const uint64_t* seed, const uint64_t* id, void* xrec, void* Y, void* xinit,
                         double* sigma, void* stream);
@@ -635,6 +665,16 @@ int pnp_log_append_inc(const double* src, int n, double* log, int n_log, uint32_
 int pnp_draw_thresholds(int M, int batch, int mb, uint64_t seed, uint32_t step0, int nsteps, const uint32_t* step_dev,
                         void* mbd, void* stream);
 int pnp_indicator_from_thresholds(int M, int batch, const void* mbd, uint8_t* sel, void* stream);
+/* pnp_draw_thresholds_pp with a population per problem (mixed-scale Deblur batches): the candidates of problem b are
+ * 0 .. M_vec[b] - 1 (M_vec: int32 [batch] on the device).  With the same draw_id, mb, seed and step, problem b's descriptor equals,
+ * bit for bit, the one pnp_draw_thresholds_pp(M_vec[b], ...) gives.  mb_vec[b] >= M_vec[b] selects every candidate (the front end
+ * refuses mb_vec[b] > M_vec[b]); consumers stop at M_b themselves.  seed_vec (uint64 [batch] on the device, or NULL): problem b's
+ * stream absorbs seed_vec[b] in place of `seed` -- the items of a sweep keep the streams of the groups they would have run in
+ * (sweep.make_runner(mixed_scales=True)).  pnp_indicator_from_thresholds_m: the indicator with row
+ * stride Mmax, sel [batch][Mmax], zero for m >= M_vec[b].                                                                   */
+int pnp_draw_thresholds_mpp(const int32_t* M_vec, int batch, const int32_t* mb_vec, const uint32_t* draw_id, uint64_t seed,
+                            const uint64_t* seed_vec, uint32_t step0, int nsteps, const uint32_t* step_dev, void* mbd, void* stream);
+int pnp_indicator_from_thresholds_m(const int32_t* M_vec, int Mmax, int batch, const void* mbd, uint8_t* sel, void* stream);
 int pnp_rows_from_thresholds(int M, int batch, int mb, const void* mbd, int32_t* rows, void* stream);
 /* indicator from host-drawn index lists (np.random.choice output): idx [batch][n] int32 -> sel [batch][M] uint8   */
 int pnp_indicator_from_indices(const int32_t* idx, int n, int M, int batch, uint8_t* sel, void* stream);

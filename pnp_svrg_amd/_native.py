@@ -124,6 +124,14 @@ SIGNATURES = {
     'pnp_deblur_objective': (_i, [_vp, _vp, _vp, _d, _vp, _vp]),
     'pnp_pr_objective_workspace_bytes': (_sz, [_i, _i]),
     'pnp_pr_objective': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _d, _vp, _vp, _vp]),
+    # mixed-scale Deblur batches (csrc/deblur_mixed.hip): a down-sampler and a measurement count per problem
+    'pnp_deblur_plan_create_mixed': (_i, [ctypes.POINTER(_vp), _i, _i, _i, _i, _vp, _i] + [_vp] * 10),
+    'pnp_deblur_grad_mixed': (_i, [_vp, _vp, _vp, _vp, _d, _vp, _vp, _vp]),
+    'pnp_deblur_grad_mb_mixed': (_i, [_vp, _vp, _vp, _vp, _d, _vp, _vp, _vp]),
+    'pnp_deblur_forward_mixed': (_i, [_vp, _vp, _vp, _vp]),
+    'pnp_deblur_objective_mixed': (_i, [_vp, _vp, _vp, _d, _vp, _vp]),
+    'pnp_draw_thresholds_mpp': (_i, [_vp, _i, _vp, _vp, ctypes.c_uint64, _vp, ctypes.c_uint32, _i, _vp, _vp, _vp]),
+    'pnp_indicator_from_thresholds_m': (_i, [_vp, _i, _i, _vp, _vp, _vp]),
     'pnp_legacy_choice':(_i, [_vp, ctypes.POINTER(ctypes.c_int), _vp, _i, _i, _vp, _vp]),
 }
 

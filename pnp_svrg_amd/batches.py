@@ -292,32 +292,84 @@ class CsmriBatch(_BatchBase):
 
 
 class DeblurBatch(_BatchBase):
-    """B Deblur / super-resolution problems sharing one blur kernel and one down-sampler (reference
-    problems/DeblurSR.py:17-147 per problem; the sweeps vary image, noise and seed, not the operator)."""
+    """B Deblur / super-resolution problems sharing one blur kernel (reference problems/DeblurSR.py:17-147 per problem).
+    By default they also share one down-sampler: the sweeps that vary image, noise and seed.  With a SEQUENCE of B `scale_percent`
+    values (the sampling-ratio sweep) every problem has a down-sampler and a measurement count of its own: `M_vec`
+    ([B] ints) holds them, `M` is their maximum, and Y, the indicators and the forward output are [B, M] with entries m >= M_vec[b]
+    of a row as padding (zero in Y, read by no kernel).  A problem of such a batch with scale_percent < 100 walks, bit for bit,
+    what it walks in a uniform batch of its scale; one with scale_percent == 100 agrees to rounding."""
     kind = 'deblur'
     per_problem = True
+    M_vec = None                                                # mixed scales: per-problem measurement counts, host int32 [B]
+    draw_seeds = None                                           # mixed scales: per-problem seeds of the device draws (see `draw`)
 
-    def __init__(self, xrec, Bk, Y, xinit, dtype=torch.float32, device='cuda', bilinear=None, *, _state=None):
+    def __init__(self, xrec, Bk, Y, xinit, dtype=torch.float32, device='cuda', bilinear=None, *, scale_percent=None, _state=None):
         if _state is not None:
             return self._init(**_state)
         B, H, W = xrec.shape
+        if scale_percent is not None and np.ndim(scale_percent) != 0:
+            # mixed scales: Y as B per-problem arrays of M_b entries, or as one padded [B, Mmax] array
+            from .problems import deblur_operator_sets
+            if bilinear is not None:
+                raise ValueError('DeblurBatch: pass either bilinear (one down-sampler) or a sequence of scale_percent, not both')
+            if len(scale_percent) != B:
+                raise ValueError(f'DeblurBatch: {B} problems need {B} scale_percent values, got {len(scale_percent)}')
+            sets, set_of, M_vec = deblur_operator_sets(H, W, scale_percent)
+            Mmax = int(M_vec.max())
+            if isinstance(Y, np.ndarray) and Y.ndim == 2:
+                if Y.shape != (B, Mmax):
+                    raise ValueError(f'DeblurBatch: a padded Y must be [{B}, {Mmax}], got {Y.shape}')
+                Yp = np.array(Y, np.float64)
+            else:
+                if len(Y) != B or any(np.size(y) != m for y, m in zip(Y, M_vec)):
+                    raise ValueError(f'DeblurBatch: per-problem Y arrays must hold {M_vec.tolist()} entries, got '
+                                     f'{[int(np.size(y)) for y in Y]}')
+                Yp = np.zeros((B, Mmax))
+                for b, y in enumerate(Y):
+                    Yp[b, :M_vec[b]] = np.ravel(y)
+            for b in range(B):
+                Yp[b, M_vec[b]:] = 0.0                          # the padding is zero by definition
+            plan = ops.DeblurPlan.mixed(H, W, dtype, Bk, sets, set_of, M_vec, device=device)
+            return self._init(plan, self._upload(xrec, dtype, device), self._upload(xinit, dtype, device, (B, H, W)),
+                              self._upload(Yp, dtype, device, (B, Mmax)))
+        if scale_percent is not None:                           # an int: exactly the batch `bilinear=` of that scale builds
+            from .problems import _deblur_taps
+            if bilinear is not None:
+                raise ValueError('DeblurBatch: pass either bilinear or scale_percent, not both')
+            bilinear = _deblur_taps(H, W, int(scale_percent))
         plan = ops.DeblurPlan(H, W, B, dtype, Bk, bilinear=bilinear)
         self._init(plan, self._upload(xrec, dtype, device), self._upload(xinit, dtype, device, (B, H, W)),
                    self._upload(Y, dtype, device, (B, plan.M)))
 
     def _init(self, plan, xrec, xinit, Y, sigma=None):
         """sigma: [B] float64 noise levels (a generated batch)."""
-        self._init_base(xrec, xinit, plan.M)
+        self._init_base(xrec, xinit, plan.M if plan.M_vec is None else plan.M_vec)
         self.plan, self.M, self.Y, self.sigma = plan, plan.M, Y, sigma
+        self.M_vec = plan.M_vec
+        self._scale_cache, self._mb_cache, self._pinned = {}, {}, set()
+
+    def _check_mb(self, mb):
+        if self.M_vec is not None and np.ndim(mb) == 0:         # mixed scales: a scalar against every problem's own M_b
+            mb = np.full(self.B, int(mb), np.int64)
+        return super()._check_mb(mb)
 
     @classmethod
     def generate(cls, images, items, H=256, W=256, dtype=torch.float32, kernel='Minimal', scale_percent=100, device='cuda'):
         """The problems of `items` (dicts of sweep.make_items; their alpha is NOT read: the operator comes from `kernel` and
         `scale_percent`) generated ON THE DEVICE from the counter-based stream of include/pnp_hip.h (pnp_deblur_generate):
         Y = S B x + noise, Xinit uniform in [0, 1) -- problems/DeblurSR.py:38-57 per item, NOT NumPy's streams.  images: a list of
-        H x W arrays, or the tensor `upload_images` made of them.  Also sets `sigma` ([B] float64, device)."""
-        from .problems import _deblur_taps
+        H x W arrays, or the tensor `upload_images` made of them.  Also sets `sigma` ([B] float64, device).
+        scale_percent: an int, or one int per item (a mixed-scale batch): an item's Y[:M_b], xinit, xrec and sigma are then those a
+        uniform `generate` of its scale gives, bit for bit, and the padding of Y is zero."""
+        from .problems import _deblur_taps, deblur_operator_sets
         from .sweep import _minimal_kernel
+        if np.ndim(scale_percent) != 0:
+            if len(scale_percent) != len(items):
+                raise ValueError(f'generate: {len(items)} items need {len(items)} scale_percent values, got {len(scale_percent)}')
+            sets, set_of, M_vec = deblur_operator_sets(H, W, scale_percent)
+            images, par = cls._generate_inputs(images, items, H, W, dtype, device)
+            plan = ops.DeblurPlan.mixed(H, W, dtype, _minimal_kernel(H, W, kernel), sets, set_of, M_vec, device=images.device)
+            return cls._of(plan=plan, **plan.generate(images, *par))
         images, par = cls._generate_inputs(images, items, H, W, dtype, device)
         plan = ops.DeblurPlan(H, W, len(items), dtype, _minimal_kernel(H, W, kernel), bilinear=_deblur_taps(H, W, scale_percent))
         return cls._of(plan=plan, **plan.generate(images, *par))
@@ -325,6 +377,10 @@ class DeblurBatch(_BatchBase):
     @classmethod
     def from_problems(cls, probs, dtype=torch.float32, device='cuda'):
         p0 = probs[0]
+        scales = [getattr(p, 'scale_percent', None) for p in probs]
+        if any(s != scales[0] for s in scales):                 # problems of different scales: a mixed-scale batch
+            return cls(np.stack([p.Xrec for p in probs]), p0.B, [p.Y for p in probs], np.stack([p.Xinit for p in probs]),
+                       dtype=dtype, device=device, scale_percent=scales)
         return cls(np.stack([p.Xrec for p in probs]), p0.B, np.stack([p.Y for p in probs]),
                    np.stack([p.Xinit for p in probs]), dtype=dtype, device=device,
                    bilinear=getattr(p0, 'Bop', None) if isinstance(getattr(p0, 'Bop', None), tuple) else None)
@@ -356,6 +412,9 @@ class DeblurBatch(_BatchBase):
         return cls(xrec, Bk, Y, rng.uniform(0.0, 1.0, (B, N)), dtype=dtype)
 
     def draw_minibatches(self, n_steps, mb, seed=1):
+        if self.M_vec is not None:
+            raise ValueError('draw_minibatches draws from one population for all problems; a mixed-scale DeblurBatch has one per '
+                             'problem: use device draws (draw), or set_host with indices below every M_vec[b]')
         self._check_mb(mb)
         rng = np.random.default_rng(seed)
         out = np.stack([[rng.choice(self.M, mb, replace=False) for _ in range(self.B)] for _ in range(n_steps)]).astype(np.int32)
@@ -368,23 +427,33 @@ class DeblurBatch(_BatchBase):
         if n < 1:
             raise ValueError('tile(n) needs n >= 1')
         rep = lambda v: None if v is None else v.repeat((n,) + (1,) * (v.dim() - 1)).contiguous()
-        return self._of(plan=self.plan.resized(self.B * n), xrec=rep(self.xrec), xinit=rep(self.xinit), Y=rep(self.Y),
-                        sigma=rep(self.sigma))
+        t = self._of(plan=self.plan.resized(self.B * n), xrec=rep(self.xrec), xinit=rep(self.xinit), Y=rep(self.Y),
+                     sigma=rep(self.sigma))
+        t.draw_seeds = rep(self.draw_seeds)
+        return t
 
     def draw(self, mbs, mb, seed, step0, nsteps=1, step_dev=None, draw_id=None):
         """mb: an int, or per problem: [B] integers on the host (checked, then uploaded) or an int32 [B] device tensor (taken as
         checked: the engines check their host copy once).  draw_id: int32 [B] device tensor, the ids the minibatch streams absorb in
-        place of the batch index."""
+        place of the batch index.  On a mixed-scale batch `draw_seeds` (int64 [B] device tensor, or None) gives every problem a seed
+        of its own in place of `seed`: in a sweep an item keeps the stream of the group it would have run in."""
         if not isinstance(mb, torch.Tensor):
             self._check_mb(mb)
             if np.ndim(mb) != 0:
                 mb = torch.from_numpy(np.ascontiguousarray(mb, np.int32)).to(self.device)
-        ops.draw_thresholds(self.M, self.B, mb, seed, step0, nsteps, out=mbs.mbd[:nsteps], step_dev=step_dev, draw_id=draw_id)
+        if self.M_vec is not None:                              # mixed scales: problem b draws among its own M_vec[b] measurements
+            if not isinstance(mb, torch.Tensor):                # (the int32 vector of a scalar: made once per value)
+                mb = self._cached(self._mb_cache, int(mb), lambda: torch.full((self.B,), int(mb), dtype=torch.int32, device=self.device))
+            ops.draw_thresholds_mpp(self.plan.M_dev, mb, seed, step0, nsteps, out=mbs.mbd[:nsteps], step_dev=step_dev, draw_id=draw_id,
+                                    seed_vec=self.draw_seeds)
+        else:
+            ops.draw_thresholds(self.M, self.B, mb, seed, step0, nsteps, out=mbs.mbd[:nsteps], step_dev=step_dev, draw_id=draw_id)
         for j in range(nsteps):
             mbs.host[j] = None
 
     def set_host(self, mbs, j, idx):
-        """idx: int32 [B, mb] measurement indices (np.flatnonzero of Problem.select_mb's indicator)."""
+        """idx: int32 [B, mb] measurement indices (np.flatnonzero of Problem.select_mb's indicator); on a mixed-scale batch row b
+        holds indices below M_vec[b] and the indicator has the row stride M."""
         mbs.host[j] = ops.indicator_from_indices(idx, self.M, out=mbs.host[j] if isinstance(mbs.host[j], torch.Tensor) else None)
 
     def _sel(self, mbs, j):
@@ -395,15 +464,40 @@ class DeblurBatch(_BatchBase):
     def objective(self, z, out=None):
         """f(z) = ||Y - S B z||^2 / 2 / M per problem (problems/DeblurSR.py:114-117) -> float64 [B] on the device
         (pnp_deblur_objective); nothing is read back."""
+        if self.M_vec is not None:                              # mixed scales: the kernel divides 1/2 by each problem's own M_b
+            return self.plan.objective(z, self.Y, 0.5, out=out)
         return self.plan.objective(z, self.Y, 0.5 / self.M, out=out)
 
     # alpha (and gamma of grad_stoch_diff): a scalar -> the plain calls; a float64 [B] device tensor -> the `_pp` entry points
     def _over_m(self, a):
-        return a / self.M
+        return a / (self.M if self.M_vec is None else self.M_vec)     # (mixed scales: per problem, alpha_b / M_b)
+
+    def _cached(self, cache, key, make):
+        """cache[key], made on first use.  A value looked up while the stream captures is pinned for the life of the batch: the
+        captured graph points to its tensor.  Of the others at most 16 are kept per cache, the oldest dropped first (a decaying
+        step size makes a new value every step)."""
+        if key not in cache:
+            loose = [k for k in cache if (id(cache), k) not in self._pinned]
+            for k in loose[:max(0, len(loose) - 15)]:
+                del cache[k]
+            cache[key] = make()
+        if torch.cuda.is_current_stream_capturing():
+            self._pinned.add((id(cache), key))
+        return cache[key]
+
+    def _scalar_over_m(self, alpha):
+        """Mixed scales: a scalar alpha over every problem's own M_b -- each quotient the float64 one a uniform batch takes on the
+        host -- as a float64 [B] device tensor, uploaded once per value (so a replayed capture sees no upload)."""
+        key = float(alpha)
+        return self._cached(self._scale_cache, key,
+                            lambda: torch.from_numpy(np.array([key / int(m) for m in self.M_vec], np.float64)).to(self.device))
 
     def grad_full(self, z, out, alpha=1.0, beta=0.0, c1=None):
-        # (per problem: alpha_b / M taken on the host in float64, as the scalar's quotient is)
-        scale = self._host(alpha, self._over_m) if isinstance(alpha, torch.Tensor) else alpha / self.M
+        # (per problem: alpha_b / M taken on the host in float64, as the scalar's quotient is; mixed scales: alpha / M_b)
+        if isinstance(alpha, torch.Tensor):
+            scale = self._host(alpha, self._over_m)
+        else:
+            scale = alpha / self.M if self.M_vec is None else self._scalar_over_m(alpha)
         g = self.plan.grad(z, self.Y, scale=scale, out=out if c1 is None else self._scratch(z))
         return self._combine(g, out, beta, c1)
 

@@ -342,11 +342,33 @@ extern "C" int pnp_deblur_plan_create(pnp_deblur_plan** out, int H, int W, int b
 extern "C" int pnp_deblur_plan_destroy(pnp_deblur_plan* p) {
     if (!p) return PNP_OK;
     for (void* q : {p->tw_line, p->tw_big, p->FB, p->w0, p->r0, p->r1, (void*)p->g_idx, p->g_w, (void*)p->a_rowptr,
-                    (void*)p->a_col, p->a_val, p->down})
+                    (void*)p->a_col, p->a_val, p->down, (void*)p->mx_prob, (void*)p->mx_M})
         if (q) (void)hipFree(q);
     delete p;
     return PNP_OK;
 }
+
+// the blurs of a gradient for the mixed-scale forms (deblur_mixed.hip): the same launches with the same arguments
+int pnp::deblur_blur(pnp_deblur_plan* p, const void* x, bool conj_kernel, double alpha, void* out, void* stream,
+                     const double* alpha_pp, double alpha_div) {
+    hipStream_t s = (hipStream_t)stream;
+    if (p->dtype == PNP_F32) {
+        const float* xx = (const float*)x;
+        float* oo = (float*)out;
+        const float a = (float)alpha;
+        return p->NL == 16 ? blur<float, 16, 16>(p, xx, conj_kernel, a, 0.f, nullptr, nullptr, oo, s, nullptr, alpha_pp, alpha_div)
+             : p->NL == 12 ? blur<float, 8, 16>(p, xx, conj_kernel, a, 0.f, nullptr, nullptr, oo, s, nullptr, alpha_pp, alpha_div)
+                           : blur<float, 8, 8>(p, xx, conj_kernel, a, 0.f, nullptr, nullptr, oo, s, nullptr, alpha_pp, alpha_div);
+    }
+    const double* xx = (const double*)x;
+    double* oo = (double*)out;
+    return p->NL == 16 ? blur<double, 16, 16>(p, xx, conj_kernel, alpha, 0.0, nullptr, nullptr, oo, s, nullptr, alpha_pp, alpha_div)
+         : p->NL == 12 ? blur<double, 8, 16>(p, xx, conj_kernel, alpha, 0.0, nullptr, nullptr, oo, s, nullptr, alpha_pp, alpha_div)
+                       : blur<double, 8, 8>(p, xx, conj_kernel, alpha, 0.0, nullptr, nullptr, oo, s, nullptr, alpha_pp, alpha_div);
+}
+
+// a mixed-scale plan has per-problem measurement counts: only the _mixed entry points know its layout
+#define PNP_DB_UNIFORM(p) PNP_CHECK_ARG((p)->n_sets == 0, "mixed-scale plan: use the _mixed entry points")
 
 // the _pp forms: one dispatch over dtype and line length for both (sel or descriptors, never both)
 static int grad_pp(pnp_deblur_plan* p, const void* z, const void* Y, const uint8_t* sel, const MbDesc* d, double scale,
@@ -368,12 +390,14 @@ static int grad_pp(pnp_deblur_plan* p, const void* z, const void* Y, const uint8
 extern "C" int pnp_deblur_grad_pp(pnp_deblur_plan* p, const void* z, const void* Y, const uint8_t* sel, double scale,
                                   const double* scale_pp, void* out, void* stream) {
     PNP_CHECK_ARG(p && z && Y && out, "null argument");
+    PNP_DB_UNIFORM(p);
     return grad_pp(p, z, Y, sel, nullptr, scale, scale_pp, out, (hipStream_t)stream);
 }
 
 extern "C" int pnp_deblur_grad_mb_pp(pnp_deblur_plan* p, const void* z, const void* Y, const void* mbd, double scale,
                                      const double* scale_pp, void* out, void* stream) {
     PNP_CHECK_ARG(p && z && Y && mbd && out, "null argument");
+    PNP_DB_UNIFORM(p);
     return grad_pp(p, z, Y, nullptr, (const MbDesc*)mbd, scale, scale_pp, out, (hipStream_t)stream);
 }
 
@@ -381,6 +405,7 @@ extern "C" int pnp_deblur_grad_mb_pp(pnp_deblur_plan* p, const void* z, const vo
 extern "C" int pnp_deblur_grad(pnp_deblur_plan* p, const void* z, const void* Y, const uint8_t* sel, double scale,
                                void* out, void* stream) {
     PNP_CHECK_ARG(p && z && Y && out, "null argument");
+    PNP_DB_UNIFORM(p);
     hipStream_t s = (hipStream_t)stream;
     if (p->dtype == PNP_F32) {
         const float *zz = (const float*)z, *yy = (const float*)Y;
@@ -398,6 +423,7 @@ extern "C" int pnp_deblur_grad(pnp_deblur_plan* p, const void* z, const void* Y,
 extern "C" int pnp_deblur_grad_mb(pnp_deblur_plan* p, const void* z, const void* Y, const void* mbd, double scale,
                                   void* out, void* stream) {
     PNP_CHECK_ARG(p && z && Y && mbd && out, "null argument");
+    PNP_DB_UNIFORM(p);
     hipStream_t s = (hipStream_t)stream;
     const MbDesc* d = (const MbDesc*)mbd;
     if (p->dtype == PNP_F32) {
@@ -415,6 +441,7 @@ extern "C" int pnp_deblur_grad_mb(pnp_deblur_plan* p, const void* z, const void*
 // forward model S B x (DeblurSR.py:110-112), for problem setup / f(w); out real [batch][M]
 extern "C" int pnp_deblur_forward(pnp_deblur_plan* p, const void* x, void* out, void* stream) {
     PNP_CHECK_ARG(p && x && out, "null argument");
+    PNP_DB_UNIFORM(p);
     hipStream_t s = (hipStream_t)stream;
     if (p->dtype == PNP_F32) {
         const float* xx = (const float*)x;

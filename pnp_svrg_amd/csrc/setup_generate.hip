@@ -113,6 +113,39 @@ __global__ __launch_bounds__(256) void k_sg_noise(T* __restrict__ Y, int M, cons
     *y = (T)fma_(sigma[prob], nrm, (double)*y);
 }
 
+// The two kernels above for a mixed-scale Deblur plan: item b has M_vec[b] measurements in a row of Mmax.  The same statements over
+// m < M_b, so an item's sigma and Y[:M_b] are those of a uniform plan of its scale; the padding is neither read nor written.
+template <typename T>
+__global__ __launch_bounds__(256) void k_sg_sigma_m(const T* __restrict__ Y0, const int32_t* __restrict__ M_vec, int Mmax,
+                                                    const double* __restrict__ snr_fac, double H, double W,
+                                                    double* __restrict__ sigma) {
+    __shared__ double sh[256];
+    const int prob = blockIdx.x, M = M_vec[prob];
+    const T* y = Y0 + (size_t)prob * Mmax;
+    double acc = 0.0;
+    for (int m = threadIdx.x; m < M; m += 256) {
+        const double v = (double)y[m];
+        acc = fma_(v, v, acc);
+    }
+    const double ss = block_sum256(acc, sh);
+    if (threadIdx.x == 0) sigma[prob] = sqrt(sqrt(ss) * snr_fac[prob] / H / W);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_sg_noise_m(T* __restrict__ Y, const int32_t* __restrict__ M_vec, int Mmax,
+                                                    const uint64_t* __restrict__ seed, const uint64_t* __restrict__ id,
+                                                    const double* __restrict__ sigma) {
+    const int prob = blockIdx.y;
+    const int m = blockIdx.x * 256 + threadIdx.x;
+    if (m >= M_vec[prob]) return;
+    const uint64_t sd = seed[prob], it = id[prob];
+    const double u1 = sg_u1(mb_key(sg_state(sd, it, 1), (uint32_t)m));
+    const double u2 = sg_u2(mb_key(sg_state(sd, it, 2), (uint32_t)m));
+    const double nrm = sqrt(-2.0 * log(u1)) * cospi(2.0 * u2);
+    T* y = Y + (size_t)prob * Mmax + m;
+    *y = (T)fma_(sigma[prob], nrm, (double)*y);
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void k_sg_uniform(T* __restrict__ xinit, int n, const uint64_t* __restrict__ seed,
                                                     const uint64_t* __restrict__ id) {
@@ -358,6 +391,18 @@ int run_deblur_generate(pnp_deblur_plan* p, const void* images, int n_images, co
     const int N = p->N, B = p->batch, M = p->M;
     k_sg_gather<T><<<dim3((N + 255) / 256, B), 256, 0, s>>>((const T*)images, n_images, image_idx, (T*)xrec, N);
     PNP_CHECK_LAUNCH();
+    if (p->n_sets > 0) {
+        // a mixed-scale plan: Y [batch][Mmax], Y0_b = S_b B x_b with zeros in the padding; sigma and noise over m < M_b
+        int rc = pnp_deblur_forward_mixed(p, xrec, Y, s);
+        if (rc) return rc;
+        k_sg_sigma_m<T><<<B, 256, 0, s>>>((const T*)Y, p->mx_M, M, snr_fac, (double)p->n, (double)(N / p->n), sigma);
+        PNP_CHECK_LAUNCH();
+        k_sg_noise_m<T><<<dim3((M + 255) / 256, B), 256, 0, s>>>((T*)Y, p->mx_M, M, seed, id, sigma);
+        PNP_CHECK_LAUNCH();
+        k_sg_uniform<T><<<dim3((N + 255) / 256, B), 256, 0, s>>>((T*)xinit, N, seed, id);
+        PNP_CHECK_LAUNCH();
+        return PNP_OK;
+    }
     int rc = pnp_deblur_forward(p, xrec, Y, s);                            // Y0 = S B x through the plan's own forward pass
     if (rc) return rc;
     // H * W = N with H and W powers of two: the two divisions of the sigma formula are exact, so (n, N / n) stands for (H, W)

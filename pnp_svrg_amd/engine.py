@@ -835,6 +835,12 @@ class SarahEngine(_StochEngine):
         self._dev_step = self.s
 
 
+def saga_row_rng(seed):
+    """The generator a SagaEngine made with `seed` draws its table rows from, one `integers(hist_size)` per step (also what
+    `sweep.make_runner(mixed_scales=True)` hands each item: the rows of the engine of its default group)."""
+    return np.random.default_rng(seed + 977)
+
+
 class SagaEngine(_FusedStep, _StochEngine):
     """pnp_saga over a batch (algorithms/pnp_saga.py:25-72): a device table [hist][B][H][W] of minibatch
     gradients (all rows start as the first one), its running sum, and ONE fused kernel per step that replaces a
@@ -872,10 +878,10 @@ class SagaEngine(_FusedStep, _StochEngine):
         self.hist = hist_size if hv is None else int(hv.max())  # the table's row count
         self.hist_pp = hv                                       # per-problem history lengths (None: one for the batch)
         self.g = torch.empty_like(self.z)
-        self._rng = np.random.default_rng(seed + 977)
+        self._rng = saga_row_rng(seed)
         self._inv_hist_pp = None
         if hv is not None:                                      # one row stream per distinct value, each the scalar engine's
-            self._rngs = {int(h): np.random.default_rng(seed + 977) for h in np.unique(hv)}
+            self._rngs = {int(h): saga_row_rng(seed) for h in np.unique(hv)}
             # the divisors as the scalar path forms them (1.0 / hist_size in Python floats), uploaded once
             self._inv_hist_pp = torch.from_numpy(np.array([1.0 / int(h) for h in hv], np.float64)).to(self.z.device)
         self._rows = None                                       # (host rows, their int32 device vector) of the last batched update

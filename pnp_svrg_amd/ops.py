@@ -3,6 +3,7 @@ allocations and the HIP stream; every op below is one call into libpnp_hip.so.""
 import contextlib
 import ctypes
 import gc
+import numpy as np
 import torch
 from . import _native as N
 
@@ -692,6 +693,36 @@ class DeblurPlan:
             N.call('pnp_deblur_plan_create', ctypes.byref(h), H, W, batch, _DT[dtype], vp(Bk), self.M, *[vp(k) for k in keep])
         self._h = h
 
+    M_vec = None                                                # mixed-scale plans: the per-problem measurement counts (host int32 [B])
+
+    @classmethod
+    def mixed(cls, H, W, dtype, Bk, sets, set_of, M_vec, device='cuda'):
+        """pnp_deblur_plan_create_mixed: a plan whose problems each have a down-sampler of their own.  sets, set_of, M_vec: what
+        `problems.deblur_operator_sets` returns (the distinct down-samplers, problem -> set, problem -> M_b).  M is Mmax = max M_b:
+        Y, sel and the forward output are [B, Mmax], entries m >= M_b of a row are padding."""
+        require_gpu()
+        self = cls.__new__(cls)
+        set_of, M_vec = np.ascontiguousarray(set_of, np.int32), np.ascontiguousarray(M_vec, np.int32)
+        batch = int(set_of.shape[0])
+        self.H, self.W, self.N, self.B, self.dtype = H, W, H * W, batch, dtype
+        npdt = np.float32 if dtype == torch.float32 else np.float64
+        Bk = np.ascontiguousarray(Bk, dtype=npdt)
+        self._Bk, self._bilinear, self._sets, self._set_of = Bk, None, list(sets), set_of
+        self.M_vec, self.M = M_vec, int(M_vec.max())
+        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None and a.size else None
+        taps = [t for _, _, t in sets if t is not None]
+        cat = lambda k, dt: np.ascontiguousarray(np.concatenate([np.asarray(t[k]).reshape(-1) for t in taps]), dt) if taps else None
+        M_set = np.array([m for _, m, _ in sets], np.int32)
+        g_off = np.cumsum([0] + [0 if t is None else t[0].shape[0] for _, _, t in sets]).astype(np.int32)
+        nz_off = np.cumsum([0] + [0 if t is None else t[3].shape[0] for _, _, t in sets]).astype(np.int32)
+        keep = [cat(0, np.int32), cat(1, npdt), nz_off, cat(2, np.int32), cat(3, np.int32), cat(4, npdt)]
+        h = ctypes.c_void_p()
+        N.call('pnp_deblur_plan_create_mixed', ctypes.byref(h), H, W, batch, _DT[dtype], vp(Bk), len(sets), vp(M_set), vp(g_off),
+               *[vp(k) for k in keep], vp(set_of), vp(M_vec))
+        self._h = h
+        self.M_dev = torch.from_numpy(M_vec).to(device)          # what the draws and indicators take
+        return self
+
     def __del__(self):
         h, self._h = getattr(self, '_h', None), None
         if h:
@@ -707,6 +738,15 @@ class DeblurPlan:
         assert z.dtype == self.dtype and z.numel() == self.B * self.N and Y.numel() == self.B * self.M
         assert sel is None or mbd is None
         out = out if out is not None else torch.empty_like(z)
+        if self.M_vec is not None:                              # mixed scales: one entry point takes the scalar and the array
+            assert Y.dtype == self.dtype and (sel is None or (sel.dtype == torch.uint8 and sel.numel() == self.B * self.M))
+            sc = _pp(scale, self.B)
+            if mbd is not None:
+                assert mbd.dtype == torch.int64 and tuple(mbd.shape) == (self.B, 2)
+                N.call('pnp_deblur_grad_mb_mixed', self._h, _p(z), _p(Y), _p(mbd), sc[0], _p(sc[1]), _p(out), _stream())
+            else:
+                N.call('pnp_deblur_grad_mixed', self._h, _p(z), _p(Y), _p(sel), sc[0], _p(sc[1]), _p(out), _stream())
+            return out
         if mbd is not None:
             assert mbd.dtype == torch.int64 and tuple(mbd.shape) == (self.B, 2)
             _route('pnp_deblur_grad_mb', [self._h, _p(z), _p(Y), _p(mbd), _pp(scale, self.B), _p(out), _stream()])
@@ -715,19 +755,32 @@ class DeblurPlan:
         return out
 
     def resized(self, batch):
-        """A plan for `batch` problems on this plan's kernel spectrum and down-sampler (DeblurBatch.tile)."""
+        """A plan for `batch` problems on this plan's kernel spectrum and down-sampler (DeblurBatch.tile).  A mixed-scale plan
+        repeats its problems' sets: batch = n * B, problem t * B + i on the set of problem i."""
+        if self.M_vec is not None:
+            n, r = divmod(int(batch), self.B)
+            if n < 1 or r:
+                raise ValueError(f'a mixed-scale plan of {self.B} problems resizes to multiples of {self.B}, got {batch}')
+            return DeblurPlan.mixed(self.H, self.W, self.dtype, self._Bk, self._sets, np.tile(self._set_of, n), np.tile(self.M_vec, n),
+                                    device=self.M_dev.device)
         return DeblurPlan(self.H, self.W, int(batch), self.dtype, self._Bk, bilinear=self._bilinear)
 
     def forward(self, x, out=None):
         out = out if out is not None else torch.empty(self.B * self.M, dtype=self.dtype, device=x.device)
+        if self.M_vec is not None:                              # mixed scales: out [B, Mmax], zero in the padding
+            assert x.dtype == self.dtype and out.dtype == self.dtype and x.numel() == self.B * self.N and out.numel() == self.B * self.M
+            N.call('pnp_deblur_forward_mixed', self._h, _p(x), _p(out), _stream())
+            return out
         N.call('pnp_deblur_forward', self._h, _p(x), _p(out), _stream())
         return out
 
     def objective(self, z, Y, scale, out=None):
-        """pnp_deblur_objective: scale * sum over the M measurements of (S B z - Y)^2 per problem -> float64 [B]."""
+        """pnp_deblur_objective: scale * sum over the M measurements of (S B z - Y)^2 per problem -> float64 [B].  A mixed-scale
+        plan (pnp_deblur_objective_mixed) sums over m < M_b and divides `scale` by M_b itself: pass 1/2 for f."""
         assert z.dtype == self.dtype and Y.dtype == self.dtype and z.numel() == self.B * self.N and Y.numel() == self.B * self.M
         out = _f_out(out, self.B, z.device)
-        N.call('pnp_deblur_objective', self._h, _p(z), _p(Y), float(scale), _p(out), _stream())
+        N.call('pnp_deblur_objective_mixed' if self.M_vec is not None else 'pnp_deblur_objective', self._h, _p(z), _p(Y), float(scale),
+               _p(out), _stream())
         return out
 
     def generate(self, images, image_idx, snr_fac, seed, item_id):
@@ -886,6 +939,35 @@ def indicator_from_thresholds(M, mbd, out=None):
     B = mbd.shape[0]
     out = out if out is not None else torch.empty((B, M), dtype=torch.uint8, device=mbd.device)
     N.call('pnp_indicator_from_thresholds', int(M), int(B), _p(mbd), _p(out), _stream())
+    return out
+
+
+def draw_thresholds_mpp(M_vec, mb, seed, step0, nsteps=1, out=None, step_dev=None, draw_id=None, seed_vec=None):
+    """pnp_draw_thresholds_mpp: `draw_thresholds` with a population per problem (mixed-scale Deblur batches) -- problem b draws
+    mb_b of its M_vec[b] measurements (M_vec: int32 [B] device tensor) -> descriptors int64 [nsteps, B, 2], problem b's equal to
+    those of draw_thresholds(M_vec[b], ...) with the same id, mb, seed and step.  seed_vec: int64 [B] device tensor holding
+    64-bit seeds; problem b's stream then absorbs seed_vec[b] in place of `seed`."""
+    require_gpu()
+    assert M_vec.dtype == torch.int32 and M_vec.dim() == 1
+    B = M_vec.shape[0]
+    out = out if out is not None else torch.empty((nsteps, B, 2), dtype=torch.int64, device=M_vec.device)
+    if not isinstance(mb, torch.Tensor):
+        mb = torch.full((B,), int(mb), dtype=torch.int32, device=M_vec.device)
+    assert mb.dtype == torch.int32 and tuple(mb.shape) == (B,) and tuple(out.shape[1:]) == (B, 2) and out.shape[0] >= nsteps
+    assert draw_id is None or (draw_id.dtype == torch.int32 and tuple(draw_id.shape) == (B,))
+    assert seed_vec is None or (seed_vec.dtype == torch.int64 and tuple(seed_vec.shape) == (B,))
+    N.call('pnp_draw_thresholds_mpp', _p(M_vec), int(B), _p(mb), _p(draw_id), int(seed) & (2 ** 64 - 1), _p(seed_vec), int(step0) & 0xFFFFFFFF,
+           int(nsteps), _p(step_dev), _p(out), _stream())
+    return out
+
+
+def indicator_from_thresholds_m(M_vec, Mmax, mbd, out=None):
+    """pnp_indicator_from_thresholds_m: uint8 [B, Mmax], problem b's minibatch among m < M_vec[b], zero in the padding."""
+    require_gpu()
+    B = mbd.shape[0]
+    assert M_vec.dtype == torch.int32 and tuple(M_vec.shape) == (B,)
+    out = out if out is not None else torch.empty((B, Mmax), dtype=torch.uint8, device=mbd.device)
+    N.call('pnp_indicator_from_thresholds_m', _p(M_vec), int(Mmax), int(B), _p(mbd), _p(out), _stream())
     return out
 
 

@@ -324,6 +324,30 @@ def _deblur_taps(H, W, scale_percent, eps=1e-10):
     return _bilinear_taps(iava, (H, W))
 
 
+def deblur_operator_sets(H, W, scales):
+    """The down-samplers of a mixed-scale Deblur batch (DeblurBatch with a sequence of scale_percent; pure NumPy).  scales: the B
+    scale_percent values of its problems.  Returns (sets, set_of, M_vec): `sets` lists the DISTINCT scales in order of first
+    appearance as (scale_percent, M, taps) with taps = `_deblur_taps(H, W, scale_percent)` (None for 100, the identity);
+    set_of int32 [B] maps a problem to its set, M_vec int32 [B] is its measurement count."""
+    scales = [s for s in np.ravel(scales)]
+    if not scales:
+        raise ValueError('deblur_operator_sets needs at least one scale_percent')
+    sets, where, set_of = [], {}, []
+    for sp in scales:
+        if int(sp) != sp or not 1 <= int(sp) <= 100:
+            raise ValueError(f'scale_percent must be an integer in [1, 100], got {sp!r}')
+        sp = int(sp)
+        if sp not in where:
+            M = int(H * sp / 100) * int(W * sp / 100)
+            if M < 1:
+                raise ValueError(f'scale_percent {sp} leaves no measurement of a {H} x {W} image')
+            where[sp] = len(sets)
+            sets.append((sp, M, _deblur_taps(H, W, sp)))
+        set_of.append(where[sp])
+    set_of = np.array(set_of, np.int32)
+    return sets, set_of, np.array([sets[s][1] for s in set_of], np.int32)
+
+
 class Deblur(Problem):
     """reference problems/DeblurSR.py:16-147 with forward model and gradients on the MI355X."""
     eps = 1e-10

@@ -154,7 +154,7 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
                 hist_size=50, H=256, W=256, dtype=torch.float32, max_batch=128, seeding='generator', variant='svrg', run_seed=1,
                 keep_trace=False, graph=True, kernel='Minimal', lr_decay=1.0, denoiser_kwargs=None, sigma_modifier=None,
                 shared_matrix=False, wide_trials=False, sarah_trials=False, t2_trials=False, objective=False, sarah_fused=False,
-                fused_steps=False, one_launch=False, hist_trials=False):
+                fused_steps=False, one_launch=False, hist_trials=False, mixed_scales=False):
     """Runner for `run_sweep` / `grid_search` over any cell of the reference's sweep (script_diff_sampratio_set12.py:23-25,
     41-51, 64-131): problem in {'csmri', 'deblur', 'pr'} x algorithm in {'gd', 'sgd', 'svrg', 'saga', 'sarah'} x denoiser in
     {'tv', 'nlm', factory}; `n_inner` inner iterations (prox evaluations of the stepped iterate) per item, hyper-parameters
@@ -215,6 +215,13 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
     for another algorithm once a trial names 'hist_size'), on the batches batch_trials already takes for saga: a slab whose trials name
     'hist_size' runs on a SagaEngine with a [B] hist_size, its table dense over the largest value.  Without it `check_trials` refuses
     the key as it always has.  `run(items)` itself is unchanged by it.
+    mixed_scales: problem='deblur' only (a ValueError that names any other problem): a rank's Deblur items of ANY mix of alpha run as
+    one batch, or slabs of max_batch, on a mixed-scale DeblurBatch instead of one batch per alpha -- under
+    seeding='counter' through `DeblurBatch.generate(scale_percent=[...])`, under 'legacy' through `from_problems`; 'generator' keeps
+    its scale-100 rule.  Every item keeps the minibatch stream (seed and id) and, for pnp_saga, the table rows of the group the
+    default runner would have run it in, so its row equals the default runner's (items with alpha == 1.0: to rounding).  Rows come
+    back in item order; `prepare_data` / `run_trials` (wide_trials=True) run on the tiled mixed batch.  False (default): grouping,
+    engines, launches, rows and messages are exactly what they were.
     Beside `run(items)` the runner offers the pieces of a trial-batched grid (`grid_search(batch_trials=True)`):
     `run.prepare_data(items)` builds a rank's batches WITHOUT engines, `run.run_trials(data, trials, max_batch_trials)` runs a list
     of trials ({'eta', 'mini_batch_size', 'sigma_modifier'} overrides) on them as tiled batches, `run.data_key` says which runners
@@ -265,6 +272,11 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
     eng_kw = {'log_objective': True} if objective else {}       # (off: the engines are made with the arguments they always got)
     if sarah_fused or fused_steps:
         eng_kw = dict(eng_kw, fused=True)                       # (rides with the other opt-in engine keyword)
+    if not isinstance(mixed_scales, (bool, np.bool_)):
+        raise ValueError(f'mixed_scales: True or False, got {mixed_scales!r}')
+    if mixed_scales and problem != 'deblur':
+        raise ValueError(f"mixed_scales=True is for problem='deblur' (got {problem!r}): CSMRI items of any mix of ratios already share a "
+                         'batch, and the matrices of phase-retrieval items of different num_meas have different shapes')
     if shared_matrix and problem != 'pr':
         raise ValueError(f"shared_matrix=True is for problem='pr' (got {problem!r}): only its problems have a matrix to share")
     mb, dkw = mini_batch_size, dict(denoiser_kwargs or {})
@@ -282,7 +294,7 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
             return E.CsmriBatch(np.stack([t[0] for t in d]), np.stack([t[1] for t in d]), np.stack([t[2] for t in d]),
                                 np.stack([t[3] for t in d]).reshape(len(chunk), -1), dtype=dtype)
         if problem == 'deblur':
-            if deblur_scale_percent(a) != 100:
+            if any(deblur_scale_percent(it['alpha']) != 100 for it in chunk):
                 raise ValueError('generator seeding builds scale_percent == 100 Deblur items; use seeding="legacy" for the bilinear operator')
             Bk = _minimal_kernel(H, W, kernel)
             FB = np.fft.fft(Bk)
@@ -317,6 +329,9 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
         a = chunk[0]['alpha']
         if problem == 'csmri':
             return E.CsmriBatch.generate(dev_imgs, chunk, H, W, dtype)
+        if problem == 'deblur' and mixed_scales:
+            return E.DeblurBatch.generate(dev_imgs, chunk, H, W, dtype, kernel=kernel,
+                                          scale_percent=[deblur_scale_percent(it['alpha']) for it in chunk])
         if problem == 'deblur':
             return E.DeblurBatch.generate(dev_imgs, chunk, H, W, dtype, kernel=kernel, scale_percent=deblur_scale_percent(a))
         return E.PrBatch.generate(dev_imgs, chunk, H, W, pr_num_meas(a, H, W), dtype)
@@ -362,15 +377,33 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
             else:
                 self.batch, self.idx_d, self.rs = build_generator(chunk), None, None
             self.done = 0
+            self.streams = None
+            if mixed_scales and getattr(self.batch, 'M_vec', None) is not None:
+                # every item keeps the minibatch stream of the group the default runner runs it in: that group's seed, its place there
+                self.streams = [item_stream[it['id']] for it in chunk]
+                self.batch.draw_seeds = torch.from_numpy(np.array([s for s, _ in self.streams], np.int64)).to(self.batch.device)
             if not with_engine:                                 # data only: trial slabs put their engines on tiles of it
                 self.tiles = {}
                 return
             kw = dict(seed=chunk[0]['id'] + 1)
+            if self.streams is not None and algorithm != 'gd':
+                kw['draw_id'] = [k for _, k in self.streams]
+            self._row_rngs()
             if algorithm == 'saga' and self.idx_d is not None:
                 kw['idx0'] = self.idx_d[0]
             self.eng = E.make_engine(self.batch, make_prox(denoiser, **dkw), eta, T2, mb, lr_decay=lr_decay, variant=variant,
                                      algorithm=algorithm, hist_size=hist_size, **kw, **eng_kw)
             self.done = 0
+
+        def _row_rngs(self):
+            """mixed_scales, pnp_saga with device draws: the row streams of the default groups' engines (engine.saga_row_rng)."""
+            self.row_rng = None
+            if self.streams is not None and algorithm == 'saga' and self.idx_d is None:
+                self.row_rng = {s: E.saga_row_rng(s) for s, _ in self.streams}
+
+        def _rows(self):
+            draws = {s: int(g.integers(hist_size)) for s, g in self.row_rng.items()}
+            return np.array([draws[s] for s, _ in self.streams], np.int64)
 
         def advance(self, n):
             eng, idx_d = self.eng, self.idx_d
@@ -395,7 +428,9 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
                 eng.run_outer(n // T2)                          # (captures first when that has not happened yet: `warm`)
             else:
                 for s in range(self.done, self.done + n):
-                    if idx_d is None:
+                    if idx_d is None and self.row_rng is not None:
+                        eng.step(r=self._rows())
+                    elif idx_d is None:
                         eng.step()
                     elif algorithm == 'saga':
                         eng.step(idx_d[s + 1], r=self.rs[s])
@@ -434,6 +469,8 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
             if nt not in base.tiles:
                 base.tiles = {nt: base.batch.tile(nt)}           # (one tiled copy at a time: slabs of one size reuse it)
             self.batch = base.tiles[nt]
+            self.streams = None if base.streams is None else base.streams * nt
+            self._row_rngs()
             per_t2 = t2_trials and any('T2' in tr for tr in trials)
             per_hist = hist_trials and any('hist_size' in tr for tr in trials)
             lay = trial_layout(n, trials, {'eta': eta, 'mini_batch_size': mb, 'sigma_modifier': dkw.get('sigma_modifier', 1.0), 'T2': T2,
@@ -445,13 +482,24 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
             self.eng = E.make_engine(self.batch, make_prox(denoiser, **pkw), lay['eta'], lay['T2'] if per_t2 else T2,
                                      None if algorithm == 'gd' else lay['mini_batch_size'], lr_decay=lr_decay, variant=variant,
                                      algorithm=algorithm, hist_size=lay['hist_size'] if per_hist else hist_size,
-                                     seed=base.items[0]['id'] + 1, draw_id=lay['draw_id'], **eng_kw)
+                                     seed=base.items[0]['id'] + 1,
+                                     draw_id=lay['draw_id'] if self.streams is None else [k for _, k in self.streams], **eng_kw)
+
+    item_stream = {}                                            # mixed_scales: item id -> (seed, place) of its minibatch stream
 
     def _group_chunks(items):
         groups = {}
         for it in items:
             groups.setdefault(group_key(it), []).append(it)
-        return [g[s0:s0 + max_batch] for g in groups.values() for s0 in range(0, len(g), max_batch)]
+        chunks = [g[s0:s0 + max_batch] for g in groups.values() for s0 in range(0, len(g), max_batch)]
+        if not mixed_scales:
+            return chunks
+        item_stream.clear()                                     # (the chunks made below copy what they need)
+        for c in chunks:                                        # the default runner's batches: seed = first id + 1, id = place
+            for k, it in enumerate(c):
+                item_stream[it['id']] = (c[0]['id'] + 1, k)
+        items = list(items)
+        return [items[s0:s0 + max_batch] for s0 in range(0, len(items), max_batch)]
 
     def prepare(items):
         """Build this rank's batches (problem data resident in HBM, engines constructed): everything before the iterations."""
@@ -538,7 +586,7 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
 
     run.prepare, run.advance, run.collect, run.warm = prepare, advance, collect, warm
     run.prepare_data, run.run_trials, run.check_trials = prepare_data, run_trials, check_trials
-    run.data_key = (id(images), problem, seeding, H, W, dtype, max_batch, kernel)
+    run.data_key = (id(images), problem, seeding, H, W, dtype, max_batch, kernel, bool(mixed_scales))
     run.objective = bool(objective)
     run.names = (_REF_NAMES[problem], 'CNN' if callable(denoiser) else _REF_NAMES.get(denoiser, str(denoiser)), 'pnp_' + algorithm)
     return run
