@@ -134,7 +134,15 @@ int pnp_csmri_grad_sel(pnp_csmri_plan* plan, const void* a, const void* b, const
  * bitsT: bit-packed selector as in pnp_csmri_grad_sel (one step's row of pnp_csmri_draw_thresholds' selbits; no data
  * term: the Y terms of the SVRG difference cancel).  sigma_modifier, fallback_sigma, xrec, sse_out, sigma_out as in
  * pnp_prox_tv (the noise estimate is always made in-kernel).  denoise == 0: stop after the noise estimate and store the
- * stepped image (for a prox that is not this one).  out may alias a, c1 or c2.                              */
+ * stepped image (for a prox that is not this one).  out may alias a, c1 or c2.
+ * `int denoise` has three values here and in pnp_csmri_svrg_outer_step, pnp_csmri_sarah_step, pnp_csmri_grad_step,
+ * pnp_csmri_saga_step and their _pp forms: 0 = store the stepped image; 1 (any value but 0 and 2) = the per-column prox of
+ * pnp_prox_tv; 2 = the two-dimensional wavelet prox of pnp_prox_wavelet2d (TVDenoiser(multi=False)) inside the kernel, on the
+ * register-resident image: the same 2 x 2 Haar operations in the same order, so the coefficients are those of pnp_prox_wavelet2d
+ * bit for bit; the 15 sub-band sums of squares are taken in another order (lane, wave tree, waves 0..7), so the thresholds and
+ * the result agree with it to a few ulps, and exactly where every sum is exact.  A problem's result does not depend on the batch.
+ * The multi-step forms that carry the argument (pnp_csmri_grad_span, pnp_csmri_saga_span, pnp_csmri_saga_step_hist_pp,
+ * pnp_csmri_saga_span_hist) hold the per-column prox only: denoise == 2 is PNP_ERR_ARG there.                        */
 int pnp_csmri_svrg_step(pnp_csmri_plan* plan, const void* a, const void* b, const uint32_t* bitsT, double alpha,
                         const void* alpha_vec, double beta, const void* c1, double gamma, const void* c2, void* out,
                         int denoise, double sigma_modifier, double fallback_sigma, const void* xrec, double* sse_out,
@@ -280,6 +288,15 @@ int pnp_csmri_svrg_outer_iteration_pp(pnp_csmri_plan* plan, void* z, void* w, vo
                                       int mini_batch_size, const int32_t* mb_vec, double sigma_modifier,
                                       const double* sigma_modifier_pp, double fallback_sigma, const void* xrec, double* sse_log,
                                       int log_row0, int n_log, void* sigma_out, void* stream);
+/* pnp_csmri_svrg_outer_iteration_pp with the prox kind: denoise == 1 IS that call (the per-column prox, the same kernels, the
+ * same bits); denoise == 2 runs pnp_csmri_svrg_outer_step_pp and then T2 - 1 times pnp_csmri_svrg_step_pp with denoise = 2 (the
+ * 2-D wavelet prox inside the kernel) on every problem back to back, bit for bit the separate calls.  lr_pp, mb_vec and
+ * sigma_modifier_pp are nullable as there.  PNP_ERR_ARG: any other value of denoise; otherwise as the _pp call.          */
+int pnp_csmri_svrg_outer_iteration_prox(pnp_csmri_plan* plan, void* z, void* w, void* mu, const uint32_t* mask_bitsT,
+                                        const void* yh, const void* alpha_vec, const uint32_t* selbits, int T2, double lr,
+                                        const double* lr_pp, int mini_batch_size, const int32_t* mb_vec, double sigma_modifier,
+                                        const double* sigma_modifier_pp, double fallback_sigma, const void* xrec,
+                                        double* sse_log, int log_row0, int n_log, void* sigma_out, int denoise, void* stream);
 /* Per-problem T2: n_steps consecutive inner iterations s = step0 .. step0 + n_steps - 1 of every problem in ONE launch, with the TV
  * prox.  Problem b refreshes (mu = grad_full(z), w = z) at the steps with s % T2_b == 0, T2_b = t2_vec ? t2_vec[b] : T2 -- at its own
  * outer iterations, wherever the span starts or ends inside them (a problem with step0 % T2_b != 0 does not refresh at the span
@@ -333,9 +350,9 @@ int pnp_csmri_sarah_outer_iteration_pp(pnp_csmri_plan* plan, void* z, void* w_pr
  *   yh (GD):  bitsT [batch][W][H/32] = the mask, the same array at every step;
  *   YT (SGD): bitsT [n_steps][batch][W][H/32] = drawn selbits, slot i = the selector of step i.
  *   sse_log  [n_log][batch] double: step i writes row (log_row0 + i) % n_log;  sigma_out [batch]: the last step's estimate.
- * The kernels hold the prox: denoise must be != 0.
+ * The kernels hold the per-column prox: denoise must be != 0 and != 2 (the 2-D wavelet prox is not in the span kernels).
  * PNP_ERR_ARG before any device work: a NULL plan, z, bitsT, xrec, sse_log or sigma_out; both or neither of yh and YT;
- * n_steps <= 0; n_log < 1; log_row0 < 0; denoise == 0; a plan that is not f32 256 x 256.                              */
+ * n_steps <= 0; n_log < 1; log_row0 < 0; denoise == 0 or 2; a plan that is not f32 256 x 256.                         */
 int pnp_csmri_grad_span(pnp_csmri_plan* plan, void* z, const uint32_t* bitsT, const void* yh, const void* YT, double alpha,
                         const double* alpha_pp, const void* alpha_vec, double beta, int denoise, double sigma_modifier,
                         const double* sigma_modifier_pp, double fallback_sigma, const void* xrec, int n_steps, double* sse_log,
@@ -349,9 +366,9 @@ int pnp_csmri_grad_span(pnp_csmri_plan* plan, void* z, const uint32_t* bitsT, co
  *   prev_row0 int32 [batch]: the row the step before the span replaced.  Step i takes prev = rows[i - 1][b] (prev_row0[b] at i = 0);
  *             rows[i][b] == prev is legal.  Entries in [0, hist): the kernel cannot check them (the Python front end checks its host
  *             copy and raises);
- *   sse_log, log_row0, n_log, sigma_out as in pnp_csmri_grad_span.  denoise must be != 0.
+ *   sse_log, log_row0, n_log, sigma_out as in pnp_csmri_grad_span.  denoise must be != 0 and != 2.
  * PNP_ERR_ARG before any device work: a NULL plan, z, bitsT, YT, table, rows, prev_row0, sum, xrec, sse_log or sigma_out;
- * hist < 1; n_steps <= 0; n_log < 1; log_row0 < 0; denoise == 0; a plan that is not f32 256 x 256; table or sum overlapping z, xrec
+ * hist < 1; n_steps <= 0; n_log < 1; log_row0 < 0; denoise == 0 or 2; a plan that is not f32 256 x 256; table or sum overlapping z, xrec
  * or each other.                                                                                                     */
 int pnp_csmri_saga_span(pnp_csmri_plan* plan, void* z, const uint32_t* bitsT, const void* YT, double alpha, const double* alpha_pp,
                         const void* alpha_vec, void* table, const int32_t* rows, const int32_t* prev_row0, void* sum, double lr,
@@ -362,7 +379,8 @@ int pnp_csmri_saga_span(pnp_csmri_plan* plan, void* z, const uint32_t* bitsT, co
  * inv_hist_pp ? inv_hist_pp[b] : inv_hist ([batch] doubles on the device, 1 / hist[b], cast to float as the scalar is cast and read
  * once per workgroup).  `hist` is the row count of the table, the largest history length of the batch; problem b names rows below its
  * own history length only (row, prev_row, rows, prev_row0: the caller checks its host copy), so the rows beyond it are never touched.
- * Problem b equals, bit for bit, problem b of the plain call made with its own divisor.  Errors as the calls they extend.       */
+ * Problem b equals, bit for bit, problem b of the plain call made with its own divisor.  Errors as the calls they extend; both hold
+ * the per-column prox only: denoise == 2 is PNP_ERR_ARG (pnp_csmri_saga_step_pp takes the 2-D prox).                          */
 int pnp_csmri_saga_step_hist_pp(pnp_csmri_plan* plan, const void* z, const uint32_t* bitsT, const void* YT, double alpha,
                                 const double* alpha_pp, const void* alpha_vec, void* table, const int32_t* row,
                                 const int32_t* prev_row, void* sum, double lr, const double* lr_pp, double inv_hist,

@@ -91,6 +91,8 @@ SIGNATURES = {
     'pnp_csmri_svrg_outer_step_pp': (_i, [_vp, _vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp, _i, _d, _vp, _d, _vp, _vp, _vp, _vp]),
     'pnp_csmri_svrg_outer_iteration_pp': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _d, _vp, _i, _vp, _d, _vp, _d, _vp, _vp, _i,
                                                _i, _vp, _vp]),
+    'pnp_csmri_svrg_outer_iteration_prox': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _d, _vp, _i, _vp, _d, _vp, _d, _vp, _vp, _i,
+                                                 _i, _vp, _i, _vp]),
     'pnp_prox_tv_pp': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _d, _vp, _d, _vp, _vp, _vp, _vp]),
     'pnp_prox_wavelet2d_pp': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _d, _vp, _d, _vp, _vp, _vp, _vp]),
     'pnp_pr_shared_workspace_elems': (_sz, [_i, _i, _i]),

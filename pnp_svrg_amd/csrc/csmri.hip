@@ -337,6 +337,11 @@ int csmri_fused_outer_launch(int batch, const void* twtab, void* z, void* w, voi
                              double sigma_modifier, double fallback_sigma, const void* xrec, double* sse_log, int log_row0, int n_log,
                              void* sigma_out, void* stream, const double* lr_pp = nullptr, const int32_t* mb_vec = nullptr,
                              const double* sm_pp = nullptr);
+int csmri_fused_outer_w2d_launch(int batch, const void* twtab, void* z, void* w, void* mu, const uint32_t* mask_bits, const void* yh,
+                                 const void* alpha_vec, const uint32_t* selbits, int T2, double lr, const double* lr_pp,
+                                 int mini_batch_size, const int32_t* mb_vec, double sigma_modifier, const double* sm_pp,
+                                 double fallback_sigma, const void* xrec, double* sse_log, int log_row0, int n_log, void* sigma_out,
+                                 void* stream);
 int csmri_fused_span_launch(int batch, const void* twtab, void* z, void* w, void* mu, const uint32_t* mask_bits, const void* yh,
                             const void* alpha_vec, const uint32_t* selbits, int step0, int n_steps, int T2, const int32_t* t2_vec,
                             double lr, const double* lr_pp, int mini_batch_size, const int32_t* mb_vec, double sigma_modifier,
@@ -443,6 +448,10 @@ extern "C" int pnp_csmri_grad(pnp_csmri_plan* p, const void* a, const void* b, c
 }
 
 // ---- whole inner iteration in one kernel (csmri_fused.hip)
+// `int denoise` of the step entry points -> the kernel's MODE: 0 = store the stepped image (FUSED_NO_DENOISE), 2 = the 2-D wavelet prox
+// (FUSED_FULL_W2D), any other value = the per-column prox (FUSED_FULL)
+static inline int fused_mode(int denoise) { return denoise == 0 ? 1 : (denoise == 2 ? 3 : 0); }
+
 extern "C" int pnp_csmri_svrg_step(pnp_csmri_plan* p, const void* a, const void* b, const uint32_t* bitsT, double alpha,
                                    const void* alpha_vec, double beta, const void* c1, double gamma, const void* c2, void* out,
                                    int denoise, double sigma_modifier, double fallback_sigma, const void* xrec,
@@ -450,7 +459,7 @@ extern "C" int pnp_csmri_svrg_step(pnp_csmri_plan* p, const void* a, const void*
     PNP_CHECK_ARG(p && a && bitsT && out, "null argument");
     PNP_CHECK_ARG(p->dtype == PNP_F32 && p->H == 256 && p->W == 256, "the one-kernel iteration exists for f32 plans of 256 x 256");
     PNP_CHECK_ARG(!(sse_out && !xrec), "sse_out needs xrec");
-    return csmri_fused_launch(p->batch, p->twtab, a, b, bitsT, nullptr, alpha, alpha_vec, beta, c1, gamma, c2, out, denoise ? 0 : 1,
+    return csmri_fused_launch(p->batch, p->twtab, a, b, bitsT, nullptr, alpha, alpha_vec, beta, c1, gamma, c2, out, fused_mode(denoise),
                               sigma_modifier, fallback_sigma, xrec, sse_out, sigma_out, stream);
 }
 
@@ -462,7 +471,7 @@ extern "C" int pnp_csmri_svrg_step_pp(pnp_csmri_plan* p, const void* a, const vo
     PNP_CHECK_ARG(p && a && bitsT && out, "null argument");
     PNP_CHECK_ARG(p->dtype == PNP_F32 && p->H == 256 && p->W == 256, "the one-kernel iteration exists for f32 plans of 256 x 256");
     PNP_CHECK_ARG(!(sse_out && !xrec), "sse_out needs xrec");
-    return csmri_fused_launch(p->batch, p->twtab, a, b, bitsT, nullptr, alpha, alpha_vec, beta, c1, gamma, c2, out, denoise ? 0 : 1,
+    return csmri_fused_launch(p->batch, p->twtab, a, b, bitsT, nullptr, alpha, alpha_vec, beta, c1, gamma, c2, out, fused_mode(denoise),
                               sigma_modifier, fallback_sigma, xrec, sse_out, sigma_out, stream, nullptr, nullptr, alpha_pp, gamma_pp,
                               sigma_modifier_pp);
 }
@@ -478,7 +487,7 @@ static int sarah_step_impl(pnp_csmri_plan* p, const void* a, const void* b, cons
     PNP_CHECK_ARG(v_out != a && v_out != b && v_out != c2 && v_out != out && v_out != out2,
                   "v_out may alias c1 only (not a, b, c2, out or out2)");
     PNP_CHECK_ARG(p->dtype == PNP_F32 && p->H == 256 && p->W == 256, "the one-kernel iteration exists for f32 plans of 256 x 256");
-    return csmri_sarah_launch(p->batch, p->twtab, a, b, bitsT, alpha, alpha_vec, beta, c1, gamma, c2, v_out, out, out2, denoise ? 0 : 1,
+    return csmri_sarah_launch(p->batch, p->twtab, a, b, bitsT, alpha, alpha_vec, beta, c1, gamma, c2, v_out, out, out2, fused_mode(denoise),
                               sigma_modifier, fallback_sigma, xrec, sse_out, sigma_out, stream, alpha_pp, gamma_pp, sigma_modifier_pp);
 }
 
@@ -512,10 +521,10 @@ static int grad_step_impl(pnp_csmri_plan* p, const void* a, const uint32_t* bits
     PNP_CHECK_ARG(!(sse_out && !xrec), "sse_out needs xrec");
     if (yh != nullptr)
         return csmri_fused_launch(p->batch, p->twtab, a, nullptr, bitsT, yh, alpha, alpha_vec, beta, c1, 0.0, nullptr, out,
-                                  denoise ? 0 : 1, sigma_modifier, fallback_sigma, xrec, sse_out, sigma_out, stream, nullptr, nullptr,
+                                  fused_mode(denoise), sigma_modifier, fallback_sigma, xrec, sse_out, sigma_out, stream, nullptr, nullptr,
                                   alpha_pp, nullptr, sigma_modifier_pp);
     return csmri_minibatch_launch(p->batch, p->twtab, a, bitsT, YT, alpha, alpha_vec, beta, c1, nullptr, nullptr, nullptr, nullptr, 0.0,
-                                  0.0, out, denoise ? 0 : 1, sigma_modifier, fallback_sigma, xrec, sse_out, sigma_out, stream, alpha_pp,
+                                  0.0, out, fused_mode(denoise), sigma_modifier, fallback_sigma, xrec, sse_out, sigma_out, stream, alpha_pp,
                                   nullptr, sigma_modifier_pp);
 }
 
@@ -544,6 +553,7 @@ static int saga_step_impl(pnp_csmri_plan* p, const void* z, const uint32_t* bits
     PNP_CHECK_ARG(p->dtype == PNP_F32 && p->H == 256 && p->W == 256, "the one-kernel iteration exists for f32 plans of 256 x 256");
     PNP_CHECK_ARG(!(sse_out && !xrec), "sse_out needs xrec");
     PNP_CHECK_ARG(hist >= 1, "need hist >= 1");
+    PNP_CHECK_ARG(!(hist_form && denoise == 2), "the per-problem-divisor form holds the per-column prox only: denoise = 2 is not accepted");
     {   // table [hist][batch][H][W] and sum [batch][H][W] are written while z, out and xrec are read or written: no overlap
         const size_t img = (size_t)p->batch * 256 * 256 * sizeof(float);
         auto overlap = [](const void* x, size_t nx, const void* y, size_t ny) {
@@ -557,10 +567,10 @@ static int saga_step_impl(pnp_csmri_plan* p, const void* z, const uint32_t* bits
     }
     if (hist_form)                                              // the kernels that take the divisor per problem (NULL: the scalar)
         return csmri_saga_hist_launch(p->batch, p->twtab, z, bitsT, YT, alpha, alpha_vec, table, row, prev_row, sum, lr, inv_hist, out,
-                                      denoise ? 0 : 1, sigma_modifier, fallback_sigma, xrec, sse_out, sigma_out, stream, alpha_pp, lr_pp,
+                                      fused_mode(denoise), sigma_modifier, fallback_sigma, xrec, sse_out, sigma_out, stream, alpha_pp, lr_pp,
                                       sigma_modifier_pp, inv_hist_pp, 0, 0, 1);
     return csmri_minibatch_launch(p->batch, p->twtab, z, bitsT, YT, alpha, alpha_vec, 0.0, nullptr, table, row, prev_row, sum, lr, inv_hist,
-                                  out, denoise ? 0 : 1, sigma_modifier, fallback_sigma, xrec, sse_out, sigma_out, stream, alpha_pp, lr_pp,
+                                  out, fused_mode(denoise), sigma_modifier, fallback_sigma, xrec, sse_out, sigma_out, stream, alpha_pp, lr_pp,
                                   sigma_modifier_pp);
 }
 
@@ -602,7 +612,7 @@ extern "C" int pnp_csmri_svrg_outer_step(pnp_csmri_plan* p, const void* z, const
     PNP_CHECK_ARG(!(sse_out && !xrec), "sse_out needs xrec");
     PNP_CHECK_ARG(w_out != z && mu_out != z && w_out != mu_out && w_out != out && mu_out != out, "w_out and mu_out must be buffers of their own");
     return csmri_fused_launch(p->batch, p->twtab, z, nullptr, mask_bitsT, yh, 1.0, alpha_vec, 1.0, z, -lr, nullptr, out,
-                              denoise ? 0 : 1, sigma_modifier, fallback_sigma, xrec, sse_out, sigma_out, stream, w_out, mu_out);
+                              fused_mode(denoise), sigma_modifier, fallback_sigma, xrec, sse_out, sigma_out, stream, w_out, mu_out);
 }
 
 // ---- a whole outer iteration (refresh + T2 inner iterations, TV prox) in one launch
@@ -628,7 +638,7 @@ extern "C" int pnp_csmri_svrg_outer_step_pp(pnp_csmri_plan* p, const void* z, co
     PNP_CHECK_ARG(!(sse_out && !xrec), "sse_out needs xrec");
     PNP_CHECK_ARG(w_out != z && mu_out != z && w_out != mu_out && w_out != out && mu_out != out, "w_out and mu_out must be buffers of their own");
     return csmri_fused_launch(p->batch, p->twtab, z, nullptr, mask_bitsT, yh, 1.0, alpha_vec, 1.0, z, -lr, nullptr, out,
-                              denoise ? 0 : 1, sigma_modifier, fallback_sigma, xrec, sse_out, sigma_out, stream, w_out, mu_out, nullptr,
+                              fused_mode(denoise), sigma_modifier, fallback_sigma, xrec, sse_out, sigma_out, stream, w_out, mu_out, nullptr,
                               lr_pp, sigma_modifier_pp);
 }
 
@@ -645,6 +655,29 @@ extern "C" int pnp_csmri_svrg_outer_iteration_pp(pnp_csmri_plan* p, void* z, voi
     return csmri_fused_outer_launch(p->batch, p->twtab, z, w, mu, mask_bitsT, yh, alpha_vec, selbits, T2, lr, mini_batch_size,
                                     sigma_modifier, fallback_sigma, xrec, sse_log, log_row0, n_log, sigma_out, stream, lr_pp, mb_vec,
                                     sigma_modifier_pp);
+}
+
+// ---- pnp_csmri_svrg_outer_iteration_pp with the prox kind: denoise = 1 IS that call (the per-column prox); denoise = 2 runs the 2-D
+// wavelet prox in every iteration -- the outer step and the T2 - 1 inner steps with denoise = 2, bit for bit
+extern "C" int pnp_csmri_svrg_outer_iteration_prox(pnp_csmri_plan* p, void* z, void* w, void* mu, const uint32_t* mask_bitsT,
+                                                   const void* yh, const void* alpha_vec, const uint32_t* selbits, int T2, double lr,
+                                                   const double* lr_pp, int mini_batch_size, const int32_t* mb_vec,
+                                                   double sigma_modifier, const double* sigma_modifier_pp, double fallback_sigma,
+                                                   const void* xrec, double* sse_log, int log_row0, int n_log, void* sigma_out,
+                                                   int denoise, void* stream) {
+    PNP_CHECK_ARG(denoise == 1 || denoise == 2, "denoise must be 1 (the per-column prox) or 2 (the 2-D wavelet prox)");
+    if (denoise == 1)
+        return pnp_csmri_svrg_outer_iteration_pp(p, z, w, mu, mask_bitsT, yh, alpha_vec, selbits, T2, lr, lr_pp, mini_batch_size, mb_vec,
+                                                 sigma_modifier, sigma_modifier_pp, fallback_sigma, xrec, sse_log, log_row0, n_log,
+                                                 sigma_out, stream);
+    PNP_CHECK_ARG(p && z && w && mu && mask_bitsT && yh && alpha_vec && xrec && sse_log && sigma_out, "null argument");
+    PNP_CHECK_ARG(p->dtype == PNP_F32 && p->H == 256 && p->W == 256, "the one-kernel iteration exists for f32 plans of 256 x 256");
+    PNP_CHECK_ARG(T2 >= 1 && (T2 == 1 || selbits != nullptr) && (mb_vec != nullptr || mini_batch_size >= 1) && n_log >= 1 && log_row0 >= 0,
+                  "bad T2 / selbits / mini_batch_size / log");
+    PNP_CHECK_ARG(z != w && z != mu && w != mu, "z, w and mu must be buffers of their own");
+    return csmri_fused_outer_w2d_launch(p->batch, p->twtab, z, w, mu, mask_bitsT, yh, alpha_vec, selbits, T2, lr, lr_pp, mini_batch_size,
+                                        mb_vec, sigma_modifier, sigma_modifier_pp, fallback_sigma, xrec, sse_log, log_row0, n_log,
+                                        sigma_out, stream);
 }
 
 // ---- n_steps inner iterations in one launch, every problem refreshing by its own T2 (t2_vec: int32 [batch]; NULL = the scalar)
@@ -713,6 +746,7 @@ extern "C" int pnp_csmri_grad_span(pnp_csmri_plan* p, void* z, const uint32_t* b
     PNP_CHECK_ARG((yh != nullptr) != (YT != nullptr), "pass the packed data term (yh) or the raw data (YT), exactly one of them");
     PNP_CHECK_ARG(n_steps >= 1 && n_log >= 1 && log_row0 >= 0 && log_row0 <= INT32_MAX - n_steps, "bad n_steps / log");
     PNP_CHECK_ARG(denoise != 0, "the span kernels hold the TV prox: denoise must be != 0");
+    PNP_CHECK_ARG(denoise != 2, "the span kernels hold the per-column prox only: denoise = 2 (the 2-D wavelet prox) is not accepted");
     PNP_CHECK_ARG(p->dtype == PNP_F32 && p->H == 256 && p->W == 256, "the one-kernel iteration exists for f32 plans of 256 x 256");
     return csmri_step_span_launch(p->batch, p->twtab, z, bitsT, yh, YT, alpha, alpha_vec, beta, nullptr, nullptr, nullptr, nullptr, 0.0, 0.0,
                                   n_steps, sigma_modifier, fallback_sigma, xrec, sse_log, log_row0, n_log, sigma_out, stream, alpha_pp,
@@ -729,6 +763,7 @@ static int saga_span_impl(pnp_csmri_plan* p, void* z, const uint32_t* bitsT, con
     PNP_CHECK_ARG(hist >= 1, "need hist >= 1");
     PNP_CHECK_ARG(n_steps >= 1 && n_log >= 1 && log_row0 >= 0 && log_row0 <= INT32_MAX - n_steps, "bad n_steps / log");
     PNP_CHECK_ARG(denoise != 0, "the span kernels hold the TV prox: denoise must be != 0");
+    PNP_CHECK_ARG(denoise != 2, "the span kernels hold the per-column prox only: denoise = 2 (the 2-D wavelet prox) is not accepted");
     PNP_CHECK_ARG(p->dtype == PNP_F32 && p->H == 256 && p->W == 256, "the one-kernel iteration exists for f32 plans of 256 x 256");
     {   // as pnp_csmri_saga_step: table [hist][batch][H][W] and sum [batch][H][W] are written while z and xrec are read or written
         const size_t img = (size_t)p->batch * 256 * 256 * sizeof(float);

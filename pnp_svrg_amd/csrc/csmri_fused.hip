@@ -721,13 +721,14 @@ __device__ __forceinline__ void saga_epilogue(RImg& R, const SagaArgs& sa, const
 // coefficients are semantically significant); the FFT code above keeps the compiler's default (contraction on)
 #pragma clang fp contract(off)
 #include "prox_tv.h"
+#include "csmri_fused_w2d.h"
 
 namespace pnp {
 
 // MODE: 0 = the whole iteration; 1 = stop after the noise estimate and store the stepped image (another prox follows);
 //       2 = the gradient only (phases 1-3: grad_full with its data term, or any other use of pnp_csmri_grad_sel that fits
-//           this kernel).
-enum { FUSED_FULL = 0, FUSED_NO_DENOISE = 1, FUSED_GRAD = 2 };
+//           this kernel); 3 = the whole iteration with the 2-D wavelet prox (csmri_fused_w2d.h) in place of the per-column one.
+enum { FUSED_FULL = 0, FUSED_NO_DENOISE = 1, FUSED_GRAD = 2, FUSED_FULL_W2D = 3 };
 // the LDS a workgroup needs beside the 132 KB hand-over buffer
 struct FusedShared {
     cx<float> twl[FN];
@@ -765,7 +766,7 @@ __device__ __forceinline__ void svrg_iter_body(unsigned char* lds_raw, FusedShar
                                                const float* xri, double* __restrict__ sse_out, float* __restrict__ sigma_out,
                                                float* w_out, float* mu_out, float* v_out = nullptr, float* out2 = nullptr,
                                                const cx<float>* __restrict__ YT = nullptr, const SagaArgs* saga = nullptr) {
-    constexpr bool DENOISE = MODE == FUSED_FULL;
+    constexpr bool DENOISE = MODE == FUSED_FULL || MODE == FUSED_FULL_W2D;
     cx<float>* ldc = reinterpret_cast<cx<float>*>(lds_raw);
     float* ldf = reinterpret_cast<float*>(lds_raw);
     cx<float>* twl = sh.twl;
@@ -843,8 +844,12 @@ __device__ __forceinline__ void svrg_iter_body(unsigned char* lds_raw, FusedShar
     if (sigma_out != nullptr && t == 0) *sigma_out = sigma_est;
     if (DENOISE) {
         const float sigma = sigma_est > 0.f ? sigma_est * sigma_modifier : fallback_sigma;
-        haar_bayes_shrink<float, FN>(x[0], sigma * sigma);
-        haar_bayes_shrink<float, FN>(x[1], sigma * sigma);
+        if constexpr (MODE == FUSED_FULL_W2D) {
+            fused_wavelet2d(x, ldf, sigma * sigma, t);
+        } else {
+            haar_bayes_shrink<float, FN>(x[0], sigma * sigma);
+            haar_bayes_shrink<float, FN>(x[1], sigma * sigma);
+        }
     }
     PNP_STAMP(8);
     // C -> R per column half, then error + store piece by piece.  The ground truth of the first half is requested once the
@@ -1434,6 +1439,48 @@ __global__ __launch_bounds__(FT) void k_saga_span_hist(float* z, const uint32_t*
     }
 }
 
+// k_svrg_outer_pp with the prox kind a template parameter (pnp_csmri_svrg_outer_iteration_prox; launched as <FUSED_FULL_W2D>: the 2-D
+// wavelet prox of csmri_fused_w2d.h in every iteration).  The per-problem arrays may all be NULL; the coefficients are formed from the
+// doubles exactly as there, so each iteration is the separate call it replaces (pnp_csmri_svrg_outer_step[_pp] / pnp_csmri_svrg_step[_pp]
+// with denoise = 2), bit for bit.  A kernel of its own with instantiations of the body of its own (MODE differs), emitted behind every
+// existing kernel.
+template <int MODE>
+__global__ __launch_bounds__(FT) void k_svrg_outer_prox(float* z, float* w, float* mu, const uint32_t* __restrict__ mask_bits,
+                                                        const cx<float>* __restrict__ yh, const float* __restrict__ alpha_vec,
+                                                        const uint32_t* __restrict__ selbits, int T2, double lr, const double* __restrict__ lr_pp,
+                                                        int mini_batch_size, const int32_t* __restrict__ mb_vec,
+                                                        const cx<float>* __restrict__ twtab, float sigma_modifier,
+                                                        const double* __restrict__ sm_pp, float fallback_sigma,
+                                                        const float* __restrict__ xrec, double* __restrict__ sse_log, int log_row0, int n_log,
+                                                        float* __restrict__ sigma_out) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    __shared__ FusedShared sh;
+    const int prob = blockIdx.x;
+    if (lr_pp != nullptr) lr = lr_pp[prob];
+    if (mb_vec != nullptr) mini_batch_size = mb_vec[prob];
+    if (sm_pp != nullptr) sigma_modifier = (float)sm_pp[prob];
+    const double alpha = -lr / (double)mini_batch_size;
+    const float scale_inner = (float)(alpha * (1.0 / ((double)FN * (double)FN))), gamma = (float)(-lr);
+    const int batch = gridDim.x;
+    const size_t img = (size_t)prob * FN * FN;
+    const float inv_n = 1.0f / ((float)FN * (float)FN);
+    float* zi = z + img;
+    svrg_iter_body<MODE, true, 0>(lds_raw, sh, zi, nullptr, mask_bits + (size_t)prob * FN * 8, yh + (size_t)prob * (FN / 2) * FN, twtab,
+                                  inv_n * alpha_vec[prob], 1.0f, zi, gamma, nullptr, zi, sigma_modifier, fallback_sigma, xrec + img,
+                                  sse_log + (size_t)(log_row0 % n_log) * batch + prob, sigma_out + prob, w + img, mu + img);
+#pragma unroll 1
+    for (int j = 1; j < T2; ++j) {
+        // this iteration reads what the last one wrote (same lanes, same addresses): stores done, no stale line in the L1
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        __syncthreads();
+        svrg_iter_body<MODE, false, 2>(lds_raw, sh, zi, w + img, selbits + ((size_t)j * batch + prob) * FN * 8, nullptr, twtab,
+                                       scale_inner, 1.0f, zi, gamma, mu + img, zi, sigma_modifier,
+                                       fallback_sigma, xrec + img, sse_log + (size_t)((log_row0 + j) % n_log) * batch + prob,
+                                       sigma_out + prob, nullptr, nullptr);
+    }
+}
+
 // stagger (see startup_stagger): only launches of more than one workgroup per CU pay for it and profit from it
 static int stagger_config(int* num_cu_out, int* groups, int* units) {
     static int num_cu = 0, st_groups = 2, st_units = 40;    // same-box sweep (tools/dev/stagger_sweep.py): 0.588 ms per config-2 step without, 0.575 with (2, 40), slower from (8, 20) on
@@ -1470,6 +1517,7 @@ static int fused_lds_optin() {
         PNP_FUSED_ATTR(1, false, 0); PNP_FUSED_ATTR(1, false, 1); PNP_FUSED_ATTR(1, false, 2);
         PNP_FUSED_ATTR(2, false, 0); PNP_FUSED_ATTR(2, false, 1); PNP_FUSED_ATTR(2, false, 2);
         PNP_FUSED_ATTR(0, true, 0); PNP_FUSED_ATTR(1, true, 0);
+        PNP_FUSED_ATTR(3, false, 0); PNP_FUSED_ATTR(3, false, 1); PNP_FUSED_ATTR(3, false, 2); PNP_FUSED_ATTR(3, true, 0);
 #undef PNP_FUSED_ATTR
         PNP_CHECK_HIP(hipFuncSetAttribute((const void*)k_svrg_outer, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F_LDS_BYTES));
         PNP_CHECK_HIP(hipFuncSetAttribute((const void*)k_svrg_outer_pp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F_LDS_BYTES));
@@ -1478,6 +1526,7 @@ static int fused_lds_optin() {
         PNP_CHECK_HIP(hipFuncSetAttribute((const void*)k_grad_span<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F_LDS_BYTES));
         PNP_CHECK_HIP(hipFuncSetAttribute((const void*)k_grad_span<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F_LDS_BYTES));
         PNP_CHECK_HIP(hipFuncSetAttribute((const void*)k_saga_span, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F_LDS_BYTES));
+        PNP_CHECK_HIP(hipFuncSetAttribute((const void*)k_svrg_outer_prox<FUSED_FULL_W2D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F_LDS_BYTES));
         attr_done |= 1ull << (dev & 63);
     }
     return PNP_OK;
@@ -1507,6 +1556,21 @@ int csmri_fused_outer_launch(int batch, const void* twtab, void* z, void* w, voi
                                                                  (const cx<float>*)twtab, (float)sigma_modifier, (float)fallback_sigma,
                                                                  (const float*)xrec, sse_log, log_row0, n_log, (float*)sigma_out, num_cu,
                                                                  st_groups, 0);     // (no stagger: same-box A/B 0.539 ms per step without, 0.546 with (2, 40))
+    PNP_CHECK_LAUNCH();
+    return PNP_OK;
+}
+
+// one launch = one outer iteration with the 2-D wavelet prox (k_svrg_outer_prox<FUSED_FULL_W2D>); the per-problem arrays may be NULL
+int csmri_fused_outer_w2d_launch(int batch, const void* twtab, void* z, void* w, void* mu, const uint32_t* mask_bits, const void* yh,
+                                 const void* alpha_vec, const uint32_t* selbits, int T2, double lr, const double* lr_pp,
+                                 int mini_batch_size, const int32_t* mb_vec, double sigma_modifier, const double* sm_pp,
+                                 double fallback_sigma, const void* xrec, double* sse_log, int log_row0, int n_log, void* sigma_out,
+                                 void* stream) {
+    { const int rc = fused_lds_optin(); if (rc != PNP_OK) return rc; }
+    k_svrg_outer_prox<FUSED_FULL_W2D><<<batch, FT, F_LDS_BYTES, (hipStream_t)stream>>>(
+        (float*)z, (float*)w, (float*)mu, mask_bits, (const cx<float>*)yh, (const float*)alpha_vec, selbits, T2, lr, lr_pp, mini_batch_size,
+        mb_vec, (const cx<float>*)twtab, (float)sigma_modifier, sm_pp, (float)fallback_sigma, (const float*)xrec, sse_log, log_row0, n_log,
+        (float*)sigma_out);
     PNP_CHECK_LAUNCH();
     return PNP_OK;
 }
@@ -1571,7 +1635,7 @@ int csmri_step_span_launch(int batch, const void* twtab, void* z, const uint32_t
 }
 
 // plan internals live in csmri.hip (pnp_csmri_svrg_step / pnp_csmri_grad_sel); the kernel only needs the plan's twiddle table.
-// mode: FUSED_FULL / FUSED_NO_DENOISE / FUSED_GRAD; w_out / mu_out != NULL: the outer refresh folded in (pnp_csmri_svrg_outer_step)
+// mode: FUSED_FULL / FUSED_NO_DENOISE / FUSED_GRAD / FUSED_FULL_W2D; w_out / mu_out != NULL: the outer refresh folded in (pnp_csmri_svrg_outer_step)
 int csmri_fused_launch(int batch, const void* twtab, const void* a, const void* b, const uint32_t* bitsT, const void* yh,
                        double alpha, const void* alpha_vec, double beta, const void* c1, double gamma, const void* c2, void* out,
                        int mode, double sigma_modifier, double fallback_sigma, const void* xrec, double* sse_out, void* sigma_out,
@@ -1596,22 +1660,30 @@ int csmri_fused_launch(int batch, const void* twtab, const void* a, const void* 
 #define PNP_FUSED_LAUNCH(...)                                                                                             \
     do { if (pp) k_svrg_iter_pp<__VA_ARGS__><<<batch, FT, F_LDS_BYTES, s>>>(PNP_FUSED_ARGS, alpha_pp, gamma_pp, sm_pp);     \
          else k_svrg_iter<__VA_ARGS__><<<batch, FT, F_LDS_BYTES, s>>>(PNP_FUSED_ARGS); } while (0)
+    // the 2-D prox: ONE kernel serves the plain and the _pp entry point (as k_grad_step) -- with the three arrays NULL k_svrg_iter_pp
+    // keeps the scalars the host converted, which is the plain call
+#define PNP_FUSED_LAUNCH_W2D(...) k_svrg_iter_pp<3, __VA_ARGS__><<<batch, FT, F_LDS_BYTES, s>>>(PNP_FUSED_ARGS, alpha_pp, gamma_pp, sm_pp)
 #define PNP_FUSED_BY_NOPS(MD)                                                     \
     do { if (nops == 0) PNP_FUSED_LAUNCH(MD, false, 0); else if (nops == 1) PNP_FUSED_LAUNCH(MD, false, 1); else PNP_FUSED_LAUNCH(MD, false, 2); } while (0)
     if (outer) {                                                // the outer refresh folded into the first inner iteration
         if (mode == FUSED_FULL) PNP_FUSED_LAUNCH(0, true, 0);
+        else if (mode == FUSED_FULL_W2D) PNP_FUSED_LAUNCH_W2D(true, 0);
         else PNP_FUSED_LAUNCH(1, true, 0);
     } else if (mode == FUSED_GRAD) PNP_FUSED_BY_NOPS(2);
     else if (mode == FUSED_FULL) PNP_FUSED_BY_NOPS(0);
+    else if (mode == FUSED_FULL_W2D) {
+        if (nops == 0) PNP_FUSED_LAUNCH_W2D(false, 0); else if (nops == 1) PNP_FUSED_LAUNCH_W2D(false, 1); else PNP_FUSED_LAUNCH_W2D(false, 2);
+    }
     else PNP_FUSED_BY_NOPS(1);
 #undef PNP_FUSED_BY_NOPS
+#undef PNP_FUSED_LAUNCH_W2D
 #undef PNP_FUSED_LAUNCH
 #undef PNP_FUSED_ARGS
     PNP_CHECK_LAUNCH();
     return PNP_OK;
 }
 
-// the SARAH form (pnp_csmri_sarah_step[_pp]); mode: FUSED_FULL / FUSED_NO_DENOISE; out2 may be NULL; scale and casts as csmri_fused_launch
+// the SARAH form (pnp_csmri_sarah_step[_pp]); mode: FUSED_FULL / FUSED_NO_DENOISE / FUSED_FULL_W2D; out2 may be NULL; scale and casts as csmri_fused_launch
 int csmri_sarah_launch(int batch, const void* twtab, const void* a, const void* b, const uint32_t* bitsT, double alpha,
                        const void* alpha_vec, double beta, const void* c1, double gamma, const void* c2, void* v_out, void* out,
                        void* out2, int mode, double sigma_modifier, double fallback_sigma, const void* xrec, double* sse_out,
@@ -1630,6 +1702,7 @@ int csmri_sarah_launch(int batch, const void* twtab, const void* a, const void* 
 #define PNP_SARAH_ATTR(K, ...) PNP_CHECK_HIP(hipFuncSetAttribute((const void*)K<__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F_LDS_BYTES))
             PNP_SARAH_ATTR(k_sarah_iter, 0, false); PNP_SARAH_ATTR(k_sarah_iter, 0, true); PNP_SARAH_ATTR(k_sarah_iter, 1, false);
             PNP_SARAH_ATTR(k_sarah_iter_pp, 0, false); PNP_SARAH_ATTR(k_sarah_iter_pp, 0, true); PNP_SARAH_ATTR(k_sarah_iter_pp, 1, false);
+            PNP_SARAH_ATTR(k_sarah_iter_pp, 3, false); PNP_SARAH_ATTR(k_sarah_iter_pp, 3, true);
 #undef PNP_SARAH_ATTR
             attr_done |= 1ull << (dev & 63);
         }
@@ -1640,7 +1713,11 @@ int csmri_sarah_launch(int batch, const void* twtab, const void* a, const void* 
 #define PNP_SARAH_LAUNCH(...)                                                                                             \
     do { if (pp) k_sarah_iter_pp<__VA_ARGS__><<<batch, FT, F_LDS_BYTES, s>>>(PNP_SARAH_ARGS, alpha_pp, gamma_pp, sm_pp);    \
          else k_sarah_iter<__VA_ARGS__><<<batch, FT, F_LDS_BYTES, s>>>(PNP_SARAH_ARGS); } while (0)
-    if (mode != FUSED_FULL) PNP_SARAH_LAUNCH(1, false);
+    if (mode == FUSED_FULL_W2D) {                               // the 2-D prox: ONE kernel serves the plain and the _pp entry point
+        if (out2 != nullptr) k_sarah_iter_pp<3, true><<<batch, FT, F_LDS_BYTES, s>>>(PNP_SARAH_ARGS, alpha_pp, gamma_pp, sm_pp);
+        else k_sarah_iter_pp<3, false><<<batch, FT, F_LDS_BYTES, s>>>(PNP_SARAH_ARGS, alpha_pp, gamma_pp, sm_pp);
+    }
+    else if (mode != FUSED_FULL) PNP_SARAH_LAUNCH(1, false);
     else if (out2 != nullptr) PNP_SARAH_LAUNCH(0, true);
     else PNP_SARAH_LAUNCH(0, false);
 #undef PNP_SARAH_LAUNCH
@@ -1649,7 +1726,7 @@ int csmri_sarah_launch(int batch, const void* twtab, const void* a, const void* 
     return PNP_OK;
 }
 
-// the minibatch forms (pnp_csmri_grad_step[_pp] with YT, pnp_csmri_saga_step[_pp]); mode: FUSED_FULL / FUSED_NO_DENOISE; scale and
+// the minibatch forms (pnp_csmri_grad_step[_pp] with YT, pnp_csmri_saga_step[_pp]); mode: FUSED_FULL / FUSED_NO_DENOISE / FUSED_FULL_W2D; scale and
 // casts as csmri_fused_launch.  saga: table != NULL selects k_saga_iter (c1 and beta are then not used)
 int csmri_minibatch_launch(int batch, const void* twtab, const void* a, const uint32_t* bitsT, const void* YT, double alpha,
                            const void* alpha_vec, double beta, const void* c1, void* table, const int32_t* row, const int32_t* prev_row,
@@ -1668,6 +1745,7 @@ int csmri_minibatch_launch(int batch, const void* twtab, const void* a, const ui
         if (!((attr_done >> (dev & 63)) & 1ull)) {
 #define PNP_MB_ATTR(K, M) PNP_CHECK_HIP(hipFuncSetAttribute((const void*)K<M>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F_LDS_BYTES))
             PNP_MB_ATTR(k_grad_step, 0); PNP_MB_ATTR(k_grad_step, 1); PNP_MB_ATTR(k_saga_iter, 0); PNP_MB_ATTR(k_saga_iter, 1);
+            PNP_MB_ATTR(k_grad_step, 3); PNP_MB_ATTR(k_saga_iter, 3);
 #undef PNP_MB_ATTR
             attr_done |= 1ull << (dev & 63);
         }
@@ -1677,6 +1755,7 @@ int csmri_minibatch_launch(int batch, const void* twtab, const void* a, const ui
                       row, prev_row, (float*)sum, (float)lr, (float)inv_hist, (float*)out, (float)sigma_modifier, (float)fallback_sigma,     \
                       (const float*)xrec, sse_out, (float*)sigma_out, num_cu, st_groups, stagger_units, alpha_pp, lr_pp, sm_pp
         if (mode == FUSED_FULL) k_saga_iter<0><<<batch, FT, F_LDS_BYTES, s>>>(PNP_SAGA_ARGS);
+        else if (mode == FUSED_FULL_W2D) k_saga_iter<3><<<batch, FT, F_LDS_BYTES, s>>>(PNP_SAGA_ARGS);
         else k_saga_iter<1><<<batch, FT, F_LDS_BYTES, s>>>(PNP_SAGA_ARGS);
 #undef PNP_SAGA_ARGS
     } else {
@@ -1684,6 +1763,7 @@ int csmri_minibatch_launch(int batch, const void* twtab, const void* a, const ui
                     (const float*)c1, (float*)out, (float)sigma_modifier, (float)fallback_sigma, (const float*)xrec, sse_out,            \
                     (float*)sigma_out, num_cu, st_groups, stagger_units, alpha_pp, sm_pp
         if (mode == FUSED_FULL) k_grad_step<0><<<batch, FT, F_LDS_BYTES, s>>>(PNP_GS_ARGS);
+        else if (mode == FUSED_FULL_W2D) k_grad_step<3><<<batch, FT, F_LDS_BYTES, s>>>(PNP_GS_ARGS);
         else k_grad_step<1><<<batch, FT, F_LDS_BYTES, s>>>(PNP_GS_ARGS);
 #undef PNP_GS_ARGS
     }

@@ -187,8 +187,8 @@ class _FusedStep:
         one-kernel iteration with the prox inside it (TV, no host-side per-call state), device-drawn minibatches, no objective log
         and a constant step size (the coefficients of a launch are those of its first step)."""
         mbs = getattr(self, 'mbs', None)
-        return (self.fused and getattr(self.prox, 'fused_denoise', False) and getattr(self.prox, 'denoise_strength', 0.0) == 0.0
-                and (mbs is None or all(h is None for h in mbs.host)) and not self.log_objective and self.lr_decay == 1.0)
+        return (self.fused and getattr(self.prox, 'fused_denoise', False) and not _in_kernel_2d(self.prox)
+                and getattr(self.prox, 'denoise_strength', 0.0) == 0.0 and (mbs is None or all(h is None for h in mbs.host)) and not self.log_objective and self.lr_decay == 1.0)
 
     def _span_done(self, m):
         """The bookkeeping of m steps run inside one launch."""
@@ -200,9 +200,21 @@ class _FusedStep:
         b, px = self.b, self.prox
         sse_out = self.sse_log[self.n_prox % self.n_log]
         den = px.fused_denoise
-        call(*args, out=self.z, denoise=den, xrec=b.xrec, sse=sse_out if den else None, **kw, **px.fused_args())
+        call(*args, out=self.z, denoise=_fused_kind(px), xrec=b.xrec, sse=sse_out if den else None, **kw, **px.fused_args())
         px.after_fused(self.z, b.xrec, sse_out)
         self.n_prox += 1
+
+
+def _fused_kind(px):
+    """`denoise` of a one-kernel step for prox px: 0 = the kernel stores the stepped image (the prox follows it), 1 = the per-column
+    TV prox inside it, 2 = the 2-D wavelet prox inside it (TVProx(multi=False, in_kernel=True))."""
+    return int(getattr(px, 'fused_kind', 1)) if px.fused_denoise else 0
+
+
+def _in_kernel_2d(px):
+    """Whether px is the 2-D wavelet prox held inside the one-kernel iteration: the single-step kernels and SvrgEngine's one-launch
+    outer iteration hold it, the span kernels and the SARAH outer kernel do not."""
+    return bool(getattr(px, 'fused_denoise', False)) and getattr(px, 'fused_kind', 1) == 2
 
 
 class GdEngine(_FusedStep, LoopEngine):
@@ -473,7 +485,8 @@ class SvrgEngine(_StochEngine):
         launches of at most `span` steps -- one draw launch plus one pnp_csmri_svrg_span_pp each, in which the workgroup that owns
         a problem runs its steps back to back and refreshes where its own T2 says -- the same bits as stepping; otherwise eager
         steps."""
-        if not (self._t2_dev is not None and self.lr_decay == 1.0 and self.outer_kernel_ok()):
+        # (pnp_csmri_svrg_span_pp holds the per-column prox only: TVProx(in_kernel=True) steps eagerly here)
+        if not (self._t2_dev is not None and self.lr_decay == 1.0 and self.outer_kernel_ok() and not _in_kernel_2d(self.prox)):
             for _ in range(n):
                 self.step()
             return
@@ -517,7 +530,7 @@ class SvrgEngine(_StochEngine):
         """outer refresh (mu = grad_full(z), w = z) + inner iteration 0 in one kernel (pnp_csmri_svrg_outer_step)."""
         b, px = self.b, self.prox
         b.plan.svrg_outer_step(self.z, b.bits, b.yh_full, b.inv_m0, self._c('lr', k, lr), self.w, self.mu, out=self.z,
-                               denoise=px.fused_denoise, xrec=b.xrec, sse=sse_out if px.fused_denoise else None, **px.fused_args())
+                               denoise=_fused_kind(px), xrec=b.xrec, sse=sse_out if px.fused_denoise else None, **px.fused_args())
         px.after_fused(self.z, b.xrec, sse_out)
 
     def _fused_inner(self, j, lr, sse_out, k):
@@ -529,7 +542,7 @@ class SvrgEngine(_StochEngine):
         else:
             bits = self.mbs.selbits[j]
         b.plan.svrg_step(self.z, self.w, bits, alpha=self._c('-lr/mb', k, -lr / self.mb), beta=1.0, c1=self.z,
-                         gamma=self._c('-lr', k, -lr), c2=self.mu, out=self.z, denoise=px.fused_denoise, xrec=b.xrec, sse=sse_out if px.fused_denoise else None, **px.fused_args())
+                         gamma=self._c('-lr', k, -lr), c2=self.mu, out=self.z, denoise=_fused_kind(px), xrec=b.xrec, sse=sse_out if px.fused_denoise else None, **px.fused_args())
         px.after_fused(self.z, b.xrec, sse_out)
 
     # ---- hipGraph form: one OUTER iteration (full-gradient refresh + T2 inner iterations) = one graph launch
@@ -601,7 +614,8 @@ class SvrgEngine(_StochEngine):
                 b.draw(self.mbs, self._mb_draw, self.seed, self.s, self.T2, **self._draw_kw)
                 lr = self.eta * self.lr_decay ** (self.s // self.T2)
                 b.plan.svrg_outer_iteration(self.z, self.w, self.mu, b.bits, b.yh_full, b.inv_m0, self.mbs.selbits, self.T2,
-                                            self._c('lr', self.s // self.T2, lr), self._mb_draw, b.xrec, self.sse_log, self.n_prox % self.n_log, px.sig, sigma_modifier=px.sigma_modifier)
+                                            self._c('lr', self.s // self.T2, lr), self._mb_draw, b.xrec, self.sse_log, self.n_prox % self.n_log, px.sig, sigma_modifier=px.sigma_modifier,
+                                            prox_kind=_fused_kind(px))
                 self.s += self.T2
                 self.n_prox += self.T2
                 px.t += self.T2
@@ -717,7 +731,7 @@ class SarahEngine(_StochEngine):
         out = w_next); z is not touched (the outer step is logged, never adopted), and eta does not decay here (F6)."""
         b, px = self.b, self.prox
         b.plan.svrg_outer_step(self.z, b.bits, b.yh_full, b.inv_m0, self._c('eta', 0, self.eta), self.w_prev, self.v_prev,
-                               out=self.w_next, denoise=px.fused_denoise, xrec=b.xrec, sse=sse_out if px.fused_denoise else None,
+                               out=self.w_next, denoise=_fused_kind(px), xrec=b.xrec, sse=sse_out if px.fused_denoise else None,
                                **px.fused_args())
         px.after_fused(self.w_next, b.xrec, sse_out)
 
@@ -733,7 +747,7 @@ class SarahEngine(_StochEngine):
         den = px.fused_denoise
         b.plan.sarah_step(self.w_next, self.w_prev, bits, alpha=self._c('1/mb', 0, 1.0 / self.mb), beta=1.0, c1=self.v_prev,
                           gamma=self._c('-lr', k, -lr), c2=self.z, v_out=self.v_prev, out=self.z, out2=self.w_prev if den else None,
-                          denoise=den, xrec=b.xrec, sse=sse_out if den else None, **px.fused_args())
+                          denoise=_fused_kind(px), xrec=b.xrec, sse=sse_out if den else None, **px.fused_args())
         if not den:
             px.after_fused(self.z, b.xrec, sse_out)
             self.w_prev.copy_(self.z)
@@ -788,6 +802,8 @@ class SarahEngine(_StochEngine):
             missing.append('fused=True')
         if not getattr(self.prox, 'fused_denoise', False):
             missing.append(f'a prox that runs inside the kernel: TVProx (got {type(self.prox).__name__})')
+        elif _in_kernel_2d(self.prox):
+            missing.append('the per-column TV prox (pnp_csmri_sarah_outer_iteration does not hold the 2-D prox of in_kernel=True)')
         elif getattr(self.prox, 'denoise_strength', 0.0) != 0.0:
             missing.append('denoise_strength == 0')
         if not all(h is None for h in self.mbs.host):
@@ -865,6 +881,9 @@ class SagaEngine(_FusedStep, _StochEngine):
         hv = None
         if np.ndim(hist_size) != 0:                             # per-problem hist_size: checked on the host (the kernels cannot)
             hv = np.asarray(hist_size)
+            if self.fused and _in_kernel_2d(prox):
+                raise ValueError('SagaEngine(fused=True) with a per-problem hist_size: pnp_csmri_saga_step_hist_pp holds the per-column '
+                                 'prox only -- use TVProx(multi=False) without in_kernel=True (the 2-D prox then follows the kernel)')
             if not batch.per_problem:
                 raise ValueError(f'per-problem hist_size needs a batch that takes per-problem values (got {batch.kind!r})')
             if hv.shape != (batch.B,) or not np.issubdtype(hv.dtype, np.integer):

@@ -28,6 +28,12 @@ def _p(t):
     return ctypes.c_void_p(t.data_ptr())
 
 
+def _dn(denoise):
+    """`int denoise` of the one-kernel step entry points: 0 = store the stepped image, 1 = the per-column prox, 2 = the 2-D wavelet
+    prox inside the kernel (True / False keep their meaning: 1 / 0)."""
+    return 2 if (denoise is not True and denoise == 2) else (1 if denoise else 0)
+
+
 class _PP(tuple):
     """(scalar, device array or None): a hyper-parameter marked as per-problem capable in an argument list for `_route`."""
     __slots__ = ()
@@ -240,7 +246,7 @@ class CsmriPlan:
         out = out if out is not None else torch.empty_like(a)
         sigma_out = sigma_out if sigma_out is not None else torch.empty(self.B, dtype=a.dtype, device=a.device)
         _route('pnp_csmri_svrg_step', [self._h, _p(a), _p(b), _p(bits), _pp(alpha, self.B), _p(alpha_vec), float(beta), _p(c1),
-                                       _pp(gamma, self.B), _p(c2), _p(out), 1 if denoise else 0, _pp(sigma_modifier, self.B),
+                                       _pp(gamma, self.B), _p(c2), _p(out), _dn(denoise), _pp(sigma_modifier, self.B),
                                        float(fallback_sigma), _p(xrec), _p(sse), _p(sigma_out), _stream()])
         return out, sse, sigma_out
 
@@ -265,7 +271,7 @@ class CsmriPlan:
             raise ValueError('sarah_step: v_out may alias c1 only (not a, b, c2, out or out2)')
         sigma_out = sigma_out if sigma_out is not None else torch.empty(self.B, dtype=a.dtype, device=a.device)
         _route('pnp_csmri_sarah_step', [self._h, _p(a), _p(b), _p(bits), _pp(alpha, self.B), _p(alpha_vec), float(beta), _p(c1),
-                                        _pp(gamma, self.B), _p(c2), _p(v_out), _p(out), _p(out2), 1 if denoise else 0,
+                                        _pp(gamma, self.B), _p(c2), _p(v_out), _p(out), _p(out2), _dn(denoise),
                                         _pp(sigma_modifier, self.B), float(fallback_sigma), _p(xrec), _p(sse), _p(sigma_out),
                                         _stream()])
         return out, sse, sigma_out, v_out
@@ -293,7 +299,7 @@ class CsmriPlan:
         out = out if out is not None else torch.empty_like(a)
         sigma_out = sigma_out if sigma_out is not None else torch.empty(self.B, dtype=a.dtype, device=a.device)
         _route('pnp_csmri_grad_step', [self._h, _p(a), _p(bits), _p(yh), _p(YT), _pp(alpha, self.B), _p(alpha_vec), float(beta), _p(c1),
-                                       _p(out), 1 if denoise else 0, _pp(sigma_modifier, self.B), float(fallback_sigma), _p(xrec),
+                                       _p(out), _dn(denoise), _pp(sigma_modifier, self.B), float(fallback_sigma), _p(xrec),
                                        _p(sse), _p(sigma_out), _stream()])
         return out, sse, sigma_out
 
@@ -318,12 +324,12 @@ class CsmriPlan:
             a, l, sm, ih = _pp(alpha, self.B), _pp(lr, self.B), _pp(sigma_modifier, self.B), _pp(inv_hist_pp, self.B)
             assert ih[1] is not None, 'inv_hist_pp: a [B] float64 device tensor'
             N.call('pnp_csmri_saga_step_hist_pp', self._h, _p(z), _p(bits), _p(YT), a[0], _p(a[1]), _p(alpha_vec), _p(table), _p(row),
-                   _p(prev_row), _p(tsum), l[0], _p(l[1]), float(inv_hist), _p(ih[1]), int(table.shape[0]), _p(out), 1 if denoise else 0,
+                   _p(prev_row), _p(tsum), l[0], _p(l[1]), float(inv_hist), _p(ih[1]), int(table.shape[0]), _p(out), _dn(denoise),
                    sm[0], _p(sm[1]), float(fallback_sigma), _p(xrec), _p(sse), _p(sigma_out), _stream())
             return out, sse, sigma_out
         _route('pnp_csmri_saga_step', [self._h, _p(z), _p(bits), _p(YT), _pp(alpha, self.B), _p(alpha_vec), _p(table), _p(row),
                                        _p(prev_row), _p(tsum), _pp(lr, self.B), float(inv_hist), int(table.shape[0]), _p(out),
-                                       1 if denoise else 0, _pp(sigma_modifier, self.B), float(fallback_sigma), _p(xrec), _p(sse),
+                                       _dn(denoise), _pp(sigma_modifier, self.B), float(fallback_sigma), _p(xrec), _p(sse),
                                        _p(sigma_out), _stream()])
         return out, sse, sigma_out
 
@@ -338,18 +344,28 @@ class CsmriPlan:
         out = out if out is not None else torch.empty_like(z)
         sigma_out = sigma_out if sigma_out is not None else torch.empty(self.B, dtype=z.dtype, device=z.device)
         _route('pnp_csmri_svrg_outer_step', [self._h, _p(z), _p(mask_bits), _p(yh), _p(alpha_vec), _pp(lr, self.B), _p(w_out),
-                                             _p(mu_out), _p(out), 1 if denoise else 0, _pp(sigma_modifier, self.B),
+                                             _p(mu_out), _p(out), _dn(denoise), _pp(sigma_modifier, self.B),
                                              float(fallback_sigma), _p(xrec), _p(sse), _p(sigma_out), _stream()])
         return out, sse, sigma_out
 
     def svrg_outer_iteration(self, z, w, mu, mask_bits, yh, alpha_vec, selbits, T2, lr, mini_batch_size, xrec, sse_log, log_row0,
-                             sigma_out, *, sigma_modifier=1.0, fallback_sigma=0.0):
-        """pnp_csmri_svrg_outer_iteration: refresh + T2 inner iterations with the TV prox in ONE launch (z in place; w, mu out)."""
+                             sigma_out, *, sigma_modifier=1.0, fallback_sigma=0.0, prox_kind=1):
+        """pnp_csmri_svrg_outer_iteration: refresh + T2 inner iterations with the TV prox in ONE launch (z in place; w, mu out).
+        prox_kind: 1 = the per-column prox (the calls above, unchanged); 2 = the 2-D wavelet prox inside the kernel
+        (pnp_csmri_svrg_outer_iteration_prox)."""
+        if prox_kind not in (1, 2):
+            raise ValueError(f'svrg_outer_iteration: prox_kind must be 1 (per-column) or 2 (2-D wavelet), not {prox_kind!r}')
         assert self.dtype == torch.float32 and self.H == 256 and self.W == 256
         for t in (z, w, mu, xrec):
             assert t.dtype == self.dtype and t.numel() == self.B * self.H * self.W
         assert selbits.dtype == torch.int32 and tuple(selbits.shape) == (T2, self.B, self.W, self.H // 32)
         assert sse_log.dtype == torch.float64 and sse_log.dim() == 2 and sse_log.shape[1] == self.B and sse_log.is_contiguous()
+        if prox_kind == 2:                                      # (scalar, array or NULL) pairs: the entry point has the _pp form only
+            l, mb, sm = _pp(lr, self.B), _pp(mini_batch_size, self.B, torch.int32), _pp(sigma_modifier, self.B)
+            N.call('pnp_csmri_svrg_outer_iteration_prox', self._h, _p(z), _p(w), _p(mu), _p(mask_bits), _p(yh), _p(alpha_vec), _p(selbits),
+                   int(T2), l[0], _p(l[1]), mb[0], _p(mb[1]), sm[0], _p(sm[1]), float(fallback_sigma), _p(xrec), _p(sse_log),
+                   int(log_row0), int(sse_log.shape[0]), _p(sigma_out), 2, _stream())
+            return
         _route('pnp_csmri_svrg_outer_iteration',
                [self._h, _p(z), _p(w), _p(mu), _p(mask_bits), _p(yh), _p(alpha_vec), _p(selbits), int(T2), _pp(lr, self.B),
                 _pp(mini_batch_size, self.B, torch.int32), _pp(sigma_modifier, self.B), float(fallback_sigma), _p(xrec), _p(sse_log),

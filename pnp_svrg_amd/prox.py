@@ -14,12 +14,20 @@ class TVProx:
     """denoisers/TV.py semantics for the engines (fused estimate_sigma + BayesShrink + error sum).
     multi=True: the per-column 1-D prox (pnp_prox_tv), which the one-kernel iteration holds inside the gradient kernel.
     multi=False: the 2-D wavelet prox (pnp_prox_wavelet2d): a kernel of its own after the gradient kernel, which in the
-    one-kernel iteration makes step + noise estimate (the DnCNNProx pattern) -- the engine then steps per iteration."""
+    one-kernel iteration makes step + noise estimate (the DnCNNProx pattern) -- the engine then steps per iteration.
+    multi=False, in_kernel=True (opt-in): the one-kernel iteration holds the 2-D prox as well (`denoise = 2` of the step entry
+    points, pnp_csmri_svrg_outer_iteration_prox): one launch per step, SvrgEngine's one-launch outer iteration.  Its 15 sub-band
+    sums are taken in another order than pnp_prox_wavelet2d's, so the two forms agree to a few ulps of the thresholds, not bit
+    for bit; outside the one-kernel iteration (fused=False engines) the prox is pnp_prox_wavelet2d as before."""
 
-    def __init__(self, sigma_modifier=1.0, decay=1.0, denoise_strength=0.0, multi=True):
+    def __init__(self, sigma_modifier=1.0, decay=1.0, denoise_strength=0.0, multi=True, in_kernel=False):
+        if in_kernel and multi:
+            raise ValueError('TVProx(in_kernel=True) selects the in-kernel form of the 2-D prox: it needs multi=False '
+                             '(the per-column prox, multi=True, always runs inside the one-kernel iteration)')
         self.sigma_modifier, self.decay, self.denoise_strength, self.t = sigma_modifier, decay, denoise_strength, 0
-        self.multi = multi
-        self.fused_denoise = bool(multi)                        # one-kernel iteration: only the 1-D prox runs inside it
+        self.multi, self.in_kernel = multi, bool(in_kernel)
+        self.fused_denoise = bool(multi) or self.in_kernel      # one-kernel iteration: does the prox run inside it
+        self.fused_kind = 2 if self.in_kernel else 1            # ... and which: `int denoise` of the step entry points
 
     def bind(self, batch):
         self.sig = torch.empty(batch.B, dtype=batch.dtype, device=batch.xrec.device)
@@ -41,13 +49,13 @@ class TVProx:
     # one-kernel iteration (pnp_csmri_svrg_step): the 1-D prox runs inside the gradient kernel (fused_denoise); for the
     # 2-D prox that kernel stops after the noise estimate and after_fused shrinks with it
     def fused_args(self):
-        if not self.multi:
+        if not self.fused_denoise:
             return dict(sigma_out=self.sig)
         self.t += 1
         return dict(sigma_modifier=self.sigma_modifier, fallback_sigma=self.denoise_strength * self.decay ** self.t, sigma_out=self.sig)
 
     def after_fused(self, z, xrec, sse_out):
-        if not self.multi:
+        if not self.fused_denoise:
             self.t += 1
             ops.prox_wavelet2d(z, sigma_in=self.sig, sigma_modifier=self.sigma_modifier,
                                fallback_sigma=self.denoise_strength * self.decay ** self.t, xrec=xrec, out=z, sse=sse_out,

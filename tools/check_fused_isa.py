@@ -22,6 +22,9 @@ this script verifies on the ISA of every k_svrg_iter instantiation that
                                                           k_saga_span -- each serves its plain and its _pp entry point), both rules
     python tools/check_fused_isa.py --hist [listing.s]    the SAGA forms with a per-problem divisor instead (k_saga_iter_hist: denoise on
                                                           and off, k_saga_span_hist), both rules
+    python tools/check_fused_isa.py --w2d [listing.s]     the instantiations that hold the 2-D wavelet prox instead (MODE = 3 of
+                                                          k_svrg_iter_pp, k_sarah_iter_pp, k_grad_step, k_saga_iter -- each serves its
+                                                          plain and its _pp entry point -- and k_svrg_outer_prox), both rules
 
 Also prints, per kernel, the spill traffic between workgroup barriers (where the register pressure bites)."""
 import re
@@ -47,7 +50,7 @@ def regs_of(text):
     return out
 
 
-def kernels(txt, pp=False, sarah=False, steps=False, spans=False, hist=False):
+def kernels(txt, pp=False, sarah=False, steps=False, spans=False, hist=False, w2d=False):
     """(name, body) of every k_svrg_iter instantiation and of k_svrg_outer; pp: also k_svrg_outer_pp and k_svrg_span_pp;
     sarah: the k_sarah_iter and k_sarah_iter_pp instantiations instead; steps: the k_grad_step and k_saga_iter instantiations instead;
     spans: k_sarah_outer, the k_grad_span instantiations and k_saga_span instead; hist: the k_saga_iter_hist instantiations and
@@ -61,11 +64,15 @@ def kernels(txt, pp=False, sarah=False, steps=False, spans=False, hist=False):
         names = ('_ZN3pnp13k_sarah_outer', '_ZN3pnp11k_grad_span', '_ZN3pnp11k_saga_span')
     if hist:
         names = ('_ZN3pnp16k_saga_iter_hist', '_ZN3pnp16k_saga_span_hist')
+    if w2d:
+        names = ('_ZN3pnp14k_svrg_iter_ppILi3E', '_ZN3pnp15k_sarah_iter_ppILi3E', '_ZN3pnp11k_grad_stepILi3E', '_ZN3pnp11k_saga_iterILi3E',
+                 '_ZN3pnp17k_svrg_outer_prox')
     lines = txt.split('\n')
     i = 0
     while i < len(lines):
         l = lines[i]
-        if l.startswith(names) and l.split(';')[0].rstrip().endswith(':'):
+        # (MODE = 3, the 2-D wavelet prox, is --w2d's: the other selections keep the kernels they had)
+        if l.startswith(names) and l.split(';')[0].rstrip().endswith(':') and (w2d or not re.match(r'_ZN3pnp\d+k_(svrg_iter|svrg_iter_pp|sarah_iter|sarah_iter_pp|grad_step|saga_iter)ILi3E', l)):
             name = l.split(':')[0]
             body = []
             i += 1
@@ -182,16 +189,17 @@ def main():
     steps = '--steps' in args                                   # the minibatch forms instead, with the store rule
     spans = '--spans' in args                                   # the one-launch forms instead, with the store rule
     hist = '--hist' in args                                     # the per-problem-divisor SAGA forms instead, with the store rule
+    w2d = '--w2d' in args                                       # the instantiations with the 2-D wavelet prox instead, with the store rule
     paths = [a for a in args if not a.startswith('-')]
     txt = listing(paths[0] if paths else None, defines)
     bad = []
     nk = 0
-    for name, body in kernels(txt, pp, sarah, steps, spans, hist):
+    for name, body in kernels(txt, pp, sarah, steps, spans, hist, w2d):
         nk += 1
         errors, n_loads, n_waits, segs = check(name, body)
         spill = ' '.join(f'{i}:{s["sst"]}/{s["sld"]}' for i, s in enumerate(segs) if s['sst'] or s['sld'])
         stores = ''
-        if sarah or steps or spans or hist:
+        if sarah or steps or spans or hist or w2d:
             st_errors, n_st = check_stores(name, body)
             errors = errors + st_errors
             stores = f'{n_st} hand-issued stores, '
