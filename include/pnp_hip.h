@@ -407,7 +407,9 @@ int pnp_prox_wavelet2d_pp(const void* z_in, void* z_out, int H, int W, int batch
  * (pylops Bilinear semantics; its adjoint as a deterministic CSR gather).  H*W in {64^2, 128^2, 256^2}.
  * Plan-creation arrays are HOST pointers: Bk [H*W] blur kernel (DeblurSR.py:93, already / N, `dtype`);
  * for scale_percent == 100 pass M = H*W and NULL operators; else g_idx/g_w [M][4] (forward taps) and
- * a_rowptr [H*W+1], a_col/a_val [nnz] (CSR of the adjoint).                                       */
+ * a_rowptr [H*W+1], a_col/a_val [nnz] (CSR of the adjoint: the transpose of the taps entry for entry,
+ * nnz = 4 * M).  PNP_ERR_ARG before any allocation or device work: g_idx outside [0, H*W), a_rowptr that
+ * does not start at 0, decreases or does not end at 4 * M, a_col outside [0, M).                  */
 typedef struct pnp_deblur_plan pnp_deblur_plan;
 int pnp_deblur_plan_create(pnp_deblur_plan** plan, int H, int W, int batch, int dtype, const void* Bk, int M,
                            const int32_t* g_idx, const void* g_w, const int32_t* a_rowptr,

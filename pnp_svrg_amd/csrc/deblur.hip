@@ -280,6 +280,15 @@ extern "C" int pnp_deblur_plan_create(pnp_deblur_plan** out, int H, int W, int b
     PNP_CHECK_ARG(dtype == PNP_F32 || dtype == PNP_F64, "bad dtype");
     PNP_CHECK_ARG(batch >= 1 && M >= 1 && M <= N, "bad batch / M");
     PNP_CHECK_ARG(g_idx == nullptr || (g_w && a_rowptr && a_col && a_val), "bilinear operator needs all five arrays");
+    if (g_idx != nullptr) {
+        // the tables k_gather4 / k_csr index with, checked here because the kernels do not (as pnp_deblur_plan_create_mixed
+        // checks its sets).  The CSR is the transpose of the M rows of 4 taps, entry for entry: 4 * M entries, which is
+        // the count a_col and a_val are read to.
+        for (long long i = 0; i < (long long)M * 4; ++i) PNP_CHECK_ARG(g_idx[i] >= 0 && g_idx[i] < N, "g_idx outside [0, H*W)");
+        PNP_CHECK_ARG(a_rowptr[0] == 0 && a_rowptr[N] == (long long)M * 4, "a_rowptr must run from 0 to 4 * M, the number of taps");
+        for (int n = 0; n < N; ++n) PNP_CHECK_ARG(a_rowptr[n] <= a_rowptr[n + 1], "a_rowptr must not decrease");
+        for (long long e = 0; e < (long long)M * 4; ++e) PNP_CHECK_ARG(a_col[e] >= 0 && a_col[e] < M, "a_col outside [0, M)");
+    }
     auto* p = new pnp_deblur_plan{};
     p->N = N; p->n = N == 65536 ? 256 : N == 16384 ? 128 : 64; p->NL = N == 65536 ? 16 : N == 16384 ? 12 : 8; p->batch = batch; p->dtype = dtype; p->M = M;
     const size_t rs = dtype == PNP_F32 ? 4 : 8, cs = 2 * rs;
