@@ -315,6 +315,31 @@ int pnp_csmri_svrg_span_pp(pnp_csmri_plan* plan, void* z, void* w, void* mu, con
                            double lr, const double* lr_pp, int mini_batch_size, const int32_t* mb_vec, double sigma_modifier,
                            const double* sigma_modifier_pp, double fallback_sigma, const void* xrec, double* sse_log,
                            int log_row0, int n_log, void* sigma_out, void* stream);
+/* Per-problem T2 for the SARAH loop: n_steps consecutive inner iterations s = step0 .. step0 + n_steps - 1 of every problem in ONE
+ * launch, with the TV prox.  Problem b takes its outer step (w_prev = z, v_prev = grad_full(z), w_next = prox_TV(z - eta * v_prev); z
+ * not written, eta without decay) at the steps with s % T2_b == 0, T2_b = t2_vec ? t2_vec[b] : T2 -- at its own outer iterations,
+ * wherever the span starts or ends inside them (a problem with step0 % T2_b != 0 takes none at the span start).  At such a step the
+ * workgroup that owns b runs pnp_csmri_svrg_outer_step (out = w_next, w_out = w_prev, mu_out = v_prev) and then, as at every other
+ * step, pnp_csmri_sarah_step (a = w_next, b = w_prev, c1 = v_prev, c2 = z, alpha = 1 / mini_batch_size, beta = 1, gamma = -lr, v_out =
+ * v_prev, out = z, out2 = w_prev), back to back; the results are bit for bit those of the separate calls.  The span form is for a
+ * constant step size: the host passes lr = eta (lr_pp = eta_pp).  eta_pp, lr_pp, mb_vec, sigma_modifier_pp: as
+ * pnp_csmri_sarah_outer_iteration_pp.
+ *   t2_vec    int32 [batch], nullable; entries must be >= 1 (the Python front end checks its host copy and raises; an entry below 1
+ *             that reaches the kernel counts as 1);
+ *   selbits   [n_steps][batch][W][H/32]: slot i = the selector of step step0 + i (drawn with the absolute step id); the slot of a
+ *             step with an outer step IS read (the outer step is no inner iteration);
+ *   sse_log   [n_log][batch] double: inner iteration s writes row (log_row0 + s - step0) % n_log;
+ *   outer_log [n_log][batch] double, a ring of its own: the same row gets the squared error of the outer prox problem b made at step
+ *             s, NaN where it made none (written by the device: a wrapping ring needs no host fill).
+ * PNP_ERR_ARG before any device work: a NULL pointer (t2_vec and the _pp arrays excepted), n_steps <= 0, step0 < 0, T2 <= 0 with a
+ * NULL t2_vec, mini_batch_size <= 0 with a NULL mb_vec, n_log < 1, log_row0 < 0, a plan that is not f32 256 x 256, z, w_prev, w_next,
+ * v_prev not four distinct buffers, sse_log == outer_log.                                                               */
+int pnp_csmri_sarah_span_pp(pnp_csmri_plan* plan, void* z, void* w_prev, void* w_next, void* v_prev, const uint32_t* mask_bitsT,
+                            const void* yh, const void* alpha_vec, const uint32_t* selbits, int step0, int n_steps, int T2,
+                            const int32_t* t2_vec, double eta, const double* eta_pp, double lr, const double* lr_pp,
+                            int mini_batch_size, const int32_t* mb_vec, double sigma_modifier, const double* sigma_modifier_pp,
+                            double fallback_sigma, const void* xrec, double* sse_log, double* outer_log, int log_row0, int n_log,
+                            void* sigma_out, void* stream);
 /* A whole OUTER iteration of the SARAH loop with the TV prox -- algorithms/pnp_sarah.py:28-104 for T2 inner iterations -- in ONE
  * launch: the workgroup that owns a problem runs the outer step, pnp_csmri_svrg_outer_step (w_out = w_prev, mu_out = v_prev,
  * out = w_next, lr = eta: w_prev = z, v_prev = grad_full(z), w_next = prox_TV(z - eta * v_prev); z is NOT written and eta does not
@@ -747,6 +772,18 @@ int pnp_axpbypcz_pp(double a, const double* a_pp, const void* x, double b, const
  * aliasing mu (or w aliasing any of the other three, or z aliasing mu).                                                    */
 int pnp_refresh_pp(const void* mu_new, const void* z, void* mu, void* w, const int32_t* t2_vec, int step, size_t n, int batch,
                    int dtype, void* stream);
+
+/* The outer step of the SARAH loop -- algorithms/pnp_sarah.py:40-50 -- where every problem has a T2 of its own, ONE launch for a batch
+ * of any kind: the engine makes the outer step for the whole batch into a scratch, and for every problem p with
+ * step % t2_vec[p] == 0 this call adopts it: dst[p] = src[p], row_out[p] = row_in[p] (the squared error of that prox).  For every other
+ * problem dst[p] is neither read nor written and row_out[p] = NaN ("no outer step here": the device writes it, so a wrapping log ring
+ * needs no host fill).  row_in and row_out: double [batch], both or neither NULL.  n = total element count, problem p owns
+ * [p * n / batch, (p + 1) * n / batch); t2_vec: int32 [batch] on the device (entries >= 1: the front end checks its host copy; an
+ * entry below 1 counts as 1); step: the host's step index.  16 bytes per lane when src and dst are 16-byte aligned and n / batch
+ * elements are a multiple of 16 bytes, else element by element.  PNP_ERR_ARG before any device work: NULL src, dst or t2_vec, only
+ * one of row_in / row_out NULL, batch <= 0, n % batch != 0, an unknown dtype, step < 0, dst aliasing src.                  */
+int pnp_select_pp(const void* src, void* dst, const double* row_in, double* row_out, const int32_t* t2_vec, int step, size_t n,
+                  int batch, int dtype, void* stream);
 
 /* ------------------------------------------------------------------ the data-fidelity objective f(z), per problem
  * f = || Y - forward_model(z) ||^2 / 2 / M (problems/CSMRI.py:61-64 with M = N, DeblurSR.py:114-117 with M = lrH * lrW, PR.py:70-73

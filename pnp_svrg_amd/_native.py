@@ -107,6 +107,11 @@ SIGNATURES = {
     'pnp_csmri_svrg_span_pp': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _d, _vp, _i, _vp, _d, _vp, _d, _vp, _vp, _i,
                                     _i, _vp, _vp]),
     'pnp_refresh_pp': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _sz, _i, _i, _vp]),
+    # per-problem T2 for pnp_sarah: a span of inner iterations with the outer steps where a problem's T2 puts them, and
+    # the adoption of a whole-batch outer step by the problems that take it (the streaming and per-step paths)
+    'pnp_csmri_sarah_span_pp': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _d, _vp, _d, _vp, _i, _vp, _d, _vp, _d,
+                                     _vp, _vp, _vp, _i, _i, _vp, _vp]),
+    'pnp_select_pp': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _sz, _i, _i, _vp]),
     # one launch per SARAH outer iteration; n-step spans of the GD / SGD / SAGA inner iteration
     'pnp_csmri_sarah_outer_iteration': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _d, _d, _i, _d, _d, _vp, _vp, _i, _i, _vp,
                                              _vp]),

@@ -356,6 +356,11 @@ int csmri_sarah_outer_launch(int batch, const void* twtab, void* z, void* w_prev
                              double lr, const double* lr_pp, int mini_batch_size, const int32_t* mb_vec, double sigma_modifier,
                              const double* sm_pp, double fallback_sigma, const void* xrec, double* sse_log, int log_row0, int n_log,
                              void* sigma_out, void* stream);
+int csmri_sarah_span_launch(int batch, const void* twtab, void* z, void* w_prev, void* w_next, void* v_prev, const uint32_t* mask_bits,
+                            const void* yh, const void* alpha_vec, const uint32_t* selbits, int step0, int n_steps, int T2,
+                            const int32_t* t2_vec, double eta, const double* eta_pp, double lr, const double* lr_pp, int mini_batch_size,
+                            const int32_t* mb_vec, double sigma_modifier, const double* sm_pp, double fallback_sigma, const void* xrec,
+                            double* sse_log, double* outer_log, int log_row0, int n_log, void* sigma_out, void* stream);
 int csmri_step_span_launch(int batch, const void* twtab, void* z, const uint32_t* bits, const void* yh, const void* YT, double alpha,
                            const void* alpha_vec, double beta, void* table, const int32_t* rows, const int32_t* prev_row0, void* sum,
                            double lr, double inv_hist, int n_steps, double sigma_modifier, double fallback_sigma, const void* xrec,
@@ -735,6 +740,29 @@ extern "C" int pnp_csmri_sarah_outer_iteration_pp(pnp_csmri_plan* p, void* z, vo
                                                   double* sse_log, int log_row0, int n_log, void* sigma_out, void* stream) {
     return sarah_outer_impl(p, z, w_prev, w_next, v_prev, mask_bitsT, yh, alpha_vec, selbits, T2, eta, eta_pp, lr, lr_pp, mini_batch_size,
                             mb_vec, sigma_modifier, sigma_modifier_pp, fallback_sigma, xrec, sse_log, log_row0, n_log, sigma_out, stream);
+}
+
+// ---- n_steps SARAH inner iterations in one launch, every problem taking its outer step by its own T2 (t2_vec: int32 [batch]; NULL =
+// the scalar); the outer steps' squared errors go to a ring of their own, NaN where a problem took none
+extern "C" int pnp_csmri_sarah_span_pp(pnp_csmri_plan* p, void* z, void* w_prev, void* w_next, void* v_prev, const uint32_t* mask_bitsT,
+                                       const void* yh, const void* alpha_vec, const uint32_t* selbits, int step0, int n_steps, int T2,
+                                       const int32_t* t2_vec, double eta, const double* eta_pp, double lr, const double* lr_pp,
+                                       int mini_batch_size, const int32_t* mb_vec, double sigma_modifier,
+                                       const double* sigma_modifier_pp, double fallback_sigma, const void* xrec, double* sse_log,
+                                       double* outer_log, int log_row0, int n_log, void* sigma_out, void* stream) {
+    PNP_CHECK_ARG(p && z && w_prev && w_next && v_prev && mask_bitsT && yh && alpha_vec && selbits && xrec && sse_log && outer_log &&
+                  sigma_out, "null argument");
+    PNP_CHECK_ARG(n_steps >= 1 && step0 >= 0 && step0 <= INT32_MAX - n_steps, "bad step0 / n_steps");
+    PNP_CHECK_ARG(t2_vec != nullptr || T2 >= 1, "bad T2: a scalar T2 >= 1 or a t2_vec");
+    PNP_CHECK_ARG((mb_vec != nullptr || mini_batch_size >= 1) && n_log >= 1 && log_row0 >= 0 && log_row0 <= INT32_MAX - n_steps,
+                  "bad mini_batch_size / log");
+    PNP_CHECK_ARG(p->dtype == PNP_F32 && p->H == 256 && p->W == 256, "the one-kernel iteration exists for f32 plans of 256 x 256");
+    PNP_CHECK_ARG(z != w_prev && z != w_next && z != v_prev && w_prev != w_next && w_prev != v_prev && w_next != v_prev,
+                  "z, w_prev, w_next and v_prev must be buffers of their own");
+    PNP_CHECK_ARG(sse_log != outer_log, "sse_log and outer_log must be rings of their own");
+    return csmri_sarah_span_launch(p->batch, p->twtab, z, w_prev, w_next, v_prev, mask_bitsT, yh, alpha_vec, selbits, step0, n_steps, T2,
+                                   t2_vec, eta, eta_pp, lr, lr_pp, mini_batch_size, mb_vec, sigma_modifier, sigma_modifier_pp,
+                                   fallback_sigma, xrec, sse_log, outer_log, log_row0, n_log, sigma_out, stream);
 }
 
 // ---- n_steps GD or SGD inner iterations in one launch, z in place (yh: the GD form on the mask; YT: the SGD form on n_steps drawn slots)

@@ -1280,6 +1280,72 @@ __global__ __launch_bounds__(FT) void k_sarah_outer(float* z, float* w_prev, flo
     }
 }
 
+// Per-problem T2 for pnp_sarah (pnp_csmri_sarah_span_pp): n_steps consecutive inner iterations s = step0 .. step0 + n_steps - 1 of
+// every problem in one launch, where problem b takes its outer step at the steps with s % T2_b == 0 -- k_sarah_outer with the loop of
+// k_svrg_span_pp.  T2_b = t2_vec[prob] (int32 [batch]; NULL: the scalar T2; an entry below 1 counts as 1); a span may begin in the
+// middle of a problem's outer iteration (j = step0 % T2_b).  One workgroup owns one problem, so "does this step take the outer
+// step" is wave-uniform.  Step i: where j == 0 the outer step, k_sarah_outer's first body (z not written, eta without decay), its
+// squared error to outer_log row (log_row0 + i) % n_log -- elsewhere one lane writes NaN there, so the ring needs no host fill --
+// then the inner iteration, the body of k_sarah_iter<FUSED_FULL, true> on selbits slot i ([n_steps][batch][W][H/32]; unlike the
+// SVRG span the slot of a refresh step IS read), its squared error to sse_log row (log_row0 + i) % n_log.  Between two bodies the
+// data goes through memory as in k_sarah_outer.  eta_pp, lr_pp, mb_vec, sm_pp and the coefficients: k_sarah_outer's, expression
+// for expression.  A template (launched as <0>; nothing reads TAG) only to be emitted behind every existing kernel, as
+// k_saga_span_hist: a plain kernel here would renumber the long-branch labels of the loop kernels behind it in the listing.
+template <int TAG>
+__global__ __launch_bounds__(FT) void k_sarah_span_pp(float* z, float* w_prev, float* w_next, float* v_prev,
+                                                      const uint32_t* __restrict__ mask_bits, const cx<float>* __restrict__ yh,
+                                                      const float* __restrict__ alpha_vec, const uint32_t* __restrict__ selbits,
+                                                      int step0, int n_steps, int T2, const int32_t* __restrict__ t2_vec, double eta,
+                                                      const double* __restrict__ eta_pp, double lr, const double* __restrict__ lr_pp,
+                                                      int mini_batch_size, const int32_t* __restrict__ mb_vec,
+                                                      const cx<float>* __restrict__ twtab, float sigma_modifier,
+                                                      const double* __restrict__ sm_pp, float fallback_sigma,
+                                                      const float* __restrict__ xrec, double* __restrict__ sse_log,
+                                                      double* __restrict__ outer_log, int log_row0, int n_log,
+                                                      float* __restrict__ sigma_out) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    __shared__ FusedShared sh;
+    const int prob = blockIdx.x, batch = gridDim.x;
+    if (eta_pp != nullptr) eta = eta_pp[prob];
+    if (lr_pp != nullptr) lr = lr_pp[prob];
+    if (mb_vec != nullptr) mini_batch_size = mb_vec[prob];
+    if (sm_pp != nullptr) sigma_modifier = (float)sm_pp[prob];
+    if (t2_vec != nullptr) T2 = t2_vec[prob];
+    if (T2 < 1) T2 = 1;
+    const double alpha = 1.0 / (double)mini_batch_size;
+    const float scale_inner = (float)(alpha * (1.0 / ((double)FN * (double)FN)));
+    const float gamma_outer = (float)(-eta), gamma_inner = (float)(-lr);
+    const size_t img = (size_t)prob * FN * FN;
+    const float inv_n = 1.0f / ((float)FN * (float)FN);
+    float* zi = z + img;
+    int j = step0 % T2;                                         // position of step s inside this problem's outer iteration
+#pragma unroll 1
+    for (int i = 0; i < n_steps; ++i) {
+        if (i > 0) {
+            // this step reads what the last one wrote (same lanes, same addresses): stores done, no stale line in the L1
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            __syncthreads();
+        }
+        const size_t row = (size_t)((log_row0 + i) % n_log) * batch + prob;
+        if (j == 0) {
+            // the outer step (pnp_csmri_svrg_outer_step with out = w_next, w_out = w_prev, mu_out = v_prev)
+            svrg_iter_body<FUSED_FULL, true, 0>(lds_raw, sh, zi, nullptr, mask_bits + (size_t)prob * FN * 8, yh + (size_t)prob * (FN / 2) * FN,
+                                                twtab, inv_n * alpha_vec[prob], 1.0f, zi, gamma_outer, nullptr, w_next + img, sigma_modifier,
+                                                fallback_sigma, xrec + img, outer_log + row, sigma_out + prob, w_prev + img, v_prev + img);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            __syncthreads();
+        } else if (threadIdx.x == 0) {
+            outer_log[row] = __builtin_nan("");
+        }
+        svrg_iter_body<FUSED_FULL, false, 2, 2>(lds_raw, sh, w_next + img, w_prev + img, selbits + ((size_t)i * batch + prob) * FN * 8, nullptr,
+                                                twtab, scale_inner, 1.0f, v_prev + img, gamma_inner, zi, zi, sigma_modifier, fallback_sigma,
+                                                xrec + img, sse_log + row, sigma_out + prob, nullptr, nullptr, v_prev + img, w_prev + img);
+        if (++j == T2) j = 0;
+    }
+}
+
 // n_steps consecutive GD or SGD inner iterations of every problem in one launch, z in place (pnp_csmri_grad_span;
 // algorithms/pnp_gd.py:24-70 / pnp_sgd.py:24-70 with a = c1 = out = z): step i is the body of the per-iteration kernel it replaces --
 // YTERM = false (GD): k_svrg_iter<FUSED_FULL, false, 1> on the packed data term yh and the SAME selector bits ([batch][W][H/32], the
@@ -1809,6 +1875,31 @@ int csmri_saga_hist_launch(int batch, const void* twtab, const void* a, const ui
         else k_saga_iter_hist<1><<<batch, FT, F_LDS_BYTES, s>>>(PNP_SAGA_ARGS);
 #undef PNP_SAGA_ARGS
     }
+    PNP_CHECK_LAUNCH();
+    return PNP_OK;
+}
+
+// one launch = n_steps SARAH inner iterations of every problem, outer steps where a problem's own T2 puts them (k_sarah_span_pp)
+int csmri_sarah_span_launch(int batch, const void* twtab, void* z, void* w_prev, void* w_next, void* v_prev, const uint32_t* mask_bits,
+                            const void* yh, const void* alpha_vec, const uint32_t* selbits, int step0, int n_steps, int T2,
+                            const int32_t* t2_vec, double eta, const double* eta_pp, double lr, const double* lr_pp, int mini_batch_size,
+                            const int32_t* mb_vec, double sigma_modifier, const double* sm_pp, double fallback_sigma, const void* xrec,
+                            double* sse_log, double* outer_log, int log_row0, int n_log, void* sigma_out, void* stream) {
+    {   // > 64 KiB of dynamic LDS needs the opt-in, once per device (as fused_lds_optin; here: the kernel's first use in the file)
+        static unsigned long long attr_done = 0;
+        int dev = 0;
+        PNP_CHECK_HIP(hipGetDevice(&dev));
+        if (!((attr_done >> (dev & 63)) & 1ull)) {
+            PNP_CHECK_HIP(hipFuncSetAttribute((const void*)k_sarah_span_pp<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F_LDS_BYTES));
+            attr_done |= 1ull << (dev & 63);
+        }
+    }
+    k_sarah_span_pp<0><<<batch, FT, F_LDS_BYTES, (hipStream_t)stream>>>((float*)z, (float*)w_prev, (float*)w_next, (float*)v_prev, mask_bits,
+                                                                       (const cx<float>*)yh, (const float*)alpha_vec, selbits, step0, n_steps,
+                                                                       T2, t2_vec, eta, eta_pp, lr, lr_pp, mini_batch_size, mb_vec,
+                                                                       (const cx<float>*)twtab, (float)sigma_modifier, sm_pp,
+                                                                       (float)fallback_sigma, (const float*)xrec, sse_log, outer_log, log_row0,
+                                                                       n_log, (float*)sigma_out);
     PNP_CHECK_LAUNCH();
     return PNP_OK;
 }

@@ -31,6 +31,11 @@ SvrgEngine takes `T2` per problem as well: a [B] integer array make
 s % T2[b] == 0 -- one `pnp_refresh_pp` launch behind a full gradient at the steps where any problem refreshes -- and `run_span(n)`
 runs n steps in launches of `pnp_csmri_svrg_span_pp` where the one-kernel iteration holds the TV prox.  A scalar T2 takes exactly
 the calls it always took.
+SarahEngine takes `T2` per problem too, with `split_log=True` (opt-in): the outer prox of problem b, made at the steps with
+s % T2[b] == 0, is logged in a second ring `outer_log` (NaN where a problem made none) beside the aligned inner rows of `sse_log`;
+`step()` makes the outer step of the whole batch into scratch and adopts it per problem with one `pnp_refresh_pp` and one
+`pnp_select_pp` launch, `run_span(n)` runs n steps in launches of `pnp_csmri_sarah_span_pp` where the one-kernel forms hold the TV
+prox.  Without it an array T2 is refused as before and a scalar T2 takes exactly the calls it always took.
 GdEngine, SgdEngine and SagaEngine take `fused=True` as well (opt-in): an inner iteration is then ONE `pnp_csmri_grad_step`
 (GD: the mask and its packed data term; SGD: the drawn slot and the raw data, the slot's data term formed inside the kernel) or ONE
 `pnp_csmri_saga_step` (gradient, table update, step and prox) on a float32 256 x 256 CsmriBatch, with the coefficients, draws and
@@ -259,6 +264,23 @@ class GdEngine(_FusedStep, LoopEngine):
             n -= m
 
 
+def _t2_vector(batch, T2, span, ahead):
+    """A per-problem T2 checked on the host (the kernels cannot): -> (the [B] int64 vector, the draw window `span`).  Shared by
+    SvrgEngine and SarahEngine; every refusal names the offender."""
+    t2 = np.asarray(T2)
+    if not batch.per_problem:
+        raise ValueError(f'per-problem T2 needs a batch that takes per-problem values (got {batch.kind!r})')
+    if t2.shape != (batch.B,) or not np.issubdtype(t2.dtype, np.integer):
+        raise ValueError(f'per-problem T2: {batch.B} integers, got shape {t2.shape} of {t2.dtype}')
+    bad = np.flatnonzero((t2 < 1) | (t2 > np.iinfo(np.int32).max))
+    if bad.size:
+        raise ValueError(f'per-problem T2: entries must be >= 1 (problem {int(bad[0])}: T2 {int(t2[bad[0]])})')
+    n = int(ahead if span is None else span)
+    if n < 1:
+        raise ValueError(f'span: at least one step per draw window, got {span}')
+    return np.ascontiguousarray(t2, np.int64), n
+
+
 class _StochEngine(LoopEngine):
     # Engines that draw one minibatch per step (sgd, saga, sarah) draw AHEAD steps per launch: the draw kernel is
     # latency-bound (a 32-step radix select per problem, ~50 us whatever the grid), and a step's descriptor depends on
@@ -286,6 +308,7 @@ class _StochEngine(LoopEngine):
         self._window = n_slots is None                          # one draw launch per AHEAD steps (else: the subclass draws)
         self.mbs = batch.minibatches(self.AHEAD if n_slots is None else n_slots)
         self._drawn_base = None                                 # first step of the window the slots currently hold
+        self._drawn_n = 0                                       # per-problem T2: the slots hold steps [_drawn_base, _drawn_base + _drawn_n)
 
     def _minibatch(self, idx_s, step_id):
         """Bind a slot to this step's minibatch and return it: host index lists when given (slot 0), else a device draw."""
@@ -306,6 +329,32 @@ class _StochEngine(LoopEngine):
     def _draw_slot(self, slot, step_id):
         self.b.draw(self.mbs.slot(slot), self._mb_draw, self.seed, step_id, 1, **self._draw_kw)
         self.mbs.host[slot] = None
+
+    # ---- per-problem T2 (SvrgEngine, SarahEngine): self.T2 a [B] int64 vector, self.span the draw window
+    def refreshes(self, s):
+        """Per-problem T2 (SvrgEngine, SarahEngine): whether any problem refreshes at step s (the host knows s and the vector)."""
+        return bool((s % self.T2 == 0).any())
+
+    def _lr_pp(self, s):
+        """Per-problem T2: (step sizes, decay exponents k_b = s // T2_b) of step s.  Each step size is the product the scalar engine
+        forms from problem b's values, eta_b * lr_decay ** k_b in Python floats; lr_decay == 1 leaves eta as it was given."""
+        k = s // self.T2
+        if self.lr_decay == 1.0:
+            return self.eta, k
+        eta = np.broadcast_to(np.asarray(self.eta, np.float64), k.shape)
+        return np.array([float(e) * self.lr_decay ** int(kb) for e, kb in zip(eta, k)], np.float64), k
+
+    def _slot_pp(self, idx_s, s):
+        """Per-problem T2: the slot that holds step s's minibatch -- a window of `span` steps from s on, drawn with the absolute step
+        ids when s is outside the window the slots hold; host index lists go to slot 0."""
+        if idx_s is not None:
+            self.b.set_host(self.mbs, 0, idx_s)
+            self._drawn_base = None
+            return 0
+        if self._drawn_base is None or not self._drawn_base <= s < self._drawn_base + self._drawn_n:
+            self.b.draw(self.mbs, self._mb_draw, self.seed, s, self.span, **self._draw_kw)
+            self._drawn_base, self._drawn_n = s, self.span
+        return s - self._drawn_base
 
 
 class SgdEngine(_FusedStep, _StochEngine):
@@ -369,25 +418,14 @@ class SvrgEngine(_StochEngine):
                  fold_outer=True, draw_id=None, span=None, log_objective=False):
         t2 = None
         if np.ndim(T2) != 0:                                    # per-problem T2: checked on the host (the kernels cannot)
-            t2 = np.asarray(T2)
-            if not batch.per_problem:
-                raise ValueError(f'per-problem T2 needs a batch that takes per-problem values (got {batch.kind!r})')
-            if t2.shape != (batch.B,) or not np.issubdtype(t2.dtype, np.integer):
-                raise ValueError(f'per-problem T2: {batch.B} integers, got shape {t2.shape} of {t2.dtype}')
-            bad = np.flatnonzero((t2 < 1) | (t2 > np.iinfo(np.int32).max))
-            if bad.size:
-                raise ValueError(f'per-problem T2: entries must be >= 1 (problem {int(bad[0])}: T2 {int(t2[bad[0]])})')
-            T2 = np.ascontiguousarray(t2, np.int64)
-            self.span = int(self.AHEAD if span is None else span)
-            if self.span < 1:
-                raise ValueError(f'span: at least one step per draw window, got {span}')
+            t2, n_span = _t2_vector(batch, T2, span, self.AHEAD)
+            T2, self.span = t2, n_span
         elif span is not None:
             raise ValueError('span is the draw window of a per-problem T2; a scalar T2 draws an outer iteration at a time')
         super().__init__(batch, prox, eta, mini_batch_size, lr_decay, n_log, seed, n_slots=T2 if t2 is None else self.span, draw_id=draw_id,
                          log_objective=log_objective)
         self.T2, self.variant = T2, variant
         self._t2_dev = self._mu_new = None                      # per-problem T2: its int32 device vector, the refresh's scratch
-        self._drawn_n = 0                                       # ... and the steps [_drawn_base, _drawn_base + _drawn_n) the slots hold
         if t2 is not None:
             self._t2_dev = torch.from_numpy(T2.astype(np.int32)).to(batch.xrec.device)
             self._mu_new = torch.empty_like(self.z)
@@ -439,31 +477,6 @@ class SvrgEngine(_StochEngine):
             self._log_obj(self.n_prox % self.n_log, self.z)
         self.n_prox += 1
         self.s += 1                                             # eager steps keep the index on the host (no counter launch)
-
-    def refreshes(self, s):
-        """Per-problem T2: whether any problem refreshes at step s (the host knows s and the vector)."""
-        return bool((s % self.T2 == 0).any())
-
-    def _lr_pp(self, s):
-        """Per-problem T2: (step sizes, decay exponents k_b = s // T2_b) of step s.  Each step size is the product the scalar engine
-        forms from problem b's values, eta_b * lr_decay ** k_b in Python floats; lr_decay == 1 leaves eta as it was given."""
-        k = s // self.T2
-        if self.lr_decay == 1.0:
-            return self.eta, k
-        eta = np.broadcast_to(np.asarray(self.eta, np.float64), k.shape)
-        return np.array([float(e) * self.lr_decay ** int(kb) for e, kb in zip(eta, k)], np.float64), k
-
-    def _slot_pp(self, idx_s, s):
-        """Per-problem T2: the slot that holds step s's minibatch -- a window of `span` steps from s on, drawn with the absolute step
-        ids when s is outside the window the slots hold; host index lists go to slot 0."""
-        if idx_s is not None:
-            self.b.set_host(self.mbs, 0, idx_s)
-            self._drawn_base = None
-            return 0
-        if self._drawn_base is None or not self._drawn_base <= s < self._drawn_base + self._drawn_n:
-            self.b.draw(self.mbs, self._mb_draw, self.seed, s, self.span, **self._draw_kw)
-            self._drawn_base, self._drawn_n = s, self.span
-        return s - self._drawn_base
 
     def _step_pp(self, idx_s):
         """`step()` with a per-problem T2: where any problem refreshes, grad_full into the scratch and ONE pnp_refresh_pp; then the
@@ -640,12 +653,37 @@ class SarahEngine(_StochEngine):
     fused=True (opt-in): the one-kernel forms -- the outer step is ONE pnp_csmri_svrg_outer_step (w_prev, v_prev and
     w_next are its three outputs), an inner iteration ONE pnp_csmri_sarah_step that updates v_prev, z and w_prev where they lie.
     Needs a float32 256 x 256 CsmriBatch, a TV or DnCNN prox and log_objective=False; `capture()` / `run_outer(n)` then replay
-    one outer iteration (T2 + 1 log rows) as a hipGraph."""
+    one outer iteration (T2 + 1 log rows) as a hipGraph.
+    T2: an int, or -- with split_log=True (opt-in) -- a [B] integer array on a batch that takes per-problem values:
+    problem b then takes its outer step at the steps with s % T2[b] == 0 and walks, bit for bit, the trajectory a scalar engine with
+    T2[b] walks on the same path.  The log is split: `sse_log` row s % n_log holds inner iteration s of every problem (n_prox == s),
+    a second ring `outer_log` holds in the same row the squared error of the outer prox a problem made at step s, NaN elsewhere
+    (`outer_trace()`, `psnr_trace_of(b)`).  At a step where any problem refreshes `step()` makes the outer step for the WHOLE batch
+    into scratch buffers and adopts it per problem with one pnp_refresh_pp and one pnp_select_pp launch; `run_span(n)` runs n steps in
+    launches of pnp_csmri_sarah_span_pp where `outer_kernel_ok()` holds and lr_decay == 1.  `span` is the draw window as in
+    SvrgEngine.  There is no hipGraph form, no objective log, and no prox whose result depends on its call count."""
 
     def __init__(self, batch, prox, eta, T2, mini_batch_size, lr_decay=1.0, n_log=4096, seed=0, draw_id=None, log_objective=False,
-                 *, fused=False):
+                 *, fused=False, split_log=False, span=None):
+        t2 = None
         if np.ndim(T2) != 0:
-            raise ValueError('SarahEngine takes a scalar T2 (its outer prox logs a row of its own: rows would stop lining up)')
+            if not split_log:
+                raise ValueError('SarahEngine takes a scalar T2 (its outer prox logs a row of its own: rows would stop lining up) '
+                                 'unless split_log=True gives the outer rows a ring of their own')
+            t2, self.span = _t2_vector(batch, T2, span, self.AHEAD)
+            if log_objective:
+                raise ValueError('SarahEngine with a per-problem T2 does not log the objective (log_objective=True): the objective '
+                                 'ring is laid out row for row with the single log of a scalar T2')
+            if getattr(prox, 'denoise_strength', 0.0) != 0.0 and getattr(prox, 'decay', 1.0) != 1.0:
+                raise ValueError('SarahEngine with a per-problem T2 needs a prox whose result does not depend on its call count '
+                                 '(denoise_strength != 0 with decay != 1 does): the problems would have made different numbers of '
+                                 'prox calls')
+            T2 = t2
+        elif split_log:
+            raise ValueError('split_log=True is the log layout of a per-problem T2 ([B] integers); a scalar T2 keeps the single log')
+        elif span is not None:
+            raise ValueError('span is the draw window of a per-problem T2; a scalar T2 draws a window of AHEAD steps (an outer '
+                             'iteration with fused=True)')
         self.fused = bool(fused)
         if self.fused:
             missing = []
@@ -663,12 +701,24 @@ class SarahEngine(_StochEngine):
             if missing:
                 raise ValueError('SarahEngine(fused=True) needs ' + ', '.join(missing))
         # fused: the draws of a whole outer iteration are ONE launch at the outer step (T2 selector slots, as SvrgEngine)
-        super().__init__(batch, prox, eta, mini_batch_size, lr_decay, n_log, seed, n_slots=T2 if self.fused else None, draw_id=draw_id,
-                         log_objective=log_objective)
+        super().__init__(batch, prox, eta, mini_batch_size, lr_decay, n_log, seed,
+                         n_slots=self.span if t2 is not None else T2 if self.fused else None, draw_id=draw_id, log_objective=log_objective)
         self.T2 = T2
         self.w_prev = torch.empty_like(self.z)
         self.w_next = torch.empty_like(self.z)
         self.v_prev = torch.empty_like(self.z)
+        self._t2_dev = self.outer_log = None
+        if t2 is not None:
+            # per-problem T2: the int32 device vector, the second ring, and the scratch of the whole-batch outer step (the full
+            # gradient, the stepped image the prox runs on, the kernel's w_out with fused=True, the row of its squared errors)
+            dev = batch.xrec.device
+            self._t2_dev = torch.from_numpy(T2.astype(np.int32)).to(dev)
+            self.outer_log = torch.full((n_log, batch.B), float('nan'), dtype=torch.float64, device=dev)
+            self._outer_dirty = np.zeros(n_log, bool)           # rows of outer_log that hold a value of some problem
+            self._v_new = torch.empty_like(self.z)
+            self._tmp = torch.empty_like(self.z)
+            self._w_scr = torch.empty_like(self.z) if self.fused else None
+            self.sse_tmp = torch.zeros(batch.B, dtype=torch.float64, device=dev)
         if not self.fused:
             self.v_next = torch.empty_like(self.z)
             return
@@ -687,8 +737,14 @@ class SarahEngine(_StochEngine):
             self.row_dev.zero_()
             self.step_dev.zero_()
             self._dev_step = 0
+        if self._t2_dev is not None:
+            self.outer_log.fill_(float('nan'))
+            self._outer_dirty[:] = False
+            self._drawn_base = None
 
     def step(self, idx_s=None):
+        if self._t2_dev is not None:
+            return self._step_pp(idx_s)
         if self.fused:
             return self._step_fused(idx_s)
         b, s = self.b, self.s
@@ -708,6 +764,105 @@ class SarahEngine(_StochEngine):
         self.v_prev, self.v_next = self.v_next, self.v_prev
         self.w_prev.copy_(self.z)
         self.s += 1
+
+    # ---- per-problem T2 (split_log=True)
+    def _outer_row(self, s, refresh):
+        """Row s % n_log of outer_log for step s.  Where some problem refreshes, pnp_select_pp (or the span kernel) writes the whole
+        row, NaN included; where none does nothing is launched -- unless the ring has wrapped onto a row that holds values."""
+        r = s % self.n_log
+        if not refresh and self._outer_dirty[r]:
+            self.outer_log[r].fill_(float('nan'))
+        self._outer_dirty[r] = refresh
+        return self.outer_log[r]
+
+    def _step_pp(self, idx_s):
+        """`step()` with a per-problem T2.  Where any problem refreshes: the outer step of the whole batch into scratch (streaming:
+        grad_full, the axpbypcz of the scalar engine, the prox; fused: ONE pnp_csmri_svrg_outer_step), then ONE pnp_refresh_pp
+        (v_prev, w_prev) and ONE pnp_select_pp (w_next and the outer log row) adopt it for the refreshing problems alone.  Then the
+        ordinary inner iteration for all problems.  The whole batch pays that gradient and prox; only the refreshing problems keep
+        them."""
+        b, px, s = self.b, self.prox, self.s
+        refresh = self.refreshes(s)
+        row = self._outer_row(s, refresh)
+        if refresh:
+            if self.fused:
+                den = px.fused_denoise
+                b.plan.svrg_outer_step(self.z, b.bits, b.yh_full, b.inv_m0, self._c('eta', 0, self.eta), self._w_scr, self._v_new,
+                                       out=self._tmp, denoise=_fused_kind(px), xrec=b.xrec, sse=self.sse_tmp if den else None,
+                                       **px.fused_args())
+                px.after_fused(self._tmp, b.xrec, self.sse_tmp)
+                res = self._tmp
+            else:
+                b.grad_full(self.z, out=self._v_new)
+            ops.refresh_pp(self._v_new, self.z, self.v_prev, self.w_prev, self._t2_dev, s)
+            if not self.fused:
+                # (F6: no lr_decay here -- '-eta' is made once; for a refreshing problem z, v_new ARE its w_prev, v_prev)
+                ops.axpbypcz(1.0, self.z, self._c('-eta', 0, -self.eta), self._v_new, out=self._tmp)
+                res = px(self._tmp, b.xrec, self.sse_tmp)
+            ops.select_pp(res, self.w_next, self._t2_dev, s, self.sse_tmp, row)
+            self._tmp = res                                     # (a prox that ping-pongs hands back the buffer that is free now)
+        j = self._slot_pp(idx_s, s)
+        lr, k = self._lr_pp(s)
+        sse_out = self.sse_log[s % self.n_log]
+        if self.fused:
+            self._fused_inner(j, lr, k, sse_out)
+        else:
+            b.grad_stoch_diff(self.w_next, self.w_prev, self.mbs, j, out=self.v_next, alpha=self._c('1/mb', 0, 1.0 / self.mb), beta=1.0,
+                              c1=self.v_prev)
+            ops.axpbypcz(1.0, self.z, self._c('-lr', k, -lr), self.v_next, out=self.z)
+            self.z = px(self.z, b.xrec, sse_out)
+            self.v_prev, self.v_next = self.v_next, self.v_prev
+            self.w_prev.copy_(self.z)
+        self.n_prox += 1
+        self.s += 1
+
+    def run_span(self, n):
+        """n inner iterations from any step count.  With a per-problem T2, `outer_kernel_ok()` and lr_decay == 1 they run in
+        launches of at most `span` steps -- one draw launch plus one pnp_csmri_sarah_span_pp each, in which the workgroup that owns
+        a problem runs its steps back to back and takes its outer step where its own T2 says -- the same bits as stepping;
+        otherwise eager steps (TVProx(in_kernel=True) among them: the span kernel holds the per-column prox only)."""
+        if not (self._t2_dev is not None and self.lr_decay == 1.0 and self.outer_kernel_ok()):
+            for _ in range(n):
+                self.step()
+            return
+        b, px = self.b, self.prox
+        while n > 0:
+            m = min(n, self.span)
+            b.draw(self.mbs, self._mb_draw, self.seed, self.s, m, **self._draw_kw)
+            self._drawn_base, self._drawn_n = self.s, m
+            eta = self._c('eta', 0, self.eta)                   # (lr_decay == 1: the inner step size is eta as well)
+            b.plan.sarah_span(self.z, self.w_prev, self.w_next, self.v_prev, b.bits, b.yh_full, b.inv_m0, self.mbs.selbits, self.s, m,
+                              self._t2_dev, eta, eta, self._mb_draw, b.xrec, self.sse_log, self.outer_log, self.s % self.n_log, px.sig,
+                              sigma_modifier=px.sigma_modifier)
+            for s in range(self.s, self.s + m):                 # (the kernel writes every row it passes, NaN included)
+                self._outer_dirty[s % self.n_log] = self.refreshes(s)
+            self.s += m
+            self.n_prox += m
+            px.t += m
+            n -= m
+
+    def _split_rows(self, log):
+        if self._t2_dev is None:
+            raise ValueError('the split log is the layout of a per-problem T2 (SarahEngine(T2=[B] ints, split_log=True))')
+        sse = self._ring(log).cpu().numpy()
+        with np.errstate(divide='ignore', invalid='ignore'):
+            return np.around(10 * np.log10(1.0 / (sse / self.b.N)), 2)
+
+    def outer_trace(self):
+        """Per-problem T2: [steps][B] PSNR of the outer prox problem b made at each step, NaN where it made none; the rows are
+        those of `psnr_trace()` (the inner iterations)."""
+        return self._split_rows(self.outer_log)
+
+    def psnr_trace_of(self, b):
+        """Per-problem T2: problem b's rows in the order a scalar SarahEngine with T2[b] logs them -- at each step the outer row if
+        the problem made an outer step there, then the inner row -- i.e. `psnr_trace()[:, 0]` of that engine on this problem."""
+        inner, outer = self._split_rows(self.sse_log)[:, b], self._split_rows(self.outer_log)[:, b]
+        rows = []
+        for o, i in zip(outer, inner):
+            if not np.isnan(o):
+                rows.append(o)
+            rows.append(i)
+        return np.array(rows, inner.dtype)
 
     # ---- the one-kernel forms (fused=True)
     def _step_fused(self, idx_s):
@@ -766,13 +921,16 @@ class SarahEngine(_StochEngine):
     def graph_ok(self):
         """Whether one outer iteration of this engine can be captured: the fused path (the streaming path swaps buffers and may get
         fresh tensors from its prox), constant step size, an in-place prox without host-side per-call state, device draws."""
-        return (self.fused and self.lr_decay == 1.0 and getattr(self.prox, 'inplace', False)
+        return (self._t2_dev is None and self.fused and self.lr_decay == 1.0 and getattr(self.prox, 'inplace', False)
                 and getattr(self.prox, 'denoise_strength', 0.0) == 0.0 and not self.log_objective
                 and all(h is None for h in self.mbs.host))
 
     def capture(self):
         """Capture one outer iteration into a hipGraph.  Needs `graph_ok()` and a step count that is a multiple of T2.  State is left
         untouched, also when the capture fails."""
+        if self._t2_dev is not None:
+            raise ValueError('capture: with a per-problem T2 the batch has no common outer iteration to capture in a hipGraph; use '
+                             'run_span(n_steps)')
         if not self.graph_ok():
             raise ValueError('this SarahEngine cannot be captured in a hipGraph (needs fused=True, lr_decay == 1, device-drawn '
                              'minibatches and an in-place prox without host-side per-call state: TVProx with denoise_strength == 0 '
@@ -818,6 +976,8 @@ class SarahEngine(_StochEngine):
         `outer_kernel_ok()`): every outer iteration is ONE draw launch + ONE pnp_csmri_sarah_outer_iteration, in which the
         workgroup that owns a problem runs the outer step (eta, no decay: F6) and its T2 inner iterations (eta * lr_decay ** k) back
         to back."""
+        if self._t2_dev is not None:
+            raise ValueError('run_outer: with a per-problem T2 the batch has no common outer iteration; use run_span(n_steps)')
         if one_launch:
             missing = self._outer_kernel_missing()
             if not (self.s % self.T2 == 0 and self.n_prox == self.s + self.s // self.T2):

@@ -411,6 +411,27 @@ class CsmriPlan:
                 _pp(eta, self.B), _pp(lr, self.B), _pp(mini_batch_size, self.B, torch.int32), _pp(sigma_modifier, self.B),
                 float(fallback_sigma), _p(xrec), _p(sse_log), int(log_row0), int(sse_log.shape[0]), _p(sigma_out), _stream()])
 
+    def sarah_span(self, z, w_prev, w_next, v_prev, mask_bits, yh, alpha_vec, selbits, step0, n_steps, T2, eta, lr, mini_batch_size,
+                   xrec, sse_log, outer_log, log_row0, sigma_out, *, sigma_modifier=1.0, fallback_sigma=0.0):
+        """pnp_csmri_sarah_span_pp: inner iterations step0 .. step0 + n_steps - 1 of pnp_sarah with the TV prox in ONE launch, every
+        problem taking its outer step (w_prev = z, v_prev = grad_full(z), w_next = prox_TV(z - eta * v_prev)) at the steps its own T2
+        names.  T2: an int32 [B] device tensor (or an int); selbits: int32 [>= n_steps, B, W, H/32], slot i = step step0 + i; sse_log
+        and outer_log: float64 [n_log, B] rings of their own, row (log_row0 + i) % n_log (outer_log: NaN where no outer step was made).
+        eta, lr, mini_batch_size, sigma_modifier: scalars or [B] device tensors."""
+        self._span_log('sarah_span', sse_log, sigma_out, z, w_prev, w_next, v_prev, xrec)
+        assert mask_bits.dtype == torch.int32 and tuple(mask_bits.shape) == (self.B, self.W, self.H // 32)
+        assert selbits.dtype == torch.int32 and selbits.shape[0] >= n_steps and tuple(selbits.shape[1:]) == (self.B, self.W, self.H // 32)
+        assert outer_log.dtype == torch.float64 and outer_log.shape == sse_log.shape and outer_log.is_contiguous()
+        if len({t.data_ptr() for t in (z, w_prev, w_next, v_prev)}) != 4:
+            raise ValueError('sarah_span: z, w_prev, w_next and v_prev must be buffers of their own')
+        args = [self._h, _p(z), _p(w_prev), _p(w_next), _p(v_prev), _p(mask_bits), _p(yh), _p(alpha_vec), _p(selbits), int(step0),
+                int(n_steps)]
+        for v in (_pp(T2, self.B, torch.int32), _pp(eta, self.B), _pp(lr, self.B), _pp(mini_batch_size, self.B, torch.int32),
+                  _pp(sigma_modifier, self.B)):
+            args += (v[0], _p(v[1]))                            # (scalar, array or NULL): the entry point has the _pp form only
+        N.call('pnp_csmri_sarah_span_pp', *args, float(fallback_sigma), _p(xrec), _p(sse_log), _p(outer_log), int(log_row0),
+               int(sse_log.shape[0]), _p(sigma_out), _stream())
+
     def grad_span(self, z, bits, n_steps, xrec, sse_log, log_row0, sigma_out, *, yh=None, YT=None, alpha=1.0, beta=1.0, alpha_vec=None,
                   sigma_modifier=1.0, fallback_sigma=0.0):
         """pnp_csmri_grad_span: n_steps GD or SGD inner iterations with the TV prox in ONE launch, z in place.  yh with bits = the mask
@@ -648,6 +669,21 @@ def refresh_pp(mu_new, z, mu, w, t2_vec, step):
     for t in (mu_new, mu, w):
         assert t.dtype == z.dtype and t.shape == z.shape
     N.call('pnp_refresh_pp', _p(mu_new), _p(z), _p(mu), _p(w), _p(t2_vec), int(step), z.numel(), int(B), _DT[z.dtype], _stream())
+
+
+def select_pp(src, dst, t2_vec, step, row_in=None, row_out=None):
+    """pnp_select_pp: dst[p] = src[p] and row_out[p] = row_in[p] for every problem p = row p of the [B, ...] tensors with
+    step % t2_vec[p] == 0; the other problems' dst stays untouched and their row_out[p] becomes NaN (t2_vec: int32 [B] device tensor,
+    entries >= 1; step: a host int; row_in, row_out: float64 [B], both or neither).  ONE launch."""
+    require_gpu()
+    B = src.shape[0]
+    assert t2_vec.dtype == torch.int32 and tuple(t2_vec.shape) == (B,), f'per-problem T2: an int32 [{B}] device tensor'
+    assert dst.dtype == src.dtype and dst.shape == src.shape
+    if (row_in is None) != (row_out is None):
+        raise ValueError('select_pp: row_in and row_out go together (both or neither)')
+    for r in (row_in, row_out):
+        assert r is None or (r.dtype == torch.float64 and tuple(r.shape) == (B,) and r.is_contiguous())
+    N.call('pnp_select_pp', _p(src), _p(dst), _p(row_in), _p(row_out), _p(t2_vec), int(step), src.numel(), int(B), _DT[src.dtype], _stream())
 
 
 _NLM_W0 = {}

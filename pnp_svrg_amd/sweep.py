@@ -154,7 +154,7 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
                 hist_size=50, H=256, W=256, dtype=torch.float32, max_batch=128, seeding='generator', variant='svrg', run_seed=1,
                 keep_trace=False, graph=True, kernel='Minimal', lr_decay=1.0, denoiser_kwargs=None, sigma_modifier=None,
                 shared_matrix=False, wide_trials=False, sarah_trials=False, t2_trials=False, objective=False, sarah_fused=False,
-                fused_steps=False, one_launch=False, hist_trials=False, mixed_scales=False):
+                fused_steps=False, one_launch=False, hist_trials=False, mixed_scales=False, sarah_t2_trials=False):
     """Runner for `run_sweep` / `grid_search` over any cell of the reference's sweep (script_diff_sampratio_set12.py:23-25,
     41-51, 64-131): problem in {'csmri', 'deblur', 'pr'} x algorithm in {'gd', 'sgd', 'svrg', 'saga', 'sarah'} x denoiser in
     {'tv', 'nlm', factory}; `n_inner` inner iterations (prox evaluations of the stepped iterate) per item, hyper-parameters
@@ -222,6 +222,11 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
     default runner would have run it in, so its row equals the default runner's (items with alpha == 1.0: to rounding).  Rows come
     back in item order; `prepare_data` / `run_trials` (wide_trials=True) run on the tiled mixed batch.  False (default): grouping,
     engines, launches, rows and messages are exactly what they were.
+    sarah_t2_trials: opt in to 'T2' as a per-problem trial key for algorithm='sarah' (DESIGN 9.11); needs sarah_trials=True and
+    algorithm='sarah' (ValueError otherwise).  On the batches sarah_trials admits, a slab whose trials name 'T2' runs on a
+    SarahEngine(T2=[B] ints, split_log=True) and advances by `run_span`; its rows ('psnr_trace' included: `psnr_trace_of`) are those of
+    the per-trial runner.  Without it `check_trials` refuses the key, with or without t2_trials, in the words it always used.
+    `run(items)` itself is unchanged by it.
     Beside `run(items)` the runner offers the pieces of a trial-batched grid (`grid_search(batch_trials=True)`):
     `run.prepare_data(items)` builds a rank's batches WITHOUT engines, `run.run_trials(data, trials, max_batch_trials)` runs a list
     of trials ({'eta', 'mini_batch_size', 'sigma_modifier'} overrides) on them as tiled batches, `run.data_key` says which runners
@@ -277,6 +282,11 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
     if mixed_scales and problem != 'deblur':
         raise ValueError(f"mixed_scales=True is for problem='deblur' (got {problem!r}): CSMRI items of any mix of ratios already share a "
                          'batch, and the matrices of phase-retrieval items of different num_meas have different shapes')
+    if not isinstance(sarah_t2_trials, (bool, np.bool_)):
+        raise ValueError(f'sarah_t2_trials: True or False, got {sarah_t2_trials!r}')
+    if sarah_t2_trials and not (sarah_trials and algorithm == 'sarah'):
+        raise ValueError(f"sarah_t2_trials=True needs sarah_trials=True and algorithm='sarah' (got sarah_trials={bool(sarah_trials)!r}, "
+                         f'algorithm {algorithm!r}): it makes T2 a per-problem key of the trial-batched pnp_sarah grid')
     if shared_matrix and problem != 'pr':
         raise ValueError(f"shared_matrix=True is for problem='pr' (got {problem!r}): only its problems have a matrix to share")
     mb, dkw = mini_batch_size, dict(denoiser_kwargs or {})
@@ -439,7 +449,8 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
             self.done += n
 
         def results(self):
-            tr = self.eng.psnr_trace()
+            tr = self.eng.psnr_trace()                          # (a SarahEngine with a T2 vector: the inner rows, so tr[-1] is the last iterate's)
+            split = getattr(self.eng, 'outer_log', None) is not None
             psnr0 = self.batch.psnr_init()
             z = self.eng.z.cpu().numpy()
             fl = self.eng.objective_log() if objective else None
@@ -450,7 +461,7 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
                 if problem == 'csmri':
                     r['M0'] = int(self.batch.M0[j])
                 if keep_trace:
-                    r['psnr_trace'] = tr[:, j].copy()
+                    r['psnr_trace'] = self.eng.psnr_trace_of(j) if split else tr[:, j].copy()
                 if objective:
                     r['f_final'] = float(fl[-1, j])
                     if keep_trace:
@@ -471,7 +482,7 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
             self.batch = base.tiles[nt]
             self.streams = None if base.streams is None else base.streams * nt
             self._row_rngs()
-            per_t2 = t2_trials and any('T2' in tr for tr in trials)
+            per_t2 = (sarah_t2_trials if algorithm == 'sarah' else t2_trials) and any('T2' in tr for tr in trials)
             per_hist = hist_trials and any('hist_size' in tr for tr in trials)
             lay = trial_layout(n, trials, {'eta': eta, 'mini_batch_size': mb, 'sigma_modifier': dkw.get('sigma_modifier', 1.0), 'T2': T2,
                                            'hist_size': hist_size},
@@ -483,7 +494,8 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
                                      None if algorithm == 'gd' else lay['mini_batch_size'], lr_decay=lr_decay, variant=variant,
                                      algorithm=algorithm, hist_size=lay['hist_size'] if per_hist else hist_size,
                                      seed=base.items[0]['id'] + 1,
-                                     draw_id=lay['draw_id'] if self.streams is None else [k for _, k in self.streams], **eng_kw)
+                                     draw_id=lay['draw_id'] if self.streams is None else [k for _, k in self.streams], **eng_kw,
+                                     **(dict(split_log=True) if per_t2 and algorithm == 'sarah' else {}))
 
     item_stream = {}                                            # mixed_scales: item id -> (seed, place) of its minibatch stream
 
@@ -508,7 +520,9 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
     def check_trials(trials):
         """What a trial-batched run supports, each refusal naming the offender."""
         keys = PER_PROBLEM_KEYS
-        if t2_trials and any('T2' in tr for tr in trials):
+        if sarah_t2_trials and any('T2' in tr for tr in trials):     # (make_runner: sarah_trials=True, algorithm 'sarah')
+            keys = PER_PROBLEM_KEYS + ('T2',)
+        elif t2_trials and any('T2' in tr for tr in trials):
             if algorithm != 'svrg':
                 raise ValueError(f"batch_trials: trial key 'T2' has no per-problem form for algorithm {algorithm!r} (t2_trials: 'svrg' "
                                  'only; SarahEngine logs its outer prox in a row of its own, the others have no T2)')
@@ -717,6 +731,7 @@ def grid_search(items, make_runner, grid, group=None, *, batch_trials=False, max
     also take pnp_sarah on csmri, on deblur with wide_trials=True and on pr with shared_matrix=True.
     batch_T2=True (with batch_trials=True; runners made with t2_trials=True, pnp_svrg only -- ValueError otherwise): 'T2' is a
     per-problem key too, so trials that differ in T2 share a batch instead of splitting the grid.  Off by default.
+    Runners made with sarah_trials=True, sarah_t2_trials=True take it for pnp_sarah as well.
     batch_hist=True (with batch_trials=True; runners made with hist_trials=True, pnp_saga only -- ValueError otherwise): 'hist_size' is
     a per-problem key too, so trials that differ in hist_size share a batch whose gradient table is dense over the largest of them
     (DESIGN 9.8).  Off by default.

@@ -20,6 +20,8 @@ this script verifies on the ISA of every k_svrg_iter instantiation that
                                                           one kernel serves the plain and the _pp entry point), both rules
     python tools/check_fused_isa.py --spans [listing.s]   the one-launch forms instead (k_sarah_outer, k_grad_span: GD and SGD,
                                                           k_saga_span -- each serves its plain and its _pp entry point), both rules
+    python tools/check_fused_isa.py --sarah-span [listing.s]   the per-problem-T2 SARAH span instead (k_sarah_span_pp: the outer body and
+                                                          the inner body inside one loop), both rules
     python tools/check_fused_isa.py --hist [listing.s]    the SAGA forms with a per-problem divisor instead (k_saga_iter_hist: denoise on
                                                           and off, k_saga_span_hist), both rules
     python tools/check_fused_isa.py --w2d [listing.s]     the instantiations that hold the 2-D wavelet prox instead (MODE = 3 of
@@ -50,11 +52,11 @@ def regs_of(text):
     return out
 
 
-def kernels(txt, pp=False, sarah=False, steps=False, spans=False, hist=False, w2d=False):
+def kernels(txt, pp=False, sarah=False, steps=False, spans=False, hist=False, w2d=False, sarah_span=False):
     """(name, body) of every k_svrg_iter instantiation and of k_svrg_outer; pp: also k_svrg_outer_pp and k_svrg_span_pp;
     sarah: the k_sarah_iter and k_sarah_iter_pp instantiations instead; steps: the k_grad_step and k_saga_iter instantiations instead;
     spans: k_sarah_outer, the k_grad_span instantiations and k_saga_span instead; hist: the k_saga_iter_hist instantiations and
-    k_saga_span_hist instead"""
+    k_saga_span_hist instead; sarah_span: k_sarah_span_pp instead"""
     names = ('_ZN3pnp11k_svrg_iter', '_ZN3pnp12k_svrg_outer') + (('_ZN3pnp15k_svrg_outer_pp', '_ZN3pnp14k_svrg_span_pp') if pp else ())
     if sarah:
         names = ('_ZN3pnp12k_sarah_iter', '_ZN3pnp15k_sarah_iter_pp')
@@ -64,6 +66,8 @@ def kernels(txt, pp=False, sarah=False, steps=False, spans=False, hist=False, w2
         names = ('_ZN3pnp13k_sarah_outer', '_ZN3pnp11k_grad_span', '_ZN3pnp11k_saga_span')
     if hist:
         names = ('_ZN3pnp16k_saga_iter_hist', '_ZN3pnp16k_saga_span_hist')
+    if sarah_span:
+        names = ('_ZN3pnp15k_sarah_span_pp',)
     if w2d:
         names = ('_ZN3pnp14k_svrg_iter_ppILi3E', '_ZN3pnp15k_sarah_iter_ppILi3E', '_ZN3pnp11k_grad_stepILi3E', '_ZN3pnp11k_saga_iterILi3E',
                  '_ZN3pnp17k_svrg_outer_prox')
@@ -189,17 +193,18 @@ def main():
     steps = '--steps' in args                                   # the minibatch forms instead, with the store rule
     spans = '--spans' in args                                   # the one-launch forms instead, with the store rule
     hist = '--hist' in args                                     # the per-problem-divisor SAGA forms instead, with the store rule
+    sarah_span = '--sarah-span' in args                         # the per-problem-T2 SARAH span instead, with the store rule
     w2d = '--w2d' in args                                       # the instantiations with the 2-D wavelet prox instead, with the store rule
     paths = [a for a in args if not a.startswith('-')]
     txt = listing(paths[0] if paths else None, defines)
     bad = []
     nk = 0
-    for name, body in kernels(txt, pp, sarah, steps, spans, hist, w2d):
+    for name, body in kernels(txt, pp, sarah, steps, spans, hist, w2d, sarah_span):
         nk += 1
         errors, n_loads, n_waits, segs = check(name, body)
         spill = ' '.join(f'{i}:{s["sst"]}/{s["sld"]}' for i, s in enumerate(segs) if s['sst'] or s['sld'])
         stores = ''
-        if sarah or steps or spans or hist or w2d:
+        if sarah or steps or spans or hist or w2d or sarah_span:
             st_errors, n_st = check_stores(name, body)
             errors = errors + st_errors
             stores = f'{n_st} hand-issued stores, '
