@@ -10,43 +10,26 @@ are the specification: every engine is tested to walk the same trajectory as B d
 The batch problems (CsmriBatch, DeblurBatch, PrBatch: the data of B problems and their gradients) are in `batches.py`, the prox
 adapters (TVProx, DnCNNProx, NLMProx) in `prox.py`; both are re-exported here.
 
-Per-problem hyper-parameters (a hyper-parameter grid as one batch): GdEngine, SgdEngine and SvrgEngine take `eta` and
-`mini_batch_size`, and TVProx takes `sigma_modifier`, as a scalar or as a [B] array.  A scalar takes exactly the plain calls; an
-array goes to the `_pp` entry points as float64 / int32 device vectors made once on the host (`-lr`, `-lr / mb`: remade when
-lr_decay != 1 changes them), and problem b then walks, bit for bit, the trajectory a scalar engine with b's values walks.
-`draw_id` ([B] ints) replaces the batch index in the minibatch stream, and `CsmriBatch.tile(n)` repeats a batch's data n times.
-A batch says whether it takes them with its `per_problem` attribute: a CsmriBatch does, and so does `PrBatch.tile(n)`, n * B problems
-on the B matrices of the batch it was tiled from (the non-fused paths only; csrc/pr_shared.hip).
-A DeblurBatch takes them too (`DeblurBatch.tile(n)`: one plan for n * B problems on the same kernel spectrum), NLMProx takes a [B]
-`sigma_modifier`, and SagaEngine takes `eta`, `mini_batch_size` and `draw_id` per problem: a step is then ONE
-`pnp_saga_table_update_pp` launch, as it is when every problem replaces a row of its own.
-SarahEngine takes `eta`, `mini_batch_size` and `draw_id` per problem as well: its two elementwise steps are one
-`pnp_axpbypcz_pp` launch each (`ops.axpbypcz` with a [B] coefficient), its difference of minibatch gradients takes 1 / mb per problem.
-The same launch carries every per-problem combine `g + beta * c1 + gamma * c2` of the Deblur and PR batches and the step of
-SvrgEngine(variant='reference').
-SarahEngine(fused=True) (opt-in) runs an inner iteration as ONE `pnp_csmri_sarah_step` and the outer step as ONE
-`pnp_csmri_svrg_outer_step` on a float32 256 x 256 CsmriBatch, and offers `capture()` / `run_outer(n)`; without it the engine makes
-exactly the calls it always made.
-SvrgEngine takes `T2` per problem as well: a [B] integer array makes problem b refresh mu and w at the steps with
-s % T2[b] == 0 -- one `pnp_refresh_pp` launch behind a full gradient at the steps where any problem refreshes -- and `run_span(n)`
-runs n steps in launches of `pnp_csmri_svrg_span_pp` where the one-kernel iteration holds the TV prox.  A scalar T2 takes exactly
-the calls it always took.
-SarahEngine takes `T2` per problem too, with `split_log=True` (opt-in): the outer prox of problem b, made at the steps with
-s % T2[b] == 0, is logged in a second ring `outer_log` (NaN where a problem made none) beside the aligned inner rows of `sse_log`;
-`step()` makes the outer step of the whole batch into scratch and adopts it per problem with one `pnp_refresh_pp` and one
-`pnp_select_pp` launch, `run_span(n)` runs n steps in launches of `pnp_csmri_sarah_span_pp` where the one-kernel forms hold the TV
-prox.  Without it an array T2 is refused as before and a scalar T2 takes exactly the calls it always took.
-GdEngine, SgdEngine and SagaEngine take `fused=True` as well (opt-in): an inner iteration is then ONE `pnp_csmri_grad_step`
-(GD: the mask and its packed data term; SGD: the drawn slot and the raw data, the slot's data term formed inside the kernel) or ONE
-`pnp_csmri_saga_step` (gradient, table update, step and prox) on a float32 256 x 256 CsmriBatch, with the coefficients, draws and
-rows of the streaming step; without it the engines make exactly the calls they always made.
-The one-launch forms (opt-in): SarahEngine.run_outer(n, one_launch=True) runs every outer iteration as ONE draw launch plus
-ONE `pnp_csmri_sarah_outer_iteration`; GdEngine, SgdEngine and SagaEngine offer `run_span(n)`, launches of at most AHEAD steps of
-`pnp_csmri_grad_span` / `pnp_csmri_saga_span` -- the same bits as stepping; without them the engines make exactly the calls they made.
-Every engine takes `log_objective=True`: beside the squared errors, a second ring `obj_log` gets the data-fidelity
-objective f(z) of the iterate every logged prox returned (`batch.objective`, row for row with `sse_log`; `objective_log()` reads it
-back) -- the convergence signal on measured data, where there is no ground truth for a PSNR.  Such an engine steps eagerly
-(`graph_ok()` and `outer_kernel_ok()` are False); with it off nothing changes.
+What each engine accepts.  Every option is opt-in: without it an engine makes exactly the calls it made before the option existed, and
+with a per-problem value problem b walks, bit for bit, the trajectory a scalar engine with b's value walks.
+
+Every engine: `eta` as a scalar or a [B] array on a batch with `per_problem` set (a CsmriBatch, `PrBatch.tile(n)`,
+`DeblurBatch.tile(n)`).  A scalar stays the Python float of the plain calls; an array goes to the `_pp` entry points as a float64
+device vector made on the host (`_c`: remade only when lr_decay changes it).  `log_objective=True`: a second ring `obj_log`,
+row for row beside `sse_log`, of f(iterate) per logged prox (`objective_log()`); such an engine steps eagerly.
+SgdEngine, SvrgEngine, SarahEngine, SagaEngine: `mini_batch_size` as a scalar or [B] int array, `draw_id` ([B] ints that replace the
+batch index in the minibatch stream), host index lists per step (`step(idx_s)`).
+GdEngine, SgdEngine, SagaEngine: `fused=True`, a step as ONE `pnp_csmri_grad_step` / `pnp_csmri_saga_step` on a float32
+256 x 256 CsmriBatch; `run_span(n)`, launches of at most AHEAD steps of `pnp_csmri_grad_span` / `pnp_csmri_saga_span`.
+SvrgEngine: `variant`, `fused` (None: by batch size) with `fold_outer`, `capture()` / `run_outer(n)` as a hipGraph or as one launch
+per outer iteration; `T2` as a [B] int array with `span` and `run_span(n)` (`pnp_refresh_pp`, `pnp_csmri_svrg_span_pp`).
+SarahEngine: per-problem values through `pnp_axpbypcz_pp`; `fused=True` with `capture()` / `run_outer(n)`,
+`run_outer(n, one_launch=True)`; `T2` as a [B] int array with `split_log=True`: the outer rows in a ring
+of their own, `span` and `run_span(n)` (`pnp_refresh_pp`, `pnp_select_pp`, `pnp_csmri_sarah_span_pp`).
+SagaEngine: rows per step for the batch or per problem (one `pnp_saga_table_update_pp` launch); `hist_size` as a [B] int
+array.
+The one-kernel forms hold the per-column TV prox, the single-step kernels and SvrgEngine's one-launch outer iteration also the 2-D
+wavelet prox of TVProx(in_kernel=True); any other prox with `fused_args` follows the kernel (`after_fused`).
 """
 import numpy as np
 import torch
@@ -113,6 +96,13 @@ class LoopEngine:
             return torch.roll(log, -(self.n_prox % self.n_log), 0)             # oldest surviving row first
         return log[:self.n_prox]
 
+    def _psnr(self, log):
+        """The rows of a ring of squared errors as PSNR, rounded to 0.01 dB like problems/problem.py:33-35, read back once (NaN stays
+        NaN: the split log of SarahEngine)."""
+        sse = self._ring(log).cpu().numpy()
+        with np.errstate(divide='ignore', invalid='ignore'):
+            return np.around(10 * np.log10(1.0 / (sse / self.b.N)), 2)
+
     def objective_log(self):
         """[prox evaluations][B] float64: f of the iterate every logged prox returned, in chronological order, read back once; the
         rows are those of `psnr_trace` (when more than n_log evaluations were logged, the last n_log of them).  Needs an engine made
@@ -120,6 +110,26 @@ class LoopEngine:
         if not self.log_objective:
             raise ValueError('objective_log() needs an engine made with log_objective=True')
         return self._ring(self.obj_log).cpu().numpy()
+
+    def _launched(self, steps, rows):
+        """The counters after a launch (or a graph replay) that ran `steps` inner iterations and logged `rows` prox evaluations."""
+        self.s += steps
+        self.n_prox += rows
+        if hasattr(self.prox, 't'):                             # (DnCNNProx keeps no call count)
+            self.prox.t += rows
+
+    def _run_steps(self, n):
+        """`run_span(n)` where no span kernel applies: n eager steps."""
+        for _ in range(n):
+            self.step()
+
+    def _fused_call(self, call, args, out, sse_out, **kw):
+        """The envelope of every one-kernel call: plan method `call` on `args`, its result in `out`.  A prox inside the kernel
+        writes its squared errors straight to the log row `sse_out`; one that is not (DnCNN, the 2-D wavelet prox) follows the
+        kernel through `after_fused`."""
+        b, px = self.b, self.prox
+        call(*args, out=out, denoise=_fused_kind(px), xrec=b.xrec, sse=sse_out if px.fused_denoise else None, **kw, **px.fused_args())
+        px.after_fused(out, b.xrec, sse_out)
 
     def _capture_graph(self, body, state):
         """`body` (the launches of one outer iteration) captured into a hipGraph (torch.cuda.CUDAGraph on ROCm): a warm-up pass on a
@@ -148,17 +158,11 @@ class LoopEngine:
     def psnr_trace(self):
         """[prox evaluations][B] PSNR (rounded to 0.01 dB like problems/problem.py:33-35) in chronological order,
         read back once; when more than n_log evaluations were logged, the last n_log of them."""
-        n = min(self.n_prox, self.n_log)
-        log = self.sse_log[:n]
-        if self.n_prox > self.n_log:
-            log = torch.roll(self.sse_log, -(self.n_prox % self.n_log), 0)     # oldest surviving row first
-        sse = log.cpu().numpy()
-        with np.errstate(divide='ignore'):
-            return np.around(10 * np.log10(1.0 / (sse / self.b.N)), 2)
+        return self._psnr(self.sse_log)
 
 
-def _check_fused(name, batch, prox, log_objective):
-    """What `fused=True` of GdEngine, SgdEngine and SagaEngine needs, every missing piece named."""
+def _fused_missing(batch, prox, log_objective):
+    """What the one-kernel forms need and this batch, prox or log does not give: every missing piece, named."""
     missing = []
     if getattr(batch, 'kind', None) != 'csmri':
         missing.append(f'a CsmriBatch (got {getattr(batch, "kind", type(batch).__name__)!r})')
@@ -171,21 +175,18 @@ def _check_fused(name, batch, prox, log_objective):
         missing.append(f'a prox with fused_args: TVProx or DnCNNProx (got {type(prox).__name__})')
     if log_objective:
         missing.append('log_objective=False')
+    return missing
+
+
+def _check_fused(name, batch, prox, log_objective):
+    """`fused=True` of GdEngine, SgdEngine, SagaEngine and SarahEngine: refused with everything that is missing."""
+    missing = _fused_missing(batch, prox, log_objective)
     if missing:
         raise ValueError(f'{name}(fused=True) needs ' + ', '.join(missing))
 
 
 class _FusedStep:
-    """The one-kernel inner iteration shared by GdEngine, SgdEngine and SagaEngine (fused=True): the selector bits of a slot, and the
-    bookkeeping around the ONE call -- the squared errors go straight to this evaluation's row of the log, a prox that is not inside
-    the kernel (DnCNN, the 2-D wavelet prox) follows it through `after_fused`."""
-    _hostbits = None
-
-    def _slot_bits(self, j):
-        if self.mbs.host[j] is not None:                        # host-drawn selector: pack it to bits (a 5 us launch)
-            self._hostbits = self.b.plan.pack_mask(self.mbs.host[j], out=self._hostbits)
-            return self._hostbits
-        return self.mbs.selbits[j]
+    """The one-kernel inner iteration of GdEngine, SgdEngine and SagaEngine (fused=True) and their span kernels."""
 
     def span_kernel_ok(self):
         """Whether `run_span` can run its steps as launches of a span kernel (pnp_csmri_grad_span / pnp_csmri_saga_span): the
@@ -195,18 +196,8 @@ class _FusedStep:
         return (self.fused and getattr(self.prox, 'fused_denoise', False) and not _in_kernel_2d(self.prox)
                 and getattr(self.prox, 'denoise_strength', 0.0) == 0.0 and (mbs is None or all(h is None for h in mbs.host)) and not self.log_objective and self.lr_decay == 1.0)
 
-    def _span_done(self, m):
-        """The bookkeeping of m steps run inside one launch."""
-        self.s += m
-        self.n_prox += m
-        self.prox.t += m
-
     def _one_kernel(self, call, *args, **kw):
-        b, px = self.b, self.prox
-        sse_out = self.sse_log[self.n_prox % self.n_log]
-        den = px.fused_denoise
-        call(*args, out=self.z, denoise=_fused_kind(px), xrec=b.xrec, sse=sse_out if den else None, **kw, **px.fused_args())
-        px.after_fused(self.z, b.xrec, sse_out)
+        self._fused_call(call, args, self.z, self.sse_log[self.n_prox % self.n_log], **kw)
         self.n_prox += 1
 
 
@@ -251,34 +242,29 @@ class GdEngine(_FusedStep, LoopEngine):
         each, in which the workgroup that owns a problem runs its steps back to back -- the same bits as stepping; otherwise n
         eager steps."""
         if not self.span_kernel_ok():
-            for _ in range(n):
-                self.step()
-            return
+            return self._run_steps(n)
         b, px = self.b, self.prox
         while n > 0:
             m = min(n, self.AHEAD)
             lr = self.eta * self.lr_decay ** self.s             # (span_kernel_ok: lr_decay == 1)
             b.plan.grad_span(self.z, b.bits, m, b.xrec, self.sse_log, self.n_prox % self.n_log, px.sig, yh=b.yh_full,
                              alpha=self._c('-lr', self.s, -lr), alpha_vec=b.inv_m0, beta=1.0, sigma_modifier=px.sigma_modifier)
-            self._span_done(m)
+            self._launched(m, m)
             n -= m
 
 
-def _t2_vector(batch, T2, span, ahead):
-    """A per-problem T2 checked on the host (the kernels cannot): -> (the [B] int64 vector, the draw window `span`).  Shared by
-    SvrgEngine and SarahEngine; every refusal names the offender."""
-    t2 = np.asarray(T2)
+def _int_vector(batch, name, values):
+    """A per-problem integer hyper-parameter (`T2`, `hist_size`) checked on the host (the kernels cannot): -> the [B] int64 vector.
+    Every refusal names the offender."""
+    v = np.asarray(values)
     if not batch.per_problem:
-        raise ValueError(f'per-problem T2 needs a batch that takes per-problem values (got {batch.kind!r})')
-    if t2.shape != (batch.B,) or not np.issubdtype(t2.dtype, np.integer):
-        raise ValueError(f'per-problem T2: {batch.B} integers, got shape {t2.shape} of {t2.dtype}')
-    bad = np.flatnonzero((t2 < 1) | (t2 > np.iinfo(np.int32).max))
+        raise ValueError(f'per-problem {name} needs a batch that takes per-problem values (got {batch.kind!r})')
+    if v.shape != (batch.B,) or not np.issubdtype(v.dtype, np.integer):
+        raise ValueError(f'per-problem {name}: {batch.B} integers, got shape {v.shape} of {v.dtype}')
+    bad = np.flatnonzero((v < 1) | (v > np.iinfo(np.int32).max))
     if bad.size:
-        raise ValueError(f'per-problem T2: entries must be >= 1 (problem {int(bad[0])}: T2 {int(t2[bad[0]])})')
-    n = int(ahead if span is None else span)
-    if n < 1:
-        raise ValueError(f'span: at least one step per draw window, got {span}')
-    return np.ascontiguousarray(t2, np.int64), n
+        raise ValueError(f'per-problem {name}: entries must be >= 1 (problem {int(bad[0])}: {name} {int(v[bad[0]])})')
+    return np.ascontiguousarray(v, np.int64)
 
 
 class _StochEngine(LoopEngine):
@@ -308,7 +294,14 @@ class _StochEngine(LoopEngine):
         self._window = n_slots is None                          # one draw launch per AHEAD steps (else: the subclass draws)
         self.mbs = batch.minibatches(self.AHEAD if n_slots is None else n_slots)
         self._drawn_base = None                                 # first step of the window the slots currently hold
-        self._drawn_n = 0                                       # per-problem T2: the slots hold steps [_drawn_base, _drawn_base + _drawn_n)
+        self._hostbits = None                                   # one-kernel forms: the packed bits of a host-fed slot
+
+    def _slot_bits(self, j):
+        """The selector bits of slot j as the one-kernel forms take them."""
+        if self.mbs.host[j] is not None:                        # host-drawn selector: pack it to bits (a 5 us launch)
+            self._hostbits = self.b.plan.pack_mask(self.mbs.host[j], out=self._hostbits)
+            return self._hostbits
+        return self.mbs.selbits[j]
 
     def _minibatch(self, idx_s, step_id):
         """Bind a slot to this step's minibatch and return it: host index lists when given (slot 0), else a device draw."""
@@ -330,31 +323,55 @@ class _StochEngine(LoopEngine):
         self.b.draw(self.mbs.slot(slot), self._mb_draw, self.seed, step_id, 1, **self._draw_kw)
         self.mbs.host[slot] = None
 
-    # ---- per-problem T2 (SvrgEngine, SarahEngine): self.T2 a [B] int64 vector, self.span the draw window
+
+class _T2PerProblem:
+    """Per-problem T2 of SvrgEngine and SarahEngine, mixed into exactly those two: T2 as a [B] int64 vector and
+    its int32 device vector `_t2_dev` (None with a scalar T2), and the draw slots as a window of `span` steps drawn with the absolute
+    step ids: the slots hold steps [_drawn_base, _drawn_base + _drawn_n)."""
+    _t2_dev = None
+    _drawn_n = 0
+
+    def _init_t2(self, batch, T2, span):
+        """Before the base constructor (the window is its slot count): T2 as given, or as the checked vector.  -> whether T2 is
+        per problem."""
+        self.T2 = T2
+        if np.ndim(T2) == 0:
+            return False
+        self.T2 = _int_vector(batch, 'T2', T2)
+        self.span = int(self.AHEAD if span is None else span)
+        if self.span < 1:
+            raise ValueError(f'span: at least one step per draw window, got {span}')
+        self._t2_dev = torch.from_numpy(self.T2.astype(np.int32)).to(batch.xrec.device)
+        return True
+
     def refreshes(self, s):
-        """Per-problem T2 (SvrgEngine, SarahEngine): whether any problem refreshes at step s (the host knows s and the vector)."""
+        """Whether any problem refreshes at step s (the host knows s and the vector)."""
         return bool((s % self.T2 == 0).any())
 
     def _lr_pp(self, s):
-        """Per-problem T2: (step sizes, decay exponents k_b = s // T2_b) of step s.  Each step size is the product the scalar engine
-        forms from problem b's values, eta_b * lr_decay ** k_b in Python floats; lr_decay == 1 leaves eta as it was given."""
+        """(step sizes, decay exponents k_b = s // T2_b) of step s.  Each step size is the product the scalar engine forms from
+        problem b's values, eta_b * lr_decay ** k_b in Python floats; lr_decay == 1 leaves eta as it was given."""
         k = s // self.T2
         if self.lr_decay == 1.0:
             return self.eta, k
         eta = np.broadcast_to(np.asarray(self.eta, np.float64), k.shape)
         return np.array([float(e) * self.lr_decay ** int(kb) for e, kb in zip(eta, k)], np.float64), k
 
-    def _slot_pp(self, idx_s, s):
-        """Per-problem T2: the slot that holds step s's minibatch -- a window of `span` steps from s on, drawn with the absolute step
-        ids when s is outside the window the slots hold; host index lists go to slot 0."""
+    def _draw_span(self, m):
+        """Draw the window of the m steps from self.s on."""
+        self.b.draw(self.mbs, self._mb_draw, self.seed, self.s, m, **self._draw_kw)
+        self._drawn_base, self._drawn_n = self.s, m
+
+    def _slot_pp(self, idx_s):
+        """The slot that holds this step's minibatch -- a new window of `span` steps when the step is outside the one the slots
+        hold; host index lists go to slot 0."""
         if idx_s is not None:
             self.b.set_host(self.mbs, 0, idx_s)
             self._drawn_base = None
             return 0
-        if self._drawn_base is None or not self._drawn_base <= s < self._drawn_base + self._drawn_n:
-            self.b.draw(self.mbs, self._mb_draw, self.seed, s, self.span, **self._draw_kw)
-            self._drawn_base, self._drawn_n = s, self.span
-        return s - self._drawn_base
+        if self._drawn_base is None or not self._drawn_base <= self.s < self._drawn_base + self._drawn_n:
+            self._draw_span(self.span)
+        return self.s - self._drawn_base
 
 
 class SgdEngine(_FusedStep, _StochEngine):
@@ -387,9 +404,7 @@ class SgdEngine(_FusedStep, _StochEngine):
         the absolute step id plus ONE pnp_csmri_grad_span each, in which the workgroup that owns a problem runs its steps back to
         back -- the same bits as stepping; otherwise n eager steps."""
         if not self.span_kernel_ok():
-            for _ in range(n):
-                self.step()
-            return
+            return self._run_steps(n)
         b, px = self.b, self.prox
         while n > 0:
             m = min(n, self.AHEAD)
@@ -398,11 +413,11 @@ class SgdEngine(_FusedStep, _StochEngine):
             lr = self.eta * self.lr_decay ** self.s             # (span_kernel_ok: lr_decay == 1)
             b.plan.grad_span(self.z, self.mbs.selbits, m, b.xrec, self.sse_log, self.n_prox % self.n_log, px.sig, YT=b.YT,
                              alpha=self._c('-lr/mb', self.s, -lr / self.mb), beta=1.0, sigma_modifier=px.sigma_modifier)
-            self._span_done(m)
+            self._launched(m, m)
             n -= m
 
 
-class SvrgEngine(_StochEngine):
+class SvrgEngine(_T2PerProblem, _StochEngine):
     """pnp_svrg over a batch.  variant='svrg' is the true direction (pnp_svrg.py:53), 'reference' is what v1
     executes (v = mu, :54).  `step()` = one inner iteration (the outer full-gradient refresh happens inside when
     s % T2 == 0, as in the reference's loop nest).  Device draws of a whole outer iteration are ONE launch at the
@@ -416,30 +431,22 @@ class SvrgEngine(_StochEngine):
 
     def __init__(self, batch, prox, eta, T2, mini_batch_size, lr_decay=1.0, variant='svrg', n_log=4096, seed=0, fused=None,
                  fold_outer=True, draw_id=None, span=None, log_objective=False):
-        t2 = None
-        if np.ndim(T2) != 0:                                    # per-problem T2: checked on the host (the kernels cannot)
-            t2, n_span = _t2_vector(batch, T2, span, self.AHEAD)
-            T2, self.span = t2, n_span
-        elif span is not None:
+        if np.ndim(T2) == 0 and span is not None:
             raise ValueError('span is the draw window of a per-problem T2; a scalar T2 draws an outer iteration at a time')
-        super().__init__(batch, prox, eta, mini_batch_size, lr_decay, n_log, seed, n_slots=T2 if t2 is None else self.span, draw_id=draw_id,
+        pp = self._init_t2(batch, T2, span)
+        super().__init__(batch, prox, eta, mini_batch_size, lr_decay, n_log, seed, n_slots=self.span if pp else T2, draw_id=draw_id,
                          log_objective=log_objective)
-        self.T2, self.variant = T2, variant
-        self._t2_dev = self._mu_new = None                      # per-problem T2: its int32 device vector, the refresh's scratch
-        if t2 is not None:
-            self._t2_dev = torch.from_numpy(T2.astype(np.int32)).to(batch.xrec.device)
-            self._mu_new = torch.empty_like(self.z)
+        self.variant = variant
+        self._mu_new = torch.empty_like(self.z) if pp else None     # per-problem T2: the refresh's scratch
         # the one-kernel inner iteration (csrc/csmri_fused.hip): CSMRI, f32, 256 x 256, true SVRG direction, a prox that
         # can follow it (TV inside the kernel, DnCNN after it)
-        ok = (batch.kind == 'csmri' and batch.dtype == torch.float32 and batch.H == 256 and batch.W == 256
-              and variant == 'svrg' and hasattr(prox, 'fused_args'))
+        ok = variant == 'svrg' and not _fused_missing(batch, prox, False)
         if fused and not ok:
             raise ValueError('the one-kernel iteration needs a float32 256 x 256 CsmriBatch, variant="svrg" and a TV or DnCNN prox')
         # one workgroup per image: it pays off from about a workgroup per CU (measured: B = 120 is slower than the
         # streaming kernels, B = 256 faster), so small batches keep the four streaming kernels unless asked otherwise
         self.fused = (ok and batch.B >= self.FUSED_MIN_BATCH) if fused is None else bool(fused)
         self.fold_outer = fold_outer                            # False: refresh as launches of its own (A/B, tests)
-        self._hostbits = None
         dev = batch.xrec.device
         self.w = torch.empty_like(self.z)
         self.mu = torch.empty_like(self.z)
@@ -457,41 +464,42 @@ class SvrgEngine(_StochEngine):
     def step(self, idx_s=None):
         """One inner iteration for all B problems.  idx_s: int32 [B][mb] minibatch index lists (e.g. drawn from
         NumPy's legacy stream for reference-identical runs); None = device draws."""
-        if self._t2_dev is not None:
-            return self._step_pp(idx_s)
         b, s = self.b, self.s
-        j, k = s % self.T2, s // self.T2
-        if j == 0:                                              # outer: mu = grad_full(z); w = z
-            if self.variant == 'svrg' and idx_s is None:
-                b.draw(self.mbs, self._mb_draw, self.seed, s, self.T2, **self._draw_kw)
-            if not (self.fused and self.fold_outer):            # (folded: the first inner iteration's kernel does it)
-                b.grad_full(self.z, out=self.mu)
-                self.w.copy_(self.z)
-        if self.variant == 'svrg':
-            if idx_s is not None:                               # (at a folded j = 0 the minibatch is bound but cannot matter)
-                b.set_host(self.mbs, j, idx_s)
-            elif self.mbs.host[j] is not None:                  # a host-fed outer iteration continued with device draws
-                self._draw_slot(j, s)
-        self.z = self._inner(j, self.eta * self.lr_decay ** k, k, self.sse_log[self.n_prox % self.n_log])
+        if self._t2_dev is not None:
+            j, (lr, k) = self._refresh_pp(idx_s), self._lr_pp(s)
+        else:
+            j, k = s % self.T2, s // self.T2
+            lr = self.eta * self.lr_decay ** k
+            if j == 0:                                          # outer: mu = grad_full(z); w = z
+                if self.variant == 'svrg' and idx_s is None:
+                    b.draw(self.mbs, self._mb_draw, self.seed, s, self.T2, **self._draw_kw)
+                if not (self.fused and self.fold_outer):        # (folded: the first inner iteration's kernel does it)
+                    b.grad_full(self.z, out=self.mu)
+                    self.w.copy_(self.z)
+            if self.variant == 'svrg':
+                if idx_s is not None:                           # (at a folded j = 0 the minibatch is bound but cannot matter)
+                    b.set_host(self.mbs, j, idx_s)
+                elif self.mbs.host[j] is not None:              # a host-fed outer iteration continued with device draws
+                    self._draw_slot(j, s)
+        row = self.n_prox % self.n_log
+        self.z = self._inner(j, lr, k, self.sse_log[row])
         if self.log_objective:
-            self._log_obj(self.n_prox % self.n_log, self.z)
+            self._log_obj(row, self.z)
         self.n_prox += 1
         self.s += 1                                             # eager steps keep the index on the host (no counter launch)
 
-    def _step_pp(self, idx_s):
-        """`step()` with a per-problem T2: where any problem refreshes, grad_full into the scratch and ONE pnp_refresh_pp; then the
-        ordinary inner iteration for all problems (at a problem's own refresh step w == z: its SVRG difference is exactly zero)."""
-        s = self.s
-        if self.refreshes(s):
+    def _refresh_pp(self, idx_s):
+        """The head of `step()` with a per-problem T2: where any problem refreshes, grad_full into the scratch and ONE
+        pnp_refresh_pp; -> the slot of the ordinary inner iteration that follows for all problems (at a problem's own refresh step
+        w == z: its SVRG difference is exactly zero)."""
+        if self.refreshes(self.s):
             self.b.grad_full(self.z, out=self._mu_new)
-            ops.refresh_pp(self._mu_new, self.z, self.mu, self.w, self._t2_dev, s)
-        j = self._slot_pp(idx_s, s) if self.variant == 'svrg' else 0
-        lr, k = self._lr_pp(s)
-        self.z = self._inner(j, lr, k, self.sse_log[self.n_prox % self.n_log])
-        if self.log_objective:
-            self._log_obj(self.n_prox % self.n_log, self.z)
-        self.n_prox += 1
-        self.s += 1
+            ops.refresh_pp(self._mu_new, self.z, self.mu, self.w, self._t2_dev, self.s)
+        return self._slot_pp(idx_s) if self.variant == 'svrg' else 0
+
+    def _at_outer(self):
+        """Whether the engine stands at the start of an outer iteration."""
+        return self.s % self.T2 == 0 and self.n_prox == self.s
 
     def run_span(self, n):
         """n inner iterations from any step count.  With a per-problem T2, `outer_kernel_ok()` and lr_decay == 1 they run in
@@ -500,20 +508,15 @@ class SvrgEngine(_StochEngine):
         steps."""
         # (pnp_csmri_svrg_span_pp holds the per-column prox only: TVProx(in_kernel=True) steps eagerly here)
         if not (self._t2_dev is not None and self.lr_decay == 1.0 and self.outer_kernel_ok() and not _in_kernel_2d(self.prox)):
-            for _ in range(n):
-                self.step()
-            return
+            return self._run_steps(n)
         b, px = self.b, self.prox
         while n > 0:
             m = min(n, self.span)
-            b.draw(self.mbs, self._mb_draw, self.seed, self.s, m, **self._draw_kw)
-            self._drawn_base, self._drawn_n = self.s, m
+            self._draw_span(m)
             b.plan.svrg_span(self.z, self.w, self.mu, b.bits, b.yh_full, b.inv_m0, self.mbs.selbits, self.s, m, self._t2_dev,
                              self._c('lr', 0, self.eta), self._mb_draw, b.xrec, self.sse_log, self.n_prox % self.n_log, px.sig,
                              sigma_modifier=px.sigma_modifier)
-            self.s += m
-            self.n_prox += m
-            px.t += m
+            self._launched(m, m)
             n -= m
 
     def _inner(self, j, lr, k, sse_out):
@@ -541,22 +544,13 @@ class SvrgEngine(_StochEngine):
 
     def _fused_outer(self, lr, sse_out, k):
         """outer refresh (mu = grad_full(z), w = z) + inner iteration 0 in one kernel (pnp_csmri_svrg_outer_step)."""
-        b, px = self.b, self.prox
-        b.plan.svrg_outer_step(self.z, b.bits, b.yh_full, b.inv_m0, self._c('lr', k, lr), self.w, self.mu, out=self.z,
-                               denoise=_fused_kind(px), xrec=b.xrec, sse=sse_out if px.fused_denoise else None, **px.fused_args())
-        px.after_fused(self.z, b.xrec, sse_out)
+        b = self.b
+        self._fused_call(b.plan.svrg_outer_step, (self.z, b.bits, b.yh_full, b.inv_m0, self._c('lr', k, lr), self.w, self.mu), self.z, sse_out)
 
     def _fused_inner(self, j, lr, sse_out, k):
         """step + estimate_sigma + prox + error of inner iteration j in one kernel (TV), or in one kernel + the network."""
-        b, px = self.b, self.prox
-        if self.mbs.host[j] is not None:                        # host-drawn selector: pack it to bits (a 5 us launch)
-            self._hostbits = b.plan.pack_mask(self.mbs.host[j], out=self._hostbits)
-            bits = self._hostbits
-        else:
-            bits = self.mbs.selbits[j]
-        b.plan.svrg_step(self.z, self.w, bits, alpha=self._c('-lr/mb', k, -lr / self.mb), beta=1.0, c1=self.z,
-                         gamma=self._c('-lr', k, -lr), c2=self.mu, out=self.z, denoise=_fused_kind(px), xrec=b.xrec, sse=sse_out if px.fused_denoise else None, **px.fused_args())
-        px.after_fused(self.z, b.xrec, sse_out)
+        self._fused_call(self.b.plan.svrg_step, (self.z, self.w, self._slot_bits(j)), self.z, sse_out,
+                         alpha=self._c('-lr/mb', k, -lr / self.mb), beta=1.0, c1=self.z, gamma=self._c('-lr', k, -lr), c2=self.mu)
 
     # ---- hipGraph form: one OUTER iteration (full-gradient refresh + T2 inner iterations) = one graph launch
     def _outer_body(self):
@@ -585,7 +579,7 @@ class SvrgEngine(_StochEngine):
         if not self.graph_ok():
             raise ValueError('this engine cannot be captured in a hipGraph (needs lr_decay == 1 and an in-place prox without '
                              'host-side per-call state: TVProx with denoise_strength == 0 or DnCNNProx); step it eagerly')
-        if not (self.s % self.T2 == 0 and self.n_prox == self.s):
+        if not self._at_outer():
             raise ValueError('capture() needs a step count that is a multiple of T2')
         self._set_dev_step(self.s)
         state = (self.z, self.w, self.mu, self.sse_log, self.step_dev)
@@ -619,7 +613,7 @@ class SvrgEngine(_StochEngine):
         if one_launch is None:
             one_launch = self.outer_kernel_ok()
         if one_launch:
-            if not self.outer_kernel_ok() or self.s % self.T2 != 0 or self.n_prox != self.s:
+            if not (self.outer_kernel_ok() and self._at_outer()):
                 raise ValueError('one launch per outer iteration needs the one-kernel iteration with the TV prox, the folded '
                                  'refresh, device-drawn minibatches and a step count that is a multiple of T2')
             b, px = self.b, self.prox
@@ -629,23 +623,18 @@ class SvrgEngine(_StochEngine):
                 b.plan.svrg_outer_iteration(self.z, self.w, self.mu, b.bits, b.yh_full, b.inv_m0, self.mbs.selbits, self.T2,
                                             self._c('lr', self.s // self.T2, lr), self._mb_draw, b.xrec, self.sse_log, self.n_prox % self.n_log, px.sig, sigma_modifier=px.sigma_modifier,
                                             prox_kind=_fused_kind(px))
-                self.s += self.T2
-                self.n_prox += self.T2
-                px.t += self.T2
+                self._launched(self.T2, self.T2)
             return
         if self.graph is None:
             self.capture()
         self._set_dev_step(self.s)
         for _ in range(n_outer):
             self.graph.replay()
-            self.s += self.T2
-            self.n_prox += self.T2
-            if hasattr(self.prox, 't'):
-                self.prox.t += self.T2
+            self._launched(self.T2, self.T2)
         self._dev_step = self.s
 
 
-class SarahEngine(_StochEngine):
+class SarahEngine(_T2PerProblem, _StochEngine):
     """pnp_sarah over a batch (algorithms/pnp_sarah.py:28-104) with the quirks of v1: the outer step
     `w_next = prox(w_prev - eta * grad_full(z))` is logged but never adopted by z, w_next stays fixed through the
     inner loop, and the outer step ignores lr_decay.  One log row per prox: outer rows at s % T2 == 0.
@@ -665,12 +654,17 @@ class SarahEngine(_StochEngine):
 
     def __init__(self, batch, prox, eta, T2, mini_batch_size, lr_decay=1.0, n_log=4096, seed=0, draw_id=None, log_objective=False,
                  *, fused=False, split_log=False, span=None):
-        t2 = None
         if np.ndim(T2) != 0:
             if not split_log:
                 raise ValueError('SarahEngine takes a scalar T2 (its outer prox logs a row of its own: rows would stop lining up) '
                                  'unless split_log=True gives the outer rows a ring of their own')
-            t2, self.span = _t2_vector(batch, T2, span, self.AHEAD)
+        elif split_log:
+            raise ValueError('split_log=True is the log layout of a per-problem T2 ([B] integers); a scalar T2 keeps the single log')
+        elif span is not None:
+            raise ValueError('span is the draw window of a per-problem T2; a scalar T2 draws a window of AHEAD steps (an outer '
+                             'iteration with fused=True)')
+        pp = self._init_t2(batch, T2, span)
+        if pp:
             if log_objective:
                 raise ValueError('SarahEngine with a per-problem T2 does not log the objective (log_objective=True): the objective '
                                  'ring is laid out row for row with the single log of a scalar T2')
@@ -678,41 +672,20 @@ class SarahEngine(_StochEngine):
                 raise ValueError('SarahEngine with a per-problem T2 needs a prox whose result does not depend on its call count '
                                  '(denoise_strength != 0 with decay != 1 does): the problems would have made different numbers of '
                                  'prox calls')
-            T2 = t2
-        elif split_log:
-            raise ValueError('split_log=True is the log layout of a per-problem T2 ([B] integers); a scalar T2 keeps the single log')
-        elif span is not None:
-            raise ValueError('span is the draw window of a per-problem T2; a scalar T2 draws a window of AHEAD steps (an outer '
-                             'iteration with fused=True)')
         self.fused = bool(fused)
         if self.fused:
-            missing = []
-            if getattr(batch, 'kind', None) != 'csmri':
-                missing.append(f'a CsmriBatch (got {getattr(batch, "kind", type(batch).__name__)!r})')
-            else:
-                if batch.dtype != torch.float32:
-                    missing.append(f'float32 (got {batch.dtype})')
-                if (batch.H, batch.W) != (256, 256):
-                    missing.append(f'256 x 256 images (got {batch.H} x {batch.W})')
-            if not hasattr(prox, 'fused_args'):
-                missing.append(f'a prox with fused_args: TVProx or DnCNNProx (got {type(prox).__name__})')
-            if log_objective:
-                missing.append('log_objective=False')
-            if missing:
-                raise ValueError('SarahEngine(fused=True) needs ' + ', '.join(missing))
+            _check_fused('SarahEngine', batch, prox, log_objective)
         # fused: the draws of a whole outer iteration are ONE launch at the outer step (T2 selector slots, as SvrgEngine)
         super().__init__(batch, prox, eta, mini_batch_size, lr_decay, n_log, seed,
-                         n_slots=self.span if t2 is not None else T2 if self.fused else None, draw_id=draw_id, log_objective=log_objective)
-        self.T2 = T2
+                         n_slots=self.span if pp else T2 if self.fused else None, draw_id=draw_id, log_objective=log_objective)
         self.w_prev = torch.empty_like(self.z)
         self.w_next = torch.empty_like(self.z)
         self.v_prev = torch.empty_like(self.z)
-        self._t2_dev = self.outer_log = None
-        if t2 is not None:
-            # per-problem T2: the int32 device vector, the second ring, and the scratch of the whole-batch outer step (the full
-            # gradient, the stepped image the prox runs on, the kernel's w_out with fused=True, the row of its squared errors)
+        self.outer_log = None
+        if pp:
+            # per-problem T2: the second ring, and the scratch of the whole-batch outer step (the full gradient, the stepped image
+            # the prox runs on, the kernel's w_out with fused=True, the row of its squared errors)
             dev = batch.xrec.device
-            self._t2_dev = torch.from_numpy(T2.astype(np.int32)).to(dev)
             self.outer_log = torch.full((n_log, batch.B), float('nan'), dtype=torch.float64, device=dev)
             self._outer_dirty = np.zeros(n_log, bool)           # rows of outer_log that hold a value of some problem
             self._v_new = torch.empty_like(self.z)
@@ -722,7 +695,6 @@ class SarahEngine(_StochEngine):
         if not self.fused:
             self.v_next = torch.empty_like(self.z)
             return
-        self._hostbits = None
         dev = batch.xrec.device
         # the hipGraph form's device-resident counters and scratch row (as SvrgEngine's).  Two counters: the draws are keyed on the
         # step count, the log on the row count -- an outer iteration appends T2 + 1 rows (log_append_inc: append and count, one launch)
@@ -754,16 +726,27 @@ class SarahEngine(_StochEngine):
             # (F6: no lr_decay here -- '-eta' is a coefficient of its own, made once whatever the decay exponent)
             ops.axpbypcz(1.0, self.w_prev, self._c('-eta', 0, -self.eta), self.v_prev, out=self.w_next)
             self.w_next = self._prox(self.w_next)
-        j = self._minibatch(idx_s, s)
-        b.grad_stoch_diff(self.w_next, self.w_prev, self.mbs, j, out=self.v_next, alpha=self._c('1/mb', 0, 1.0 / self.mb), beta=1.0,
-                          c1=self.v_prev)
         k = s // self.T2
-        lr = self.eta * self.lr_decay ** k
-        ops.axpbypcz(1.0, self.z, self._c('-lr', k, -lr), self.v_next, out=self.z)
-        self.z = self._prox(self.z)
-        self.v_prev, self.v_next = self.v_next, self.v_prev
-        self.w_prev.copy_(self.z)
+        self._inner(self._minibatch(idx_s, s), self.eta * self.lr_decay ** k, k)
+
+    def _inner(self, j, lr, k):
+        """The inner iteration on slot j (step size lr, decay exponent k), logged in the next row of sse_log: ONE pnp_csmri_sarah_step,
+        or the difference of minibatch gradients, the step, the prox, the buffer swap and the copy w_prev <- z."""
+        if self.fused:
+            self._fused_inner(j, lr, k, self.sse_log[self.n_prox % self.n_log])
+            self.n_prox += 1
+        else:
+            self.b.grad_stoch_diff(self.w_next, self.w_prev, self.mbs, j, out=self.v_next, alpha=self._c('1/mb', 0, 1.0 / self.mb),
+                                   beta=1.0, c1=self.v_prev)
+            ops.axpbypcz(1.0, self.z, self._c('-lr', k, -lr), self.v_next, out=self.z)
+            self.z = self._prox(self.z)
+            self.v_prev, self.v_next = self.v_next, self.v_prev
+            self.w_prev.copy_(self.z)
         self.s += 1
+
+    def _at_outer(self):
+        """Whether the engine stands at the start of an outer iteration: a multiple of T2 steps, each outer iteration T2 + 1 rows."""
+        return self.s % self.T2 == 0 and self.n_prox == self.s + self.s // self.T2
 
     # ---- per-problem T2 (split_log=True, DESIGN 9.11)
     def _outer_row(self, s, refresh):
@@ -786,12 +769,7 @@ class SarahEngine(_StochEngine):
         row = self._outer_row(s, refresh)
         if refresh:
             if self.fused:
-                den = px.fused_denoise
-                b.plan.svrg_outer_step(self.z, b.bits, b.yh_full, b.inv_m0, self._c('eta', 0, self.eta), self._w_scr, self._v_new,
-                                       out=self._tmp, denoise=_fused_kind(px), xrec=b.xrec, sse=self.sse_tmp if den else None,
-                                       **px.fused_args())
-                px.after_fused(self._tmp, b.xrec, self.sse_tmp)
-                res = self._tmp
+                res = self._fused_outer(self._w_scr, self._v_new, self._tmp, self.sse_tmp)
             else:
                 b.grad_full(self.z, out=self._v_new)
             ops.refresh_pp(self._v_new, self.z, self.v_prev, self.w_prev, self._t2_dev, s)
@@ -801,20 +779,7 @@ class SarahEngine(_StochEngine):
                 res = px(self._tmp, b.xrec, self.sse_tmp)
             ops.select_pp(res, self.w_next, self._t2_dev, s, self.sse_tmp, row)
             self._tmp = res                                     # (a prox that ping-pongs hands back the buffer that is free now)
-        j = self._slot_pp(idx_s, s)
-        lr, k = self._lr_pp(s)
-        sse_out = self.sse_log[s % self.n_log]
-        if self.fused:
-            self._fused_inner(j, lr, k, sse_out)
-        else:
-            b.grad_stoch_diff(self.w_next, self.w_prev, self.mbs, j, out=self.v_next, alpha=self._c('1/mb', 0, 1.0 / self.mb), beta=1.0,
-                              c1=self.v_prev)
-            ops.axpbypcz(1.0, self.z, self._c('-lr', k, -lr), self.v_next, out=self.z)
-            self.z = px(self.z, b.xrec, sse_out)
-            self.v_prev, self.v_next = self.v_next, self.v_prev
-            self.w_prev.copy_(self.z)
-        self.n_prox += 1
-        self.s += 1
+        self._inner(self._slot_pp(idx_s), *self._lr_pp(s))      # (n_prox == s: the inner row of step s is row s % n_log)
 
     def run_span(self, n):
         """n inner iterations from any step count.  With a per-problem T2, `outer_kernel_ok()` and lr_decay == 1 they run in
@@ -822,31 +787,24 @@ class SarahEngine(_StochEngine):
         a problem runs its steps back to back and takes its outer step where its own T2 says -- the same bits as stepping;
         otherwise eager steps (TVProx(in_kernel=True) among them: the span kernel holds the per-column prox only)."""
         if not (self._t2_dev is not None and self.lr_decay == 1.0 and self.outer_kernel_ok()):
-            for _ in range(n):
-                self.step()
-            return
+            return self._run_steps(n)
         b, px = self.b, self.prox
         while n > 0:
             m = min(n, self.span)
-            b.draw(self.mbs, self._mb_draw, self.seed, self.s, m, **self._draw_kw)
-            self._drawn_base, self._drawn_n = self.s, m
+            self._draw_span(m)
             eta = self._c('eta', 0, self.eta)                   # (lr_decay == 1: the inner step size is eta as well)
             b.plan.sarah_span(self.z, self.w_prev, self.w_next, self.v_prev, b.bits, b.yh_full, b.inv_m0, self.mbs.selbits, self.s, m,
                               self._t2_dev, eta, eta, self._mb_draw, b.xrec, self.sse_log, self.outer_log, self.s % self.n_log, px.sig,
                               sigma_modifier=px.sigma_modifier)
             for s in range(self.s, self.s + m):                 # (the kernel writes every row it passes, NaN included)
                 self._outer_dirty[s % self.n_log] = self.refreshes(s)
-            self.s += m
-            self.n_prox += m
-            px.t += m
+            self._launched(m, m)
             n -= m
 
     def _split_rows(self, log):
         if self._t2_dev is None:
             raise ValueError('the split log is the layout of a per-problem T2 (SarahEngine(T2=[B] ints, split_log=True))')
-        sse = self._ring(log).cpu().numpy()
-        with np.errstate(divide='ignore', invalid='ignore'):
-            return np.around(10 * np.log10(1.0 / (sse / self.b.N)), 2)
+        return self._psnr(log)
 
     def outer_trace(self):
         """Per-problem T2: [steps][B] PSNR of the outer prox problem b made at each step, NaN where it made none; the rows are
@@ -871,46 +829,36 @@ class SarahEngine(_StochEngine):
         if j == 0:
             if idx_s is None:
                 b.draw(self.mbs, self._mb_draw, self.seed, s, self.T2, **self._draw_kw)
-            self._fused_outer(self.sse_log[self.n_prox % self.n_log])
+            self._fused_outer(self.w_prev, self.v_prev, self.w_next, self.sse_log[self.n_prox % self.n_log])
             self.n_prox += 1
         if idx_s is not None:
             b.set_host(self.mbs, j, idx_s)
         elif self.mbs.host[j] is not None:                      # a host-fed outer iteration continued with device draws
             self._draw_slot(j, s)
-        self._fused_inner(j, self.eta * self.lr_decay ** k, k, self.sse_log[self.n_prox % self.n_log])
-        self.n_prox += 1
-        self.s += 1
+        self._inner(j, self.eta * self.lr_decay ** k, k)
 
-    def _fused_outer(self, sse_out):
-        """w_prev = z, v_prev = grad_full(z), w_next = prox(z - eta * v_prev) in one kernel (pnp_csmri_svrg_outer_step with
-        out = w_next); z is not touched (the outer step is logged, never adopted), and eta does not decay here (F6)."""
-        b, px = self.b, self.prox
-        b.plan.svrg_outer_step(self.z, b.bits, b.yh_full, b.inv_m0, self._c('eta', 0, self.eta), self.w_prev, self.v_prev,
-                               out=self.w_next, denoise=_fused_kind(px), xrec=b.xrec, sse=sse_out if px.fused_denoise else None,
-                               **px.fused_args())
-        px.after_fused(self.w_next, b.xrec, sse_out)
+    def _fused_outer(self, w_out, v_out, out, sse_out):
+        """w_out = z, v_out = grad_full(z), out = prox(z - eta * v_out) in one kernel (pnp_csmri_svrg_outer_step): the outer step into
+        w_prev, v_prev and w_next, or into scratch (per-problem T2).  z is not touched (the outer step is logged, never adopted),
+        and eta does not decay here (F6).  -> out"""
+        b = self.b
+        self._fused_call(b.plan.svrg_outer_step, (self.z, b.bits, b.yh_full, b.inv_m0, self._c('eta', 0, self.eta), w_out, v_out), out, sse_out)
+        return out
 
     def _fused_inner(self, j, lr, k, sse_out):
         """v_prev <- v_next, z <- prox(z - lr * v_next), w_prev <- z in one kernel (pnp_csmri_sarah_step), all three in place; with
         a prox that follows the kernel (DnCNN, the 2-D wavelet prox) the copy to w_prev follows the prox."""
-        b, px = self.b, self.prox
-        if self.mbs.host[j] is not None:                        # host-drawn selector: pack it to bits (a 5 us launch)
-            self._hostbits = b.plan.pack_mask(self.mbs.host[j], out=self._hostbits)
-            bits = self._hostbits
-        else:
-            bits = self.mbs.selbits[j]
-        den = px.fused_denoise
-        b.plan.sarah_step(self.w_next, self.w_prev, bits, alpha=self._c('1/mb', 0, 1.0 / self.mb), beta=1.0, c1=self.v_prev,
-                          gamma=self._c('-lr', k, -lr), c2=self.z, v_out=self.v_prev, out=self.z, out2=self.w_prev if den else None,
-                          denoise=_fused_kind(px), xrec=b.xrec, sse=sse_out if den else None, **px.fused_args())
+        den = self.prox.fused_denoise
+        self._fused_call(self.b.plan.sarah_step, (self.w_next, self.w_prev, self._slot_bits(j)), self.z, sse_out,
+                         alpha=self._c('1/mb', 0, 1.0 / self.mb), beta=1.0, c1=self.v_prev, gamma=self._c('-lr', k, -lr), c2=self.z,
+                         v_out=self.v_prev, out2=self.w_prev if den else None)
         if not den:
-            px.after_fused(self.z, b.xrec, sse_out)
             self.w_prev.copy_(self.z)
 
     # ---- hipGraph form of the fused path: one OUTER iteration (outer step + T2 inner iterations, T2 + 1 log rows) = one graph launch
     def _outer_body(self):
         b = self.b
-        self._fused_outer(self.sse_tmp)
+        self._fused_outer(self.w_prev, self.v_prev, self.w_next, self.sse_tmp)
         ops.log_append_inc(self.sse_tmp, self.sse_log, self.row_dev)
         b.draw(self.mbs, self._mb_draw, self.seed, 0, self.T2, step_dev=self.step_dev, **self._draw_kw)
         for j in range(self.T2):
@@ -935,7 +883,7 @@ class SarahEngine(_StochEngine):
             raise ValueError('this SarahEngine cannot be captured in a hipGraph (needs fused=True, lr_decay == 1, device-drawn '
                              'minibatches and an in-place prox without host-side per-call state: TVProx with denoise_strength == 0 '
                              'or DnCNNProx); step it eagerly')
-        if not (self.s % self.T2 == 0 and self.n_prox == self.s + self.s // self.T2):
+        if not self._at_outer():
             raise ValueError('capture() needs a step count that is a multiple of T2')
         self._set_dev_step()
         g = self._capture_graph(self._outer_body, (self.z, self.w_prev, self.w_next, self.v_prev, self.sse_log, self.row_dev, self.step_dev))
@@ -980,7 +928,7 @@ class SarahEngine(_StochEngine):
             raise ValueError('run_outer: with a per-problem T2 the batch has no common outer iteration; use run_span(n_steps)')
         if one_launch:
             missing = self._outer_kernel_missing()
-            if not (self.s % self.T2 == 0 and self.n_prox == self.s + self.s // self.T2):
+            if not self._at_outer():
                 missing.append(f'a step count that is a multiple of T2 (s = {self.s}, T2 = {self.T2})')
             if missing:
                 raise ValueError('run_outer(one_launch=True) needs ' + ', '.join(missing))
@@ -993,21 +941,16 @@ class SarahEngine(_StochEngine):
                                              self.mbs.selbits, self.T2, self._c('eta', 0, self.eta), self._c('lr', k, lr),
                                              self._mb_draw, b.xrec, self.sse_log, self.n_prox % self.n_log, px.sig,
                                              sigma_modifier=px.sigma_modifier)
-                self.s += self.T2
-                self.n_prox += self.T2 + 1
-                px.t += self.T2 + 1
+                self._launched(self.T2, self.T2 + 1)
             return
         if self.graph is None:
             self.capture()
-        if not (self.s % self.T2 == 0 and self.n_prox == self.s + self.s // self.T2):
+        if not self._at_outer():
             raise ValueError('run_outer() needs a step count that is a multiple of T2')
         self._set_dev_step()
         for _ in range(n_outer):
             self.graph.replay()
-            self.s += self.T2
-            self.n_prox += self.T2 + 1
-            if hasattr(self.prox, 't'):
-                self.prox.t += self.T2 + 1
+            self._launched(self.T2, self.T2 + 1)
         self._dev_step = self.s
 
 
@@ -1040,18 +983,10 @@ class SagaEngine(_FusedStep, _StochEngine):
             _check_fused('SagaEngine', batch, prox, log_objective)
         hv = None
         if np.ndim(hist_size) != 0:                             # per-problem hist_size: checked on the host (the kernels cannot)
-            hv = np.asarray(hist_size)
             if self.fused and _in_kernel_2d(prox):
                 raise ValueError('SagaEngine(fused=True) with a per-problem hist_size: pnp_csmri_saga_step_hist_pp holds the per-column '
                                  'prox only -- use TVProx(multi=False) without in_kernel=True (the 2-D prox then follows the kernel)')
-            if not batch.per_problem:
-                raise ValueError(f'per-problem hist_size needs a batch that takes per-problem values (got {batch.kind!r})')
-            if hv.shape != (batch.B,) or not np.issubdtype(hv.dtype, np.integer):
-                raise ValueError(f'per-problem hist_size: {batch.B} integers, got shape {hv.shape} of {hv.dtype}')
-            bad = np.flatnonzero((hv < 1) | (hv > np.iinfo(np.int32).max))
-            if bad.size:
-                raise ValueError(f'per-problem hist_size: entries must be >= 1 (problem {int(bad[0])}: hist_size {int(hv[bad[0]])})')
-            hv = np.ascontiguousarray(hv, np.int64)
+            hv = _int_vector(batch, 'hist_size', hist_size)
         self._row_cache = {}                                    # fused: one row for the whole batch -> its device vector, made once
         super().__init__(batch, prox, eta, mini_batch_size, lr_decay, n_log, seed, draw_id=draw_id, log_objective=log_objective)
         self.hist = hist_size if hv is None else int(hv.max())  # the table's row count
@@ -1096,34 +1031,35 @@ class SagaEngine(_FusedStep, _StochEngine):
         draws = {h: [int(g.integers(h)) for _ in range(n)] for h, g in self._rngs.items()}
         return np.array([draws[int(h)] for h in self.hist_pp], np.int64).T.reshape(n, self.b.B)
 
-    def _check_rows_pp(self, r):
-        """Per-problem hist_size: rows (a scalar, [B], or [n][B]) as int64 against every problem's own bound [0, hist_size[b])."""
+    def _check_rows(self, r, bound):
+        """Rows against the bound [0, bound) -- `hist`: r as it is, one message for the batch; `hist_pp`: r (a scalar, [B], or
+        [n][B]) as int64 over the problems, each against its own bound, the first offender named.  -> r"""
+        if np.ndim(bound) == 0:
+            if (not 0 <= r < bound) if np.ndim(r) == 0 else (r.min() < 0 or r.max() >= bound):
+                raise ValueError(f'SAGA row outside the table: rows in [0, {bound}), got {np.ravel(r).tolist()}')
+            return r
         r = np.broadcast_to(np.asarray(r, np.int64), np.shape(r)[:-1] + (self.b.B,) if np.ndim(r) else (self.b.B,)).copy()
-        bad = np.argwhere((r < 0) | (r >= self.hist_pp))
+        bad = np.argwhere((r < 0) | (r >= bound))
         if bad.size:
             b = int(bad[0][-1])
-            raise ValueError(f'SAGA row outside the table of problem {b}: rows in [0, {int(self.hist_pp[b])}), got {int(r[tuple(bad[0])])}')
+            raise ValueError(f'SAGA row outside the table of problem {b}: rows in [0, {int(bound[b])}), got {int(r[tuple(bad[0])])}')
         return r
 
     def step(self, idx_s=None, r=None):
         """r: the table row this step replaces -- one value for the whole batch, or one per problem (legacy-seeded sweeps:
         every item follows its own np.random stream, and with masks of different sizes the streams drift apart)."""
         j = self._minibatch(idx_s, self.s)
-        if self.hist_pp is not None:
-            return self._step_hist_pp(j, self._draw_rows_pp(1)[0] if r is None else r)
         if r is None:
-            r = int(self._rng.integers(self.hist))
-        if self.fused:
-            return self._step_fused(j, r)
+            r = self._draw_rows_pp(1)[0] if self.hist_pp is not None else int(self._rng.integers(self.hist))
+        if self.fused or self.hist_pp is not None:
+            return self._step_batched(j, r)
         self.b.grad_stoch(self.z, self.mbs, j, out=self.g, alpha=self._c('1/mb', 0, 1.0 / self.mb))
         lr = self.eta * self.lr_decay ** self.s
         if np.ndim(r) == 0 and np.ndim(self.r_prev) == 0 and np.ndim(lr) == 0:
             r = int(r)
             ops.saga_table_update(self.z, self.g, self.table[r], self.table[self.r_prev], self.tsum, lr, 1.0 / self.hist)
         else:                                                   # per-problem rows or step sizes: ONE launch for the batch
-            r = np.broadcast_to(np.asarray(r, np.int64), (self.b.B,)).copy()
-            if r.min() < 0 or r.max() >= self.hist:
-                raise ValueError(f'SAGA row outside the table: rows in [0, {self.hist}), got {r.tolist()}')
+            r = self._check_rows(np.broadcast_to(np.asarray(r, np.int64), (self.b.B,)).copy(), self.hist)
             prev = self._row_vec(self.r_prev)
             self._rows = (r, self._row_vec(r))
             ops.saga_table_update_pp(self.z, self.g, self.table, self._rows[1], prev, self.tsum, self._c('lr', self.s, lr),
@@ -1132,47 +1068,26 @@ class SagaEngine(_FusedStep, _StochEngine):
         self.z = self._prox(self.z)
         self.s += 1
 
-    def _step_hist_pp(self, j, r):
-        """`step()` with a per-problem hist_size: the rows checked against every problem's own bound, then ONE batched launch with the
-        divisor vector -- pnp_saga_table_update_hist_pp behind the minibatch gradient, or the one-kernel step."""
-        b = self.b
-        r = self._check_rows_pp(r)
-        prev = self._row_vec(self.r_prev)
-        self._rows = (r, self._row_vec(r))
-        lr = self.eta * self.lr_decay ** self.s
-        if self.fused:
-            self._one_kernel(b.plan.saga_step, self.z, self._slot_bits(j), b.YT, self.table, self._rows[1], prev, self.tsum,
-                             self._c('lr', self.s, lr), 1.0 / self.hist, alpha=self._c('1/mb', 0, 1.0 / self.mb),
-                             inv_hist_pp=self._inv_hist_pp)
-            self.r_prev = r
-            self.s += 1
-            return
-        b.grad_stoch(self.z, self.mbs, j, out=self.g, alpha=self._c('1/mb', 0, 1.0 / self.mb))
-        ops.saga_table_update_pp(self.z, self.g, self.table, self._rows[1], prev, self.tsum, self._c('lr', self.s, lr), 1.0 / self.hist,
-                                 inv_hist_pp=self._inv_hist_pp)
-        self.r_prev = r
-        self.z = self._prox(self.z)
-        self.s += 1
-
-    def _step_fused(self, j, r):
-        """The step in ONE kernel: the rows and coefficients are those of the streaming step (a row for the whole batch as a
-        constant [B] vector)."""
-        b = self.b
-        if np.ndim(r) == 0:
-            r = int(r)
-            bad = not 0 <= r < self.hist
+    def _step_batched(self, j, r):
+        """`step()` in ONE kernel (fused=True) and with a per-problem hist_size: the rows checked, then ONE batched launch -- the
+        one-kernel step with the rows and coefficients of the streaming step (a row for the whole batch as a constant [B] vector),
+        or pnp_saga_table_update_hist_pp behind the minibatch gradient; a per-problem hist_size adds the divisor vector."""
+        b, kw = self.b, {}
+        if self.hist_pp is not None:
+            r, kw = self._check_rows(r, self.hist_pp), dict(inv_hist_pp=self._inv_hist_pp)
         else:
-            r = np.broadcast_to(np.asarray(r, np.int64), (b.B,)).copy()
-            bad = r.min() < 0 or r.max() >= self.hist
-        if bad:
-            raise ValueError(f'SAGA row outside the table: rows in [0, {self.hist}), got {np.ravel(r).tolist()}')
-        prev = self._row_vec(self.r_prev)
-        row = self._row_vec(r)
+            r = self._check_rows(int(r) if np.ndim(r) == 0 else np.broadcast_to(np.asarray(r, np.int64), (b.B,)).copy(), self.hist)
+        prev, row = self._row_vec(self.r_prev), self._row_vec(r)
         if np.ndim(r) != 0:
             self._rows = (r, row)
         lr = self.eta * self.lr_decay ** self.s
-        self._one_kernel(b.plan.saga_step, self.z, self._slot_bits(j), b.YT, self.table, row, prev, self.tsum,
-                         self._c('lr', self.s, lr), 1.0 / self.hist, alpha=self._c('1/mb', 0, 1.0 / self.mb))
+        if self.fused:
+            self._one_kernel(b.plan.saga_step, self.z, self._slot_bits(j), b.YT, self.table, row, prev, self.tsum,
+                             self._c('lr', self.s, lr), 1.0 / self.hist, alpha=self._c('1/mb', 0, 1.0 / self.mb), **kw)
+        else:
+            b.grad_stoch(self.z, self.mbs, j, out=self.g, alpha=self._c('1/mb', 0, 1.0 / self.mb))
+            ops.saga_table_update_pp(self.z, self.g, self.table, row, prev, self.tsum, self._c('lr', self.s, lr), 1.0 / self.hist, **kw)
+            self.z = self._prox(self.z)
         self.r_prev = r
         self.s += 1
 
@@ -1196,10 +1111,9 @@ class SagaEngine(_FusedStep, _StochEngine):
         b, px = self.b, self.prox
         kw = {}
         if self.hist_pp is not None:                            # every problem's own bound; the rows are then always [n][B]
-            r = self._check_rows_pp(r.reshape(n, -1))
-            kw = dict(inv_hist_pp=self._inv_hist_pp)
-        elif r.min() < 0 or r.max() >= self.hist:
-            raise ValueError(f'SAGA row outside the table: rows in [0, {self.hist}), got {np.ravel(r).tolist()}')
+            r, kw = self._check_rows(r.reshape(n, -1), self.hist_pp), dict(inv_hist_pp=self._inv_hist_pp)
+        else:
+            self._check_rows(r, self.hist)
         rows = np.ascontiguousarray(np.broadcast_to(r.reshape(n, -1), (n, b.B)), np.int32)
         rows_dev = torch.from_numpy(rows).to(self.z.device)
         prev, i0 = self._row_vec(self.r_prev), 0
@@ -1211,7 +1125,7 @@ class SagaEngine(_FusedStep, _StochEngine):
             b.plan.saga_span(self.z, self.mbs.selbits, b.YT, self.table, rows_dev[i0:i0 + m], prev, self.tsum, self._c('lr', self.s, lr),
                              1.0 / self.hist, m, b.xrec, self.sse_log, self.n_prox % self.n_log, px.sig,
                              alpha=self._c('1/mb', 0, 1.0 / self.mb), sigma_modifier=px.sigma_modifier, **kw)
-            self._span_done(m)
+            self._launched(m, m)
             i0 += m
             prev = rows_dev[i0 - 1]
         if r.ndim == 1:                                         # as the last step leaves them: a row for the whole batch ...
