@@ -11,6 +11,7 @@
 //   k_rows_inv   (csmri_rows.h) Hermitian re-expansion, inverse row FFT, fused epilogue
 #include "csmri_rows.h"
 #include "draw.h"
+#include "csmri_fused.h"
 #include <vector>
 #include <cstdlib>
 #include <cmath>
@@ -326,58 +327,6 @@ extern "C" int pnp_csmri_pack_y(pnp_csmri_plan* p, const void* YT, const uint8_t
     return PNP_OK;
 }
 
-namespace pnp {
-int csmri_fused_launch(int batch, const void* twtab, const void* a, const void* b, const uint32_t* bitsT, const void* yh,
-                       double alpha, const void* alpha_vec, double beta, const void* c1, double gamma, const void* c2, void* out,
-                       int mode, double sigma_modifier, double fallback_sigma, const void* xrec, double* sse_out, void* sigma_out,
-                       void* stream, void* w_out = nullptr, void* mu_out = nullptr, const double* alpha_pp = nullptr,
-                       const double* gamma_pp = nullptr, const double* sm_pp = nullptr);
-int csmri_fused_outer_launch(int batch, const void* twtab, void* z, void* w, void* mu, const uint32_t* mask_bits, const void* yh,
-                             const void* alpha_vec, const uint32_t* selbits, int T2, double lr, int mini_batch_size,
-                             double sigma_modifier, double fallback_sigma, const void* xrec, double* sse_log, int log_row0, int n_log,
-                             void* sigma_out, void* stream, const double* lr_pp = nullptr, const int32_t* mb_vec = nullptr,
-                             const double* sm_pp = nullptr);
-int csmri_fused_outer_w2d_launch(int batch, const void* twtab, void* z, void* w, void* mu, const uint32_t* mask_bits, const void* yh,
-                                 const void* alpha_vec, const uint32_t* selbits, int T2, double lr, const double* lr_pp,
-                                 int mini_batch_size, const int32_t* mb_vec, double sigma_modifier, const double* sm_pp,
-                                 double fallback_sigma, const void* xrec, double* sse_log, int log_row0, int n_log, void* sigma_out,
-                                 void* stream);
-int csmri_fused_span_launch(int batch, const void* twtab, void* z, void* w, void* mu, const uint32_t* mask_bits, const void* yh,
-                            const void* alpha_vec, const uint32_t* selbits, int step0, int n_steps, int T2, const int32_t* t2_vec,
-                            double lr, const double* lr_pp, int mini_batch_size, const int32_t* mb_vec, double sigma_modifier,
-                            const double* sm_pp, double fallback_sigma, const void* xrec, double* sse_log, int log_row0, int n_log,
-                            void* sigma_out, void* stream);
-int csmri_sarah_launch(int batch, const void* twtab, const void* a, const void* b, const uint32_t* bitsT, double alpha,
-                       const void* alpha_vec, double beta, const void* c1, double gamma, const void* c2, void* v_out, void* out,
-                       void* out2, int mode, double sigma_modifier, double fallback_sigma, const void* xrec, double* sse_out,
-                       void* sigma_out, void* stream, const double* alpha_pp, const double* gamma_pp, const double* sm_pp);
-int csmri_sarah_outer_launch(int batch, const void* twtab, void* z, void* w_prev, void* w_next, void* v_prev, const uint32_t* mask_bits,
-                             const void* yh, const void* alpha_vec, const uint32_t* selbits, int T2, double eta, const double* eta_pp,
-                             double lr, const double* lr_pp, int mini_batch_size, const int32_t* mb_vec, double sigma_modifier,
-                             const double* sm_pp, double fallback_sigma, const void* xrec, double* sse_log, int log_row0, int n_log,
-                             void* sigma_out, void* stream);
-int csmri_sarah_span_launch(int batch, const void* twtab, void* z, void* w_prev, void* w_next, void* v_prev, const uint32_t* mask_bits,
-                            const void* yh, const void* alpha_vec, const uint32_t* selbits, int step0, int n_steps, int T2,
-                            const int32_t* t2_vec, double eta, const double* eta_pp, double lr, const double* lr_pp, int mini_batch_size,
-                            const int32_t* mb_vec, double sigma_modifier, const double* sm_pp, double fallback_sigma, const void* xrec,
-                            double* sse_log, double* outer_log, int log_row0, int n_log, void* sigma_out, void* stream);
-int csmri_step_span_launch(int batch, const void* twtab, void* z, const uint32_t* bits, const void* yh, const void* YT, double alpha,
-                           const void* alpha_vec, double beta, void* table, const int32_t* rows, const int32_t* prev_row0, void* sum,
-                           double lr, double inv_hist, int n_steps, double sigma_modifier, double fallback_sigma, const void* xrec,
-                           double* sse_log, int log_row0, int n_log, void* sigma_out, void* stream, const double* alpha_pp,
-                           const double* lr_pp, const double* sm_pp);
-int csmri_minibatch_launch(int batch, const void* twtab, const void* a, const uint32_t* bitsT, const void* YT, double alpha,
-                           const void* alpha_vec, double beta, const void* c1, void* table, const int32_t* row, const int32_t* prev_row,
-                           void* sum, double lr, double inv_hist, void* out, int mode, double sigma_modifier, double fallback_sigma,
-                           const void* xrec, double* sse_out, void* sigma_out, void* stream, const double* alpha_pp, const double* lr_pp,
-                           const double* sm_pp);
-int csmri_saga_hist_launch(int batch, const void* twtab, const void* a, const uint32_t* bitsT, const void* YT, double alpha,
-                           const void* alpha_vec, void* table, const int32_t* row, const int32_t* prev_row, void* sum, double lr,
-                           double inv_hist, void* out, int mode, double sigma_modifier, double fallback_sigma, const void* xrec,
-                           double* sse_out, void* sigma_out, void* stream, const double* alpha_pp, const double* lr_pp, const double* sm_pp,
-                           const double* inv_hist_pp, int n_steps, int log_row0, int n_log);
-}
-
 namespace {
 template <typename T, int RA, int LA>
 int run_grad(pnp_csmri_plan* p, const void* a, const void* b, const uint8_t* selT, const uint32_t* bitsT,
@@ -417,7 +366,7 @@ static int grad_sel_impl(pnp_csmri_plan* p, const void* a, const void* b, const 
     // large f32 256 x 256 batches with a bit-packed selector: the three passes in ONE kernel, the spectrum never in HBM
     // (csmri_fused.hip; one workgroup per image, so it needs about a workgroup per CU to pay off)
     if (p->dtype == PNP_F32 && p->H == 256 && bitsT != nullptr && YT == nullptr && p->batch >= p->fused_min_batch)
-        return csmri_fused_launch(p->batch, p->twtab, a, b, bitsT, yh, alpha, alpha_vec, beta, c1, gamma, c2, out, 2, 1.0, 0.0,
+        return csmri_fused_launch(p->batch, p->twtab, a, b, bitsT, yh, alpha, alpha_vec, beta, c1, gamma, c2, out, FUSED_GRAD, 1.0, 0.0,
                                   nullptr, nullptr, nullptr, stream, nullptr, nullptr, alpha_pp, gamma_pp, nullptr);
     hipStream_t s = (hipStream_t)stream;
 #define PNP_CS_ARGS p, a, b, selT, bitsT, yh, YT, alpha, alpha_vec, beta, c1, gamma, c2, out, s, alpha_pp, gamma_pp
@@ -455,17 +404,64 @@ extern "C" int pnp_csmri_grad(pnp_csmri_plan* p, const void* a, const void* b, c
 // ---- whole inner iteration in one kernel (csmri_fused.hip)
 // `int denoise` of the step entry points -> the kernel's MODE: 0 = store the stepped image (FUSED_NO_DENOISE), 2 = the 2-D wavelet prox
 // (FUSED_FULL_W2D), any other value = the per-column prox (FUSED_FULL)
-static inline int fused_mode(int denoise) { return denoise == 0 ? 1 : (denoise == 2 ? 3 : 0); }
+static inline int fused_mode(int denoise) { return denoise == 0 ? FUSED_NO_DENOISE : (denoise == 2 ? FUSED_FULL_W2D : FUSED_FULL); }
+
+// The argument checks the entry points below share.  Macros, not functions: a refusal names the function that made it (PNP_CHECK_ARG's
+// __func__) and callers see that text, so a check expands inside the function that answers.  The _AS forms are for an _impl that answers
+// in the name of the public entry point that called it: it is handed that name (`who`).
+#define PNP_CHECK_ARG_AS(who, cond, msg) \
+    do { if (!(cond)) { pnp::set_error(std::string(who) + ": " + (msg)); return PNP_ERR_ARG; } } while (0)
+#define PNP_CHECK_ONE_KERNEL_PLAN_AS(who, p) \
+    PNP_CHECK_ARG_AS(who, (p)->dtype == PNP_F32 && (p)->H == 256 && (p)->W == 256, "the one-kernel iteration exists for f32 plans of 256 x 256")
+#define PNP_CHECK_ONE_KERNEL_PLAN(p) PNP_CHECK_ONE_KERNEL_PLAN_AS(__func__, p)
+#define PNP_CHECK_SSE_XREC_AS(who, sse, xrec) PNP_CHECK_ARG_AS(who, !((sse) && !(xrec)), "sse_out needs xrec")
+#define PNP_CHECK_SSE_XREC(sse, xrec) PNP_CHECK_SSE_XREC_AS(__func__, sse, xrec)
+#define PNP_CHECK_OWN_BUFFERS3_AS(who, z, w, mu) \
+    PNP_CHECK_ARG_AS(who, (z) != (w) && (z) != (mu) && (w) != (mu), "z, w and mu must be buffers of their own")
+#define PNP_CHECK_OWN_BUFFERS3(z, w, mu) PNP_CHECK_OWN_BUFFERS3_AS(__func__, z, w, mu)
+#define PNP_CHECK_OWN_BUFFERS4(z, wp, wn, vp)                                                                                      \
+    PNP_CHECK_ARG((z) != (wp) && (z) != (wn) && (z) != (vp) && (wp) != (wn) && (wp) != (vp) && (wn) != (vp),                        \
+                  "z, w_prev, w_next and v_prev must be buffers of their own")
+// the n-step forms: n_steps log rows from log_row0 on (an int in the kernel), and a prox they hold
+#define PNP_CHECK_LOG_RANGE(n_steps, n_log, log_row0) \
+    PNP_CHECK_ARG((n_steps) >= 1 && (n_log) >= 1 && (log_row0) >= 0 && (log_row0) <= INT32_MAX - (n_steps), "bad n_steps / log")
+#define PNP_CHECK_SPAN_DENOISE(denoise) do {                                                                                       \
+    PNP_CHECK_ARG((denoise) != 0, "the span kernels hold the TV prox: denoise must be != 0");                                      \
+    PNP_CHECK_ARG((denoise) != 2, "the span kernels hold the per-column prox only: denoise = 2 (the 2-D wavelet prox) is not accepted"); \
+} while (0)
+// the per-problem-T2 spans (pnp_csmri_svrg_span_pp, pnp_csmri_sarah_span_pp)
+#define PNP_CHECK_SPAN_RANGE(step0, n_steps, T2, t2_vec, mini_batch_size, mb_vec, n_log, log_row0) do {                            \
+    PNP_CHECK_ARG((n_steps) >= 1 && (step0) >= 0 && (step0) <= INT32_MAX - (n_steps), "bad step0 / n_steps");                      \
+    PNP_CHECK_ARG((t2_vec) != nullptr || (T2) >= 1, "bad T2: a scalar T2 >= 1 or a t2_vec");                                       \
+    PNP_CHECK_ARG(((mb_vec) != nullptr || (mini_batch_size) >= 1) && (n_log) >= 1 && (log_row0) >= 0 &&                            \
+                  (log_row0) <= INT32_MAX - (n_steps), "bad mini_batch_size / log");                                               \
+} while (0)
+
+// [x, x + nx) and [y, y + ny) share a byte (a NULL buffer shares none)
+static bool overlap(const void* x, size_t nx, const void* y, size_t ny) {
+    const uintptr_t a0 = (uintptr_t)x, b0 = (uintptr_t)y;
+    return x != nullptr && y != nullptr && a0 < b0 + ny && b0 < a0 + nx;
+}
+
+static int svrg_step_impl(const char* who, pnp_csmri_plan* p, const void* a, const void* b, const uint32_t* bitsT, double alpha,
+                          const double* alpha_pp, const void* alpha_vec, double beta, const void* c1, double gamma,
+                          const double* gamma_pp, const void* c2, void* out, int denoise, double sigma_modifier,
+                          const double* sigma_modifier_pp, double fallback_sigma, const void* xrec, double* sse_out, void* sigma_out,
+                          void* stream) {
+    PNP_CHECK_ARG_AS(who, p && a && bitsT && out, "null argument");
+    PNP_CHECK_ONE_KERNEL_PLAN_AS(who, p);
+    PNP_CHECK_SSE_XREC_AS(who, sse_out, xrec);
+    return csmri_fused_launch(p->batch, p->twtab, a, b, bitsT, nullptr, alpha, alpha_vec, beta, c1, gamma, c2, out, fused_mode(denoise),
+                              sigma_modifier, fallback_sigma, xrec, sse_out, sigma_out, stream, nullptr, nullptr, alpha_pp, gamma_pp,
+                              sigma_modifier_pp);
+}
 
 extern "C" int pnp_csmri_svrg_step(pnp_csmri_plan* p, const void* a, const void* b, const uint32_t* bitsT, double alpha,
                                    const void* alpha_vec, double beta, const void* c1, double gamma, const void* c2, void* out,
                                    int denoise, double sigma_modifier, double fallback_sigma, const void* xrec,
                                    double* sse_out, void* sigma_out, void* stream) {
-    PNP_CHECK_ARG(p && a && bitsT && out, "null argument");
-    PNP_CHECK_ARG(p->dtype == PNP_F32 && p->H == 256 && p->W == 256, "the one-kernel iteration exists for f32 plans of 256 x 256");
-    PNP_CHECK_ARG(!(sse_out && !xrec), "sse_out needs xrec");
-    return csmri_fused_launch(p->batch, p->twtab, a, b, bitsT, nullptr, alpha, alpha_vec, beta, c1, gamma, c2, out, fused_mode(denoise),
-                              sigma_modifier, fallback_sigma, xrec, sse_out, sigma_out, stream);
+    return svrg_step_impl(__func__, p, a, b, bitsT, alpha, nullptr, alpha_vec, beta, c1, gamma, nullptr, c2, out, denoise, sigma_modifier,
+                          nullptr, fallback_sigma, xrec, sse_out, sigma_out, stream);
 }
 
 extern "C" int pnp_csmri_svrg_step_pp(pnp_csmri_plan* p, const void* a, const void* b, const uint32_t* bitsT, double alpha,
@@ -473,12 +469,8 @@ extern "C" int pnp_csmri_svrg_step_pp(pnp_csmri_plan* p, const void* a, const vo
                                       const double* gamma_pp, const void* c2, void* out, int denoise, double sigma_modifier,
                                       const double* sigma_modifier_pp, double fallback_sigma, const void* xrec, double* sse_out,
                                       void* sigma_out, void* stream) {
-    PNP_CHECK_ARG(p && a && bitsT && out, "null argument");
-    PNP_CHECK_ARG(p->dtype == PNP_F32 && p->H == 256 && p->W == 256, "the one-kernel iteration exists for f32 plans of 256 x 256");
-    PNP_CHECK_ARG(!(sse_out && !xrec), "sse_out needs xrec");
-    return csmri_fused_launch(p->batch, p->twtab, a, b, bitsT, nullptr, alpha, alpha_vec, beta, c1, gamma, c2, out, fused_mode(denoise),
-                              sigma_modifier, fallback_sigma, xrec, sse_out, sigma_out, stream, nullptr, nullptr, alpha_pp, gamma_pp,
-                              sigma_modifier_pp);
+    return svrg_step_impl(__func__, p, a, b, bitsT, alpha, alpha_pp, alpha_vec, beta, c1, gamma, gamma_pp, c2, out, denoise,
+                          sigma_modifier, sigma_modifier_pp, fallback_sigma, xrec, sse_out, sigma_out, stream);
 }
 
 // ---- the SARAH form of the one-kernel iteration: v_out stored from the epilogue, then out = prox_TV(c2 + gamma * v_out), out2 = out
@@ -487,11 +479,11 @@ static int sarah_step_impl(pnp_csmri_plan* p, const void* a, const void* b, cons
                            void* v_out, void* out, void* out2, int denoise, double sigma_modifier, const double* sigma_modifier_pp,
                            double fallback_sigma, const void* xrec, double* sse_out, void* sigma_out, void* stream) {
     PNP_CHECK_ARG(p && a && b && bitsT && c1 && c2 && v_out && out, "null argument");
-    PNP_CHECK_ARG(!(sse_out && !xrec), "sse_out needs xrec");
+    PNP_CHECK_SSE_XREC(sse_out, xrec);
     PNP_CHECK_ARG(denoise || out2 == nullptr, "out2 needs denoise != 0 (without the prox the stored image is not the iterate)");
     PNP_CHECK_ARG(v_out != a && v_out != b && v_out != c2 && v_out != out && v_out != out2,
                   "v_out may alias c1 only (not a, b, c2, out or out2)");
-    PNP_CHECK_ARG(p->dtype == PNP_F32 && p->H == 256 && p->W == 256, "the one-kernel iteration exists for f32 plans of 256 x 256");
+    PNP_CHECK_ONE_KERNEL_PLAN(p);
     return csmri_sarah_launch(p->batch, p->twtab, a, b, bitsT, alpha, alpha_vec, beta, c1, gamma, c2, v_out, out, out2, fused_mode(denoise),
                               sigma_modifier, fallback_sigma, xrec, sse_out, sigma_out, stream, alpha_pp, gamma_pp, sigma_modifier_pp);
 }
@@ -522,8 +514,8 @@ static int grad_step_impl(pnp_csmri_plan* p, const void* a, const uint32_t* bits
                           double* sse_out, void* sigma_out, void* stream) {
     PNP_CHECK_ARG(p && a && bitsT && c1 && out, "null argument");
     PNP_CHECK_ARG((yh != nullptr) != (YT != nullptr), "pass the packed data term (yh) or the raw data (YT), exactly one of them");
-    PNP_CHECK_ARG(p->dtype == PNP_F32 && p->H == 256 && p->W == 256, "the one-kernel iteration exists for f32 plans of 256 x 256");
-    PNP_CHECK_ARG(!(sse_out && !xrec), "sse_out needs xrec");
+    PNP_CHECK_ONE_KERNEL_PLAN(p);
+    PNP_CHECK_SSE_XREC(sse_out, xrec);
     if (yh != nullptr)
         return csmri_fused_launch(p->batch, p->twtab, a, nullptr, bitsT, yh, alpha, alpha_vec, beta, c1, 0.0, nullptr, out,
                                   fused_mode(denoise), sigma_modifier, fallback_sigma, xrec, sse_out, sigma_out, stream, nullptr, nullptr,
@@ -555,16 +547,12 @@ static int saga_step_impl(pnp_csmri_plan* p, const void* z, const uint32_t* bits
                           const double* sigma_modifier_pp, double fallback_sigma, const void* xrec, double* sse_out, void* sigma_out,
                           void* stream, bool hist_form = false, const double* inv_hist_pp = nullptr) {
     PNP_CHECK_ARG(p && z && bitsT && YT && table && row && prev_row && sum && out, "null argument");
-    PNP_CHECK_ARG(p->dtype == PNP_F32 && p->H == 256 && p->W == 256, "the one-kernel iteration exists for f32 plans of 256 x 256");
-    PNP_CHECK_ARG(!(sse_out && !xrec), "sse_out needs xrec");
+    PNP_CHECK_ONE_KERNEL_PLAN(p);
+    PNP_CHECK_SSE_XREC(sse_out, xrec);
     PNP_CHECK_ARG(hist >= 1, "need hist >= 1");
     PNP_CHECK_ARG(!(hist_form && denoise == 2), "the per-problem-divisor form holds the per-column prox only: denoise = 2 is not accepted");
     {   // table [hist][batch][H][W] and sum [batch][H][W] are written while z, out and xrec are read or written: no overlap
         const size_t img = (size_t)p->batch * 256 * 256 * sizeof(float);
-        auto overlap = [](const void* x, size_t nx, const void* y, size_t ny) {
-            const uintptr_t a0 = (uintptr_t)x, b0 = (uintptr_t)y;
-            return x != nullptr && y != nullptr && a0 < b0 + ny && b0 < a0 + nx;
-        };
         const size_t tb = img * (size_t)hist;
         PNP_CHECK_ARG(!overlap(table, tb, z, img) && !overlap(table, tb, out, img) && !overlap(table, tb, xrec, img) &&
                       !overlap(sum, img, z, img) && !overlap(sum, img, out, img) && !overlap(sum, img, xrec, img) &&
@@ -607,44 +595,65 @@ extern "C" int pnp_csmri_saga_step_hist_pp(pnp_csmri_plan* p, const void* z, con
                           sigma_modifier, sigma_modifier_pp, fallback_sigma, xrec, sse_out, sigma_out, stream, true, inv_hist_pp);
 }
 
-// ---- the same with the outer-loop refresh folded in (first inner iteration of an outer iteration)
+// ---- the same with the outer-loop refresh folded in (first inner iteration of an outer iteration); lr_pp, sigma_modifier_pp: double
+// [batch], NULL = the scalar
+static int svrg_outer_step_impl(const char* who, pnp_csmri_plan* p, const void* z, const uint32_t* mask_bitsT, const void* yh,
+                                const void* alpha_vec, double lr, const double* lr_pp, void* w_out, void* mu_out, void* out, int denoise,
+                                double sigma_modifier, const double* sigma_modifier_pp, double fallback_sigma, const void* xrec,
+                                double* sse_out, void* sigma_out, void* stream) {
+    PNP_CHECK_ARG_AS(who, p && z && mask_bitsT && yh && w_out && mu_out && out, "null argument");
+    PNP_CHECK_ONE_KERNEL_PLAN_AS(who, p);
+    PNP_CHECK_SSE_XREC_AS(who, sse_out, xrec);
+    PNP_CHECK_ARG_AS(who, w_out != z && mu_out != z && w_out != mu_out && w_out != out && mu_out != out,
+                     "w_out and mu_out must be buffers of their own");
+    return csmri_fused_launch(p->batch, p->twtab, z, nullptr, mask_bitsT, yh, 1.0, alpha_vec, 1.0, z, -lr, nullptr, out,
+                              fused_mode(denoise), sigma_modifier, fallback_sigma, xrec, sse_out, sigma_out, stream, w_out, mu_out, nullptr,
+                              lr_pp, sigma_modifier_pp);
+}
+
 extern "C" int pnp_csmri_svrg_outer_step(pnp_csmri_plan* p, const void* z, const uint32_t* mask_bitsT, const void* yh,
                                          const void* alpha_vec, double lr, void* w_out, void* mu_out, void* out, int denoise,
                                          double sigma_modifier, double fallback_sigma, const void* xrec, double* sse_out,
                                          void* sigma_out, void* stream) {
-    PNP_CHECK_ARG(p && z && mask_bitsT && yh && w_out && mu_out && out, "null argument");
-    PNP_CHECK_ARG(p->dtype == PNP_F32 && p->H == 256 && p->W == 256, "the one-kernel iteration exists for f32 plans of 256 x 256");
-    PNP_CHECK_ARG(!(sse_out && !xrec), "sse_out needs xrec");
-    PNP_CHECK_ARG(w_out != z && mu_out != z && w_out != mu_out && w_out != out && mu_out != out, "w_out and mu_out must be buffers of their own");
-    return csmri_fused_launch(p->batch, p->twtab, z, nullptr, mask_bitsT, yh, 1.0, alpha_vec, 1.0, z, -lr, nullptr, out,
-                              fused_mode(denoise), sigma_modifier, fallback_sigma, xrec, sse_out, sigma_out, stream, w_out, mu_out);
+    return svrg_outer_step_impl(__func__, p, z, mask_bitsT, yh, alpha_vec, lr, nullptr, w_out, mu_out, out, denoise, sigma_modifier,
+                                nullptr, fallback_sigma, xrec, sse_out, sigma_out, stream);
 }
 
-// ---- a whole outer iteration (refresh + T2 inner iterations, TV prox) in one launch
-extern "C" int pnp_csmri_svrg_outer_iteration(pnp_csmri_plan* p, void* z, void* w, void* mu, const uint32_t* mask_bitsT, const void* yh,
-                                              const void* alpha_vec, const uint32_t* selbits, int T2, double lr, int mini_batch_size,
-                                              double sigma_modifier, double fallback_sigma, const void* xrec, double* sse_log,
-                                              int log_row0, int n_log, void* sigma_out, void* stream) {
-    PNP_CHECK_ARG(p && z && w && mu && mask_bitsT && yh && alpha_vec && xrec && sse_log && sigma_out, "null argument");
-    PNP_CHECK_ARG(p->dtype == PNP_F32 && p->H == 256 && p->W == 256, "the one-kernel iteration exists for f32 plans of 256 x 256");
-    PNP_CHECK_ARG(T2 >= 1 && (T2 == 1 || selbits != nullptr) && mini_batch_size >= 1 && n_log >= 1 && log_row0 >= 0, "bad T2 / selbits / mini_batch_size / log");
-    PNP_CHECK_ARG(z != w && z != mu && w != mu, "z, w and mu must be buffers of their own");
-    return csmri_fused_outer_launch(p->batch, p->twtab, z, w, mu, mask_bitsT, yh, alpha_vec, selbits, T2, lr, mini_batch_size,
-                                    sigma_modifier, fallback_sigma, xrec, sse_log, log_row0, n_log, sigma_out, stream);
-}
-
-// ---- the per-problem forms of the two calls above (lr_pp, sigma_modifier_pp: double [batch]; mb_vec: int32 [batch]; NULL = the scalar)
 extern "C" int pnp_csmri_svrg_outer_step_pp(pnp_csmri_plan* p, const void* z, const uint32_t* mask_bitsT, const void* yh,
                                             const void* alpha_vec, double lr, const double* lr_pp, void* w_out, void* mu_out, void* out,
                                             int denoise, double sigma_modifier, const double* sigma_modifier_pp, double fallback_sigma,
                                             const void* xrec, double* sse_out, void* sigma_out, void* stream) {
-    PNP_CHECK_ARG(p && z && mask_bitsT && yh && w_out && mu_out && out, "null argument");
-    PNP_CHECK_ARG(p->dtype == PNP_F32 && p->H == 256 && p->W == 256, "the one-kernel iteration exists for f32 plans of 256 x 256");
-    PNP_CHECK_ARG(!(sse_out && !xrec), "sse_out needs xrec");
-    PNP_CHECK_ARG(w_out != z && mu_out != z && w_out != mu_out && w_out != out && mu_out != out, "w_out and mu_out must be buffers of their own");
-    return csmri_fused_launch(p->batch, p->twtab, z, nullptr, mask_bitsT, yh, 1.0, alpha_vec, 1.0, z, -lr, nullptr, out,
-                              fused_mode(denoise), sigma_modifier, fallback_sigma, xrec, sse_out, sigma_out, stream, w_out, mu_out, nullptr,
-                              lr_pp, sigma_modifier_pp);
+    return svrg_outer_step_impl(__func__, p, z, mask_bitsT, yh, alpha_vec, lr, lr_pp, w_out, mu_out, out, denoise, sigma_modifier,
+                                sigma_modifier_pp, fallback_sigma, xrec, sse_out, sigma_out, stream);
+}
+
+// ---- a whole outer iteration (refresh + T2 inner iterations) in one launch; lr_pp, sigma_modifier_pp: double [batch], mb_vec: int32
+// [batch], NULL = the scalar.  w2d: the 2-D wavelet prox in every iteration instead of the per-column one
+static int svrg_outer_iteration_impl(const char* who, pnp_csmri_plan* p, void* z, void* w, void* mu, const uint32_t* mask_bitsT,
+                                     const void* yh, const void* alpha_vec, const uint32_t* selbits, int T2, double lr,
+                                     const double* lr_pp, int mini_batch_size, const int32_t* mb_vec, double sigma_modifier,
+                                     const double* sigma_modifier_pp, double fallback_sigma, const void* xrec, double* sse_log,
+                                     int log_row0, int n_log, void* sigma_out, bool w2d, void* stream) {
+    PNP_CHECK_ARG_AS(who, p && z && w && mu && mask_bitsT && yh && alpha_vec && xrec && sse_log && sigma_out, "null argument");
+    PNP_CHECK_ONE_KERNEL_PLAN_AS(who, p);
+    PNP_CHECK_ARG_AS(who, T2 >= 1 && (T2 == 1 || selbits != nullptr) && (mb_vec != nullptr || mini_batch_size >= 1) && n_log >= 1 &&
+                     log_row0 >= 0, "bad T2 / selbits / mini_batch_size / log");
+    PNP_CHECK_OWN_BUFFERS3_AS(who, z, w, mu);
+    if (w2d)
+        return csmri_fused_outer_w2d_launch(p->batch, p->twtab, z, w, mu, mask_bitsT, yh, alpha_vec, selbits, T2, lr, lr_pp,
+                                            mini_batch_size, mb_vec, sigma_modifier, sigma_modifier_pp, fallback_sigma, xrec, sse_log,
+                                            log_row0, n_log, sigma_out, stream);
+    return csmri_fused_outer_launch(p->batch, p->twtab, z, w, mu, mask_bitsT, yh, alpha_vec, selbits, T2, lr, mini_batch_size,
+                                    sigma_modifier, fallback_sigma, xrec, sse_log, log_row0, n_log, sigma_out, stream, lr_pp, mb_vec,
+                                    sigma_modifier_pp);
+}
+
+extern "C" int pnp_csmri_svrg_outer_iteration(pnp_csmri_plan* p, void* z, void* w, void* mu, const uint32_t* mask_bitsT, const void* yh,
+                                              const void* alpha_vec, const uint32_t* selbits, int T2, double lr, int mini_batch_size,
+                                              double sigma_modifier, double fallback_sigma, const void* xrec, double* sse_log,
+                                              int log_row0, int n_log, void* sigma_out, void* stream) {
+    return svrg_outer_iteration_impl(__func__, p, z, w, mu, mask_bitsT, yh, alpha_vec, selbits, T2, lr, nullptr, mini_batch_size, nullptr,
+                                     sigma_modifier, nullptr, fallback_sigma, xrec, sse_log, log_row0, n_log, sigma_out, false, stream);
 }
 
 extern "C" int pnp_csmri_svrg_outer_iteration_pp(pnp_csmri_plan* p, void* z, void* w, void* mu, const uint32_t* mask_bitsT, const void* yh,
@@ -652,18 +661,14 @@ extern "C" int pnp_csmri_svrg_outer_iteration_pp(pnp_csmri_plan* p, void* z, voi
                                                  int mini_batch_size, const int32_t* mb_vec, double sigma_modifier,
                                                  const double* sigma_modifier_pp, double fallback_sigma, const void* xrec,
                                                  double* sse_log, int log_row0, int n_log, void* sigma_out, void* stream) {
-    PNP_CHECK_ARG(p && z && w && mu && mask_bitsT && yh && alpha_vec && xrec && sse_log && sigma_out, "null argument");
-    PNP_CHECK_ARG(p->dtype == PNP_F32 && p->H == 256 && p->W == 256, "the one-kernel iteration exists for f32 plans of 256 x 256");
-    PNP_CHECK_ARG(T2 >= 1 && (T2 == 1 || selbits != nullptr) && (mb_vec != nullptr || mini_batch_size >= 1) && n_log >= 1 && log_row0 >= 0,
-                  "bad T2 / selbits / mini_batch_size / log");
-    PNP_CHECK_ARG(z != w && z != mu && w != mu, "z, w and mu must be buffers of their own");
-    return csmri_fused_outer_launch(p->batch, p->twtab, z, w, mu, mask_bitsT, yh, alpha_vec, selbits, T2, lr, mini_batch_size,
-                                    sigma_modifier, fallback_sigma, xrec, sse_log, log_row0, n_log, sigma_out, stream, lr_pp, mb_vec,
-                                    sigma_modifier_pp);
+    return svrg_outer_iteration_impl(__func__, p, z, w, mu, mask_bitsT, yh, alpha_vec, selbits, T2, lr, lr_pp, mini_batch_size, mb_vec,
+                                     sigma_modifier, sigma_modifier_pp, fallback_sigma, xrec, sse_log, log_row0, n_log, sigma_out, false,
+                                     stream);
 }
 
-// ---- pnp_csmri_svrg_outer_iteration_pp with the prox kind: denoise = 1 IS that call (the per-column prox); denoise = 2 runs the 2-D
-// wavelet prox in every iteration -- the outer step and the T2 - 1 inner steps with denoise = 2, bit for bit
+// ---- pnp_csmri_svrg_outer_iteration_pp with the prox kind: denoise = 1 IS that call (the per-column prox; it answers a bad argument
+// in that call's name); denoise = 2 runs the 2-D wavelet prox in every iteration -- the outer step and the T2 - 1 inner steps with
+// denoise = 2, bit for bit
 extern "C" int pnp_csmri_svrg_outer_iteration_prox(pnp_csmri_plan* p, void* z, void* w, void* mu, const uint32_t* mask_bitsT,
                                                    const void* yh, const void* alpha_vec, const uint32_t* selbits, int T2, double lr,
                                                    const double* lr_pp, int mini_batch_size, const int32_t* mb_vec,
@@ -671,18 +676,9 @@ extern "C" int pnp_csmri_svrg_outer_iteration_prox(pnp_csmri_plan* p, void* z, v
                                                    const void* xrec, double* sse_log, int log_row0, int n_log, void* sigma_out,
                                                    int denoise, void* stream) {
     PNP_CHECK_ARG(denoise == 1 || denoise == 2, "denoise must be 1 (the per-column prox) or 2 (the 2-D wavelet prox)");
-    if (denoise == 1)
-        return pnp_csmri_svrg_outer_iteration_pp(p, z, w, mu, mask_bitsT, yh, alpha_vec, selbits, T2, lr, lr_pp, mini_batch_size, mb_vec,
-                                                 sigma_modifier, sigma_modifier_pp, fallback_sigma, xrec, sse_log, log_row0, n_log,
-                                                 sigma_out, stream);
-    PNP_CHECK_ARG(p && z && w && mu && mask_bitsT && yh && alpha_vec && xrec && sse_log && sigma_out, "null argument");
-    PNP_CHECK_ARG(p->dtype == PNP_F32 && p->H == 256 && p->W == 256, "the one-kernel iteration exists for f32 plans of 256 x 256");
-    PNP_CHECK_ARG(T2 >= 1 && (T2 == 1 || selbits != nullptr) && (mb_vec != nullptr || mini_batch_size >= 1) && n_log >= 1 && log_row0 >= 0,
-                  "bad T2 / selbits / mini_batch_size / log");
-    PNP_CHECK_ARG(z != w && z != mu && w != mu, "z, w and mu must be buffers of their own");
-    return csmri_fused_outer_w2d_launch(p->batch, p->twtab, z, w, mu, mask_bitsT, yh, alpha_vec, selbits, T2, lr, lr_pp, mini_batch_size,
-                                        mb_vec, sigma_modifier, sigma_modifier_pp, fallback_sigma, xrec, sse_log, log_row0, n_log,
-                                        sigma_out, stream);
+    return svrg_outer_iteration_impl(denoise == 1 ? "pnp_csmri_svrg_outer_iteration_pp" : __func__, p, z, w, mu, mask_bitsT, yh, alpha_vec,
+                                     selbits, T2, lr, lr_pp, mini_batch_size, mb_vec, sigma_modifier, sigma_modifier_pp, fallback_sigma,
+                                     xrec, sse_log, log_row0, n_log, sigma_out, denoise == 2, stream);
 }
 
 // ---- n_steps inner iterations in one launch, every problem refreshing by its own T2 (t2_vec: int32 [batch]; NULL = the scalar)
@@ -692,12 +688,9 @@ extern "C" int pnp_csmri_svrg_span_pp(pnp_csmri_plan* p, void* z, void* w, void*
                                       double sigma_modifier, const double* sigma_modifier_pp, double fallback_sigma, const void* xrec,
                                       double* sse_log, int log_row0, int n_log, void* sigma_out, void* stream) {
     PNP_CHECK_ARG(p && z && w && mu && mask_bitsT && yh && alpha_vec && selbits && xrec && sse_log && sigma_out, "null argument");
-    PNP_CHECK_ARG(n_steps >= 1 && step0 >= 0 && step0 <= INT32_MAX - n_steps, "bad step0 / n_steps");
-    PNP_CHECK_ARG(t2_vec != nullptr || T2 >= 1, "bad T2: a scalar T2 >= 1 or a t2_vec");
-    PNP_CHECK_ARG((mb_vec != nullptr || mini_batch_size >= 1) && n_log >= 1 && log_row0 >= 0 && log_row0 <= INT32_MAX - n_steps,
-                  "bad mini_batch_size / log");
-    PNP_CHECK_ARG(p->dtype == PNP_F32 && p->H == 256 && p->W == 256, "the one-kernel iteration exists for f32 plans of 256 x 256");
-    PNP_CHECK_ARG(z != w && z != mu && w != mu, "z, w and mu must be buffers of their own");
+    PNP_CHECK_SPAN_RANGE(step0, n_steps, T2, t2_vec, mini_batch_size, mb_vec, n_log, log_row0);
+    PNP_CHECK_ONE_KERNEL_PLAN(p);
+    PNP_CHECK_OWN_BUFFERS3(z, w, mu);
     return csmri_fused_span_launch(p->batch, p->twtab, z, w, mu, mask_bitsT, yh, alpha_vec, selbits, step0, n_steps, T2, t2_vec, lr, lr_pp,
                                    mini_batch_size, mb_vec, sigma_modifier, sigma_modifier_pp, fallback_sigma, xrec, sse_log, log_row0,
                                    n_log, sigma_out, stream);
@@ -713,9 +706,8 @@ static int sarah_outer_impl(pnp_csmri_plan* p, void* z, void* w_prev, void* w_ne
                   "null argument");
     PNP_CHECK_ARG(T2 >= 1 && T2 <= INT32_MAX - 1 && (mb_vec != nullptr || mini_batch_size >= 1) && n_log >= 1 && log_row0 >= 0 &&
                   log_row0 <= INT32_MAX - 1 - T2, "bad T2 / mini_batch_size / log");
-    PNP_CHECK_ARG(p->dtype == PNP_F32 && p->H == 256 && p->W == 256, "the one-kernel iteration exists for f32 plans of 256 x 256");
-    PNP_CHECK_ARG(z != w_prev && z != w_next && z != v_prev && w_prev != w_next && w_prev != v_prev && w_next != v_prev,
-                  "z, w_prev, w_next and v_prev must be buffers of their own");
+    PNP_CHECK_ONE_KERNEL_PLAN(p);
+    PNP_CHECK_OWN_BUFFERS4(z, w_prev, w_next, v_prev);
     return csmri_sarah_outer_launch(p->batch, p->twtab, z, w_prev, w_next, v_prev, mask_bitsT, yh, alpha_vec, selbits, T2, eta, eta_pp, lr,
                                     lr_pp, mini_batch_size, mb_vec, sigma_modifier, sigma_modifier_pp, fallback_sigma, xrec, sse_log,
                                     log_row0, n_log, sigma_out, stream);
@@ -752,13 +744,9 @@ extern "C" int pnp_csmri_sarah_span_pp(pnp_csmri_plan* p, void* z, void* w_prev,
                                        double* outer_log, int log_row0, int n_log, void* sigma_out, void* stream) {
     PNP_CHECK_ARG(p && z && w_prev && w_next && v_prev && mask_bitsT && yh && alpha_vec && selbits && xrec && sse_log && outer_log &&
                   sigma_out, "null argument");
-    PNP_CHECK_ARG(n_steps >= 1 && step0 >= 0 && step0 <= INT32_MAX - n_steps, "bad step0 / n_steps");
-    PNP_CHECK_ARG(t2_vec != nullptr || T2 >= 1, "bad T2: a scalar T2 >= 1 or a t2_vec");
-    PNP_CHECK_ARG((mb_vec != nullptr || mini_batch_size >= 1) && n_log >= 1 && log_row0 >= 0 && log_row0 <= INT32_MAX - n_steps,
-                  "bad mini_batch_size / log");
-    PNP_CHECK_ARG(p->dtype == PNP_F32 && p->H == 256 && p->W == 256, "the one-kernel iteration exists for f32 plans of 256 x 256");
-    PNP_CHECK_ARG(z != w_prev && z != w_next && z != v_prev && w_prev != w_next && w_prev != v_prev && w_next != v_prev,
-                  "z, w_prev, w_next and v_prev must be buffers of their own");
+    PNP_CHECK_SPAN_RANGE(step0, n_steps, T2, t2_vec, mini_batch_size, mb_vec, n_log, log_row0);
+    PNP_CHECK_ONE_KERNEL_PLAN(p);
+    PNP_CHECK_OWN_BUFFERS4(z, w_prev, w_next, v_prev);
     PNP_CHECK_ARG(sse_log != outer_log, "sse_log and outer_log must be rings of their own");
     return csmri_sarah_span_launch(p->batch, p->twtab, z, w_prev, w_next, v_prev, mask_bitsT, yh, alpha_vec, selbits, step0, n_steps, T2,
                                    t2_vec, eta, eta_pp, lr, lr_pp, mini_batch_size, mb_vec, sigma_modifier, sigma_modifier_pp,
@@ -772,10 +760,9 @@ extern "C" int pnp_csmri_grad_span(pnp_csmri_plan* p, void* z, const uint32_t* b
                                    int log_row0, int n_log, void* sigma_out, void* stream) {
     PNP_CHECK_ARG(p && z && bitsT && xrec && sse_log && sigma_out, "null argument");
     PNP_CHECK_ARG((yh != nullptr) != (YT != nullptr), "pass the packed data term (yh) or the raw data (YT), exactly one of them");
-    PNP_CHECK_ARG(n_steps >= 1 && n_log >= 1 && log_row0 >= 0 && log_row0 <= INT32_MAX - n_steps, "bad n_steps / log");
-    PNP_CHECK_ARG(denoise != 0, "the span kernels hold the TV prox: denoise must be != 0");
-    PNP_CHECK_ARG(denoise != 2, "the span kernels hold the per-column prox only: denoise = 2 (the 2-D wavelet prox) is not accepted");
-    PNP_CHECK_ARG(p->dtype == PNP_F32 && p->H == 256 && p->W == 256, "the one-kernel iteration exists for f32 plans of 256 x 256");
+    PNP_CHECK_LOG_RANGE(n_steps, n_log, log_row0);
+    PNP_CHECK_SPAN_DENOISE(denoise);
+    PNP_CHECK_ONE_KERNEL_PLAN(p);
     return csmri_step_span_launch(p->batch, p->twtab, z, bitsT, yh, YT, alpha, alpha_vec, beta, nullptr, nullptr, nullptr, nullptr, 0.0, 0.0,
                                   n_steps, sigma_modifier, fallback_sigma, xrec, sse_log, log_row0, n_log, sigma_out, stream, alpha_pp,
                                   nullptr, sigma_modifier_pp);
@@ -789,16 +776,11 @@ static int saga_span_impl(pnp_csmri_plan* p, void* z, const uint32_t* bitsT, con
                           int log_row0, int n_log, void* sigma_out, void* stream, bool hist_form, const double* inv_hist_pp) {
     PNP_CHECK_ARG(p && z && bitsT && YT && table && rows && prev_row0 && sum && xrec && sse_log && sigma_out, "null argument");
     PNP_CHECK_ARG(hist >= 1, "need hist >= 1");
-    PNP_CHECK_ARG(n_steps >= 1 && n_log >= 1 && log_row0 >= 0 && log_row0 <= INT32_MAX - n_steps, "bad n_steps / log");
-    PNP_CHECK_ARG(denoise != 0, "the span kernels hold the TV prox: denoise must be != 0");
-    PNP_CHECK_ARG(denoise != 2, "the span kernels hold the per-column prox only: denoise = 2 (the 2-D wavelet prox) is not accepted");
-    PNP_CHECK_ARG(p->dtype == PNP_F32 && p->H == 256 && p->W == 256, "the one-kernel iteration exists for f32 plans of 256 x 256");
+    PNP_CHECK_LOG_RANGE(n_steps, n_log, log_row0);
+    PNP_CHECK_SPAN_DENOISE(denoise);
+    PNP_CHECK_ONE_KERNEL_PLAN(p);
     {   // as pnp_csmri_saga_step: table [hist][batch][H][W] and sum [batch][H][W] are written while z and xrec are read or written
         const size_t img = (size_t)p->batch * 256 * 256 * sizeof(float);
-        auto overlap = [](const void* x, size_t nx, const void* y, size_t ny) {
-            const uintptr_t a0 = (uintptr_t)x, b0 = (uintptr_t)y;
-            return x != nullptr && y != nullptr && a0 < b0 + ny && b0 < a0 + nx;
-        };
         const size_t tb = img * (size_t)hist;
         PNP_CHECK_ARG(!overlap(table, tb, z, img) && !overlap(table, tb, xrec, img) && !overlap(sum, img, z, img) &&
                       !overlap(sum, img, xrec, img) && !overlap(table, tb, sum, img), "table and sum must not alias z, xrec or each other");

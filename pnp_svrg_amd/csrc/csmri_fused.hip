@@ -39,6 +39,7 @@
 // between wavefronts.  DENOISE = false stops after the noise estimate and stores the stepped image (the DnCNN prox takes
 // over from there).
 #include "fft.h"
+#include "csmri_fused.h"
 #include <type_traits>
 #include <cstdlib>
 
@@ -725,10 +726,7 @@ __device__ __forceinline__ void saga_epilogue(RImg& R, const SagaArgs& sa, const
 
 namespace pnp {
 
-// MODE: 0 = the whole iteration; 1 = stop after the noise estimate and store the stepped image (another prox follows);
-//       2 = the gradient only (phases 1-3: grad_full with its data term, or any other use of pnp_csmri_grad_sel that fits
-//           this kernel); 3 = the whole iteration with the 2-D wavelet prox (csmri_fused_w2d.h) in place of the per-column one.
-enum { FUSED_FULL = 0, FUSED_NO_DENOISE = 1, FUSED_GRAD = 2, FUSED_FULL_W2D = 3 };
+// (MODE of the kernels below: FUSED_FULL / FUSED_NO_DENOISE / FUSED_GRAD / FUSED_FULL_W2D of csmri_fused.h)
 // the LDS a workgroup needs beside the 132 KB hand-over buffer
 struct FusedShared {
     cx<float> twl[FN];
@@ -1547,8 +1545,55 @@ __global__ __launch_bounds__(FT) void k_svrg_outer_prox(float* z, float* w, floa
     }
 }
 
-// stagger (see startup_stagger): only launches of more than one workgroup per CU pay for it and profit from it
-static int stagger_config(int* num_cu_out, int* groups, int* units) {
+// > 64 KiB of dynamic LDS needs the opt-in, once per device (the attribute is per device).  The ONE list: every instantiation that a
+// launcher below can launch is named here -- a kernel that is missing has its launch refused ("invalid argument").  Taking a template
+// kernel's address instantiates it, and the code object holds the kernels in the order of their first use in this file: a new kernel
+// goes to the END of the list (several kernels are templates only to be emitted behind the older ones).
+static int fused_lds_optin() {
+    static unsigned long long attr_done = 0;
+    int dev = 0;
+    PNP_CHECK_HIP(hipGetDevice(&dev));
+    if ((attr_done >> (dev & 63)) & 1ull) return PNP_OK;
+#define PNP_OPTIN(...) PNP_CHECK_HIP(hipFuncSetAttribute((const void*)__VA_ARGS__, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F_LDS_BYTES))
+    // csmri_fused_launch
+    PNP_OPTIN(k_svrg_iter<0, false, 0>); PNP_OPTIN(k_svrg_iter<0, false, 1>); PNP_OPTIN(k_svrg_iter<0, false, 2>);
+    PNP_OPTIN(k_svrg_iter<1, false, 0>); PNP_OPTIN(k_svrg_iter<1, false, 1>); PNP_OPTIN(k_svrg_iter<1, false, 2>);
+    PNP_OPTIN(k_svrg_iter<2, false, 0>); PNP_OPTIN(k_svrg_iter<2, false, 1>); PNP_OPTIN(k_svrg_iter<2, false, 2>);
+    PNP_OPTIN(k_svrg_iter<0, true, 0>); PNP_OPTIN(k_svrg_iter<1, true, 0>);
+    PNP_OPTIN(k_svrg_iter_pp<0, false, 0>); PNP_OPTIN(k_svrg_iter_pp<0, false, 1>); PNP_OPTIN(k_svrg_iter_pp<0, false, 2>);
+    PNP_OPTIN(k_svrg_iter_pp<1, false, 0>); PNP_OPTIN(k_svrg_iter_pp<1, false, 1>); PNP_OPTIN(k_svrg_iter_pp<1, false, 2>);
+    PNP_OPTIN(k_svrg_iter_pp<2, false, 0>); PNP_OPTIN(k_svrg_iter_pp<2, false, 1>); PNP_OPTIN(k_svrg_iter_pp<2, false, 2>);
+    PNP_OPTIN(k_svrg_iter_pp<0, true, 0>); PNP_OPTIN(k_svrg_iter_pp<1, true, 0>);
+    PNP_OPTIN(k_svrg_iter_pp<3, false, 0>); PNP_OPTIN(k_svrg_iter_pp<3, false, 1>); PNP_OPTIN(k_svrg_iter_pp<3, false, 2>);
+    PNP_OPTIN(k_svrg_iter_pp<3, true, 0>);
+    // csmri_fused_outer_launch, csmri_fused_span_launch, csmri_sarah_outer_launch, csmri_step_span_launch, csmri_fused_outer_w2d_launch
+    PNP_OPTIN(k_svrg_outer); PNP_OPTIN(k_svrg_outer_pp); PNP_OPTIN(k_svrg_span_pp); PNP_OPTIN(k_sarah_outer);
+    PNP_OPTIN(k_grad_span<false>); PNP_OPTIN(k_grad_span<true>); PNP_OPTIN(k_saga_span); PNP_OPTIN(k_svrg_outer_prox<FUSED_FULL_W2D>);
+    // csmri_sarah_launch
+    PNP_OPTIN(k_sarah_iter<0, false>); PNP_OPTIN(k_sarah_iter<0, true>); PNP_OPTIN(k_sarah_iter<1, false>);
+    PNP_OPTIN(k_sarah_iter_pp<0, false>); PNP_OPTIN(k_sarah_iter_pp<0, true>); PNP_OPTIN(k_sarah_iter_pp<1, false>);
+    PNP_OPTIN(k_sarah_iter_pp<3, false>); PNP_OPTIN(k_sarah_iter_pp<3, true>);
+    // csmri_minibatch_launch
+    PNP_OPTIN(k_grad_step<0>); PNP_OPTIN(k_grad_step<1>); PNP_OPTIN(k_saga_iter<0>); PNP_OPTIN(k_saga_iter<1>);
+    PNP_OPTIN(k_grad_step<3>); PNP_OPTIN(k_saga_iter<3>);
+    // csmri_saga_hist_launch, csmri_sarah_span_launch
+    PNP_OPTIN(k_saga_iter_hist<0>); PNP_OPTIN(k_saga_iter_hist<1>); PNP_OPTIN(k_saga_span_hist<3>);
+    PNP_OPTIN(k_sarah_span_pp<0>);
+#undef PNP_OPTIN
+    attr_done |= 1ull << (dev & 63);
+    return PNP_OK;
+}
+
+// What every launcher needs in front of its <<<>>>: the stream, `alpha` with the transforms' 1 / N^2 folded in as the entry points have
+// always formed it, the stagger of a launch of `batch` workgroups (see startup_stagger: only launches of more than one workgroup per
+// CU pay for it and profit from it), and the LDS opt-in made.
+struct FusedLaunch {
+    hipStream_t s;
+    float scale;
+    int num_cu, st_groups, stagger_units;
+};
+
+static int fused_prologue(FusedLaunch* g, int batch, double alpha, void* stream) {
     static int num_cu = 0, st_groups = 2, st_units = 40;    // same-box sweep (tools/dev/stagger_sweep.py): 0.588 ms per config-2 step without, 0.575 with (2, 40), slower from (8, 20) on
     if (num_cu == 0) {
         int d0 = 0;
@@ -1556,72 +1601,39 @@ static int stagger_config(int* num_cu_out, int* groups, int* units) {
         PNP_CHECK_HIP(hipGetDevice(&d0));
         PNP_CHECK_HIP(hipGetDeviceProperties(&prop, d0));
         if (const char* ev = getenv("PNP_FUSED_STAGGER")) {   // "groups,units" (A/B timing); "0" switches it off
-            int g = 0, u = 0;
-            if (sscanf(ev, "%d,%d", &g, &u) == 2 && g >= 1 && u >= 0) { st_groups = g; st_units = u; }
+            int gr = 0, u = 0;
+            if (sscanf(ev, "%d,%d", &gr, &u) == 2 && gr >= 1 && u >= 0) { st_groups = gr; st_units = u; }
             else st_units = 0;
         }
         num_cu = prop.multiProcessorCount;
     }
-    *num_cu_out = num_cu; *groups = st_groups; *units = st_units;
-    return PNP_OK;
+    *g = {(hipStream_t)stream, (float)(alpha / ((double)FN * (double)FN)), num_cu, st_groups, batch > num_cu ? st_units : 0};
+    return fused_lds_optin();
 }
-
-static int fused_lds_optin() {
-    // > 64 KiB of dynamic LDS needs the opt-in, once per device (the attribute is per device)
-    static unsigned long long attr_done = 0;
-    int dev = 0;
-    PNP_CHECK_HIP(hipGetDevice(&dev));
-    if (!((attr_done >> (dev & 63)) & 1ull)) {
-#define PNP_FUSED_ATTR(...) PNP_CHECK_HIP(hipFuncSetAttribute((const void*)k_svrg_iter<__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F_LDS_BYTES))
-        PNP_FUSED_ATTR(0, false, 0); PNP_FUSED_ATTR(0, false, 1); PNP_FUSED_ATTR(0, false, 2);
-        PNP_FUSED_ATTR(1, false, 0); PNP_FUSED_ATTR(1, false, 1); PNP_FUSED_ATTR(1, false, 2);
-        PNP_FUSED_ATTR(2, false, 0); PNP_FUSED_ATTR(2, false, 1); PNP_FUSED_ATTR(2, false, 2);
-        PNP_FUSED_ATTR(0, true, 0); PNP_FUSED_ATTR(1, true, 0);
-#undef PNP_FUSED_ATTR
-#define PNP_FUSED_ATTR(...) PNP_CHECK_HIP(hipFuncSetAttribute((const void*)k_svrg_iter_pp<__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F_LDS_BYTES))
-        PNP_FUSED_ATTR(0, false, 0); PNP_FUSED_ATTR(0, false, 1); PNP_FUSED_ATTR(0, false, 2);
-        PNP_FUSED_ATTR(1, false, 0); PNP_FUSED_ATTR(1, false, 1); PNP_FUSED_ATTR(1, false, 2);
-        PNP_FUSED_ATTR(2, false, 0); PNP_FUSED_ATTR(2, false, 1); PNP_FUSED_ATTR(2, false, 2);
-        PNP_FUSED_ATTR(0, true, 0); PNP_FUSED_ATTR(1, true, 0);
-        PNP_FUSED_ATTR(3, false, 0); PNP_FUSED_ATTR(3, false, 1); PNP_FUSED_ATTR(3, false, 2); PNP_FUSED_ATTR(3, true, 0);
-#undef PNP_FUSED_ATTR
-        PNP_CHECK_HIP(hipFuncSetAttribute((const void*)k_svrg_outer, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F_LDS_BYTES));
-        PNP_CHECK_HIP(hipFuncSetAttribute((const void*)k_svrg_outer_pp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F_LDS_BYTES));
-        PNP_CHECK_HIP(hipFuncSetAttribute((const void*)k_svrg_span_pp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F_LDS_BYTES));
-        PNP_CHECK_HIP(hipFuncSetAttribute((const void*)k_sarah_outer, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F_LDS_BYTES));
-        PNP_CHECK_HIP(hipFuncSetAttribute((const void*)k_grad_span<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F_LDS_BYTES));
-        PNP_CHECK_HIP(hipFuncSetAttribute((const void*)k_grad_span<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F_LDS_BYTES));
-        PNP_CHECK_HIP(hipFuncSetAttribute((const void*)k_saga_span, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F_LDS_BYTES));
-        PNP_CHECK_HIP(hipFuncSetAttribute((const void*)k_svrg_outer_prox<FUSED_FULL_W2D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F_LDS_BYTES));
-        attr_done |= 1ull << (dev & 63);
-    }
-    return PNP_OK;
-}
+// (declares the FusedLaunch `g` and returns the prologue's error from the launcher)
+#define PNP_FUSED_PROLOGUE(g, batch, alpha, stream) \
+    FusedLaunch g; do { const int rc_ = fused_prologue(&g, batch, alpha, stream); if (rc_ != PNP_OK) return rc_; } while (0)
 
 // one launch = one outer iteration (k_svrg_outer); scales computed exactly as the per-iteration entry points compute them
 int csmri_fused_outer_launch(int batch, const void* twtab, void* z, void* w, void* mu, const uint32_t* mask_bits, const void* yh,
                              const void* alpha_vec, const uint32_t* selbits, int T2, double lr, int mini_batch_size,
                              double sigma_modifier, double fallback_sigma, const void* xrec, double* sse_log, int log_row0, int n_log,
                              void* sigma_out, void* stream, const double* lr_pp, const int32_t* mb_vec, const double* sm_pp) {
-    int num_cu = 0, st_groups = 0, st_units = 0;
-    { const int rc = stagger_config(&num_cu, &st_groups, &st_units); if (rc != PNP_OK) return rc; }
-    { const int rc = fused_lds_optin(); if (rc != PNP_OK) return rc; }
-    if (lr_pp != nullptr || mb_vec != nullptr || sm_pp != nullptr) {    // per-problem form: the coefficients are made in the kernel
-        k_svrg_outer_pp<<<batch, FT, F_LDS_BYTES, (hipStream_t)stream>>>((float*)z, (float*)w, (float*)mu, mask_bits, (const cx<float>*)yh,
-                                                                        (const float*)alpha_vec, selbits, T2, lr, lr_pp, mini_batch_size,
-                                                                        mb_vec, (const cx<float>*)twtab, (float)sigma_modifier, sm_pp,
-                                                                        (float)fallback_sigma, (const float*)xrec, sse_log, log_row0,
-                                                                        n_log, (float*)sigma_out);
+    const bool pp = lr_pp != nullptr || mb_vec != nullptr || sm_pp != nullptr;
+    PNP_FUSED_PROLOGUE(g, batch, pp ? 0.0 : -lr / (double)mini_batch_size, stream);    // (g.scale: the inner iterations' alpha of the scalar form)
+    if (pp) {                                                   // per-problem form: the coefficients are made in the kernel
+        k_svrg_outer_pp<<<batch, FT, F_LDS_BYTES, g.s>>>((float*)z, (float*)w, (float*)mu, mask_bits, (const cx<float>*)yh,
+                                                        (const float*)alpha_vec, selbits, T2, lr, lr_pp, mini_batch_size, mb_vec,
+                                                        (const cx<float>*)twtab, (float)sigma_modifier, sm_pp, (float)fallback_sigma,
+                                                        (const float*)xrec, sse_log, log_row0, n_log, (float*)sigma_out);
         PNP_CHECK_LAUNCH();
         return PNP_OK;
     }
-    const double alpha = -lr / (double)mini_batch_size;
-    const float scale_inner = (float)(alpha / ((double)FN * (double)FN));
-    k_svrg_outer<<<batch, FT, F_LDS_BYTES, (hipStream_t)stream>>>((float*)z, (float*)w, (float*)mu, mask_bits, (const cx<float>*)yh,
-                                                                 (const float*)alpha_vec, selbits, T2, scale_inner, (float)(-lr),
-                                                                 (const cx<float>*)twtab, (float)sigma_modifier, (float)fallback_sigma,
-                                                                 (const float*)xrec, sse_log, log_row0, n_log, (float*)sigma_out, num_cu,
-                                                                 st_groups, 0);     // (no stagger: same-box A/B 0.539 ms per step without, 0.546 with (2, 40))
+    k_svrg_outer<<<batch, FT, F_LDS_BYTES, g.s>>>((float*)z, (float*)w, (float*)mu, mask_bits, (const cx<float>*)yh,
+                                                 (const float*)alpha_vec, selbits, T2, g.scale, (float)(-lr), (const cx<float>*)twtab,
+                                                 (float)sigma_modifier, (float)fallback_sigma, (const float*)xrec, sse_log, log_row0,
+                                                 n_log, (float*)sigma_out, g.num_cu, g.st_groups,
+                                                 0);     // (no stagger: same-box A/B 0.539 ms per step without, 0.546 with (2, 40))
     PNP_CHECK_LAUNCH();
     return PNP_OK;
 }
@@ -1632,8 +1644,8 @@ int csmri_fused_outer_w2d_launch(int batch, const void* twtab, void* z, void* w,
                                  int mini_batch_size, const int32_t* mb_vec, double sigma_modifier, const double* sm_pp,
                                  double fallback_sigma, const void* xrec, double* sse_log, int log_row0, int n_log, void* sigma_out,
                                  void* stream) {
-    { const int rc = fused_lds_optin(); if (rc != PNP_OK) return rc; }
-    k_svrg_outer_prox<FUSED_FULL_W2D><<<batch, FT, F_LDS_BYTES, (hipStream_t)stream>>>(
+    PNP_FUSED_PROLOGUE(g, batch, 0.0, stream);
+    k_svrg_outer_prox<FUSED_FULL_W2D><<<batch, FT, F_LDS_BYTES, g.s>>>(
         (float*)z, (float*)w, (float*)mu, mask_bits, (const cx<float>*)yh, (const float*)alpha_vec, selbits, T2, lr, lr_pp, mini_batch_size,
         mb_vec, (const cx<float>*)twtab, (float)sigma_modifier, sm_pp, (float)fallback_sigma, (const float*)xrec, sse_log, log_row0, n_log,
         (float*)sigma_out);
@@ -1647,12 +1659,11 @@ int csmri_fused_span_launch(int batch, const void* twtab, void* z, void* w, void
                             double lr, const double* lr_pp, int mini_batch_size, const int32_t* mb_vec, double sigma_modifier,
                             const double* sm_pp, double fallback_sigma, const void* xrec, double* sse_log, int log_row0, int n_log,
                             void* sigma_out, void* stream) {
-    { const int rc = fused_lds_optin(); if (rc != PNP_OK) return rc; }
-    k_svrg_span_pp<<<batch, FT, F_LDS_BYTES, (hipStream_t)stream>>>((float*)z, (float*)w, (float*)mu, mask_bits, (const cx<float>*)yh,
-                                                                   (const float*)alpha_vec, selbits, step0, n_steps, T2, t2_vec, lr, lr_pp,
-                                                                   mini_batch_size, mb_vec, (const cx<float>*)twtab, (float)sigma_modifier,
-                                                                   sm_pp, (float)fallback_sigma, (const float*)xrec, sse_log, log_row0,
-                                                                   n_log, (float*)sigma_out);
+    PNP_FUSED_PROLOGUE(g, batch, 0.0, stream);
+    k_svrg_span_pp<<<batch, FT, F_LDS_BYTES, g.s>>>((float*)z, (float*)w, (float*)mu, mask_bits, (const cx<float>*)yh, (const float*)alpha_vec,
+                                                   selbits, step0, n_steps, T2, t2_vec, lr, lr_pp, mini_batch_size, mb_vec,
+                                                   (const cx<float>*)twtab, (float)sigma_modifier, sm_pp, (float)fallback_sigma,
+                                                   (const float*)xrec, sse_log, log_row0, n_log, (float*)sigma_out);
     PNP_CHECK_LAUNCH();
     return PNP_OK;
 }
@@ -1663,37 +1674,34 @@ int csmri_sarah_outer_launch(int batch, const void* twtab, void* z, void* w_prev
                              double lr, const double* lr_pp, int mini_batch_size, const int32_t* mb_vec, double sigma_modifier,
                              const double* sm_pp, double fallback_sigma, const void* xrec, double* sse_log, int log_row0, int n_log,
                              void* sigma_out, void* stream) {
-    { const int rc = fused_lds_optin(); if (rc != PNP_OK) return rc; }
-    k_sarah_outer<<<batch, FT, F_LDS_BYTES, (hipStream_t)stream>>>((float*)z, (float*)w_prev, (float*)w_next, (float*)v_prev, mask_bits,
-                                                                  (const cx<float>*)yh, (const float*)alpha_vec, selbits, T2, eta, eta_pp, lr,
-                                                                  lr_pp, mini_batch_size, mb_vec, (const cx<float>*)twtab,
-                                                                  (float)sigma_modifier, sm_pp, (float)fallback_sigma, (const float*)xrec,
-                                                                  sse_log, log_row0, n_log, (float*)sigma_out);
+    PNP_FUSED_PROLOGUE(g, batch, 0.0, stream);
+    k_sarah_outer<<<batch, FT, F_LDS_BYTES, g.s>>>((float*)z, (float*)w_prev, (float*)w_next, (float*)v_prev, mask_bits, (const cx<float>*)yh,
+                                                  (const float*)alpha_vec, selbits, T2, eta, eta_pp, lr, lr_pp, mini_batch_size, mb_vec,
+                                                  (const cx<float>*)twtab, (float)sigma_modifier, sm_pp, (float)fallback_sigma,
+                                                  (const float*)xrec, sse_log, log_row0, n_log, (float*)sigma_out);
     PNP_CHECK_LAUNCH();
     return PNP_OK;
 }
 
 // one launch = n_steps GD / SGD (table == NULL; YT != NULL selects the SGD form) or SAGA inner iterations of every problem, z in place
-// (k_grad_span, k_saga_span); scale and casts as csmri_minibatch_launch
+// (k_grad_span, k_saga_span); casts as csmri_minibatch_launch
 int csmri_step_span_launch(int batch, const void* twtab, void* z, const uint32_t* bits, const void* yh, const void* YT, double alpha,
                            const void* alpha_vec, double beta, void* table, const int32_t* rows, const int32_t* prev_row0, void* sum,
                            double lr, double inv_hist, int n_steps, double sigma_modifier, double fallback_sigma, const void* xrec,
                            double* sse_log, int log_row0, int n_log, void* sigma_out, void* stream, const double* alpha_pp,
                            const double* lr_pp, const double* sm_pp) {
-    const float scale = (float)(alpha / ((double)FN * (double)FN));
-    hipStream_t s = (hipStream_t)stream;
-    { const int rc = fused_lds_optin(); if (rc != PNP_OK) return rc; }
+    PNP_FUSED_PROLOGUE(g, batch, alpha, stream);
     if (table != nullptr) {
-        k_saga_span<<<batch, FT, F_LDS_BYTES, s>>>((float*)z, bits, (const cx<float>*)YT, (const cx<float>*)twtab, scale, (const float*)alpha_vec,
-                                                  (float*)table, rows, prev_row0, (float*)sum, (float)lr, (float)inv_hist, n_steps,
-                                                  (float)sigma_modifier, (float)fallback_sigma, (const float*)xrec, sse_log, log_row0, n_log,
-                                                  (float*)sigma_out, alpha_pp, lr_pp, sm_pp);
+        k_saga_span<<<batch, FT, F_LDS_BYTES, g.s>>>((float*)z, bits, (const cx<float>*)YT, (const cx<float>*)twtab, g.scale,
+                                                    (const float*)alpha_vec, (float*)table, rows, prev_row0, (float*)sum, (float)lr,
+                                                    (float)inv_hist, n_steps, (float)sigma_modifier, (float)fallback_sigma,
+                                                    (const float*)xrec, sse_log, log_row0, n_log, (float*)sigma_out, alpha_pp, lr_pp, sm_pp);
     } else {
-#define PNP_GSPAN_ARGS (float*)z, bits, (const cx<float>*)yh, (const cx<float>*)YT, (const cx<float>*)twtab, scale, (const float*)alpha_vec,   \
+#define PNP_GSPAN_ARGS (float*)z, bits, (const cx<float>*)yh, (const cx<float>*)YT, (const cx<float>*)twtab, g.scale, (const float*)alpha_vec, \
                        (float)beta, n_steps, (float)sigma_modifier, (float)fallback_sigma, (const float*)xrec, sse_log, log_row0, n_log,     \
                        (float*)sigma_out, alpha_pp, sm_pp
-        if (YT != nullptr) k_grad_span<true><<<batch, FT, F_LDS_BYTES, s>>>(PNP_GSPAN_ARGS);
-        else k_grad_span<false><<<batch, FT, F_LDS_BYTES, s>>>(PNP_GSPAN_ARGS);
+        if (YT != nullptr) k_grad_span<true><<<batch, FT, F_LDS_BYTES, g.s>>>(PNP_GSPAN_ARGS);
+        else k_grad_span<false><<<batch, FT, F_LDS_BYTES, g.s>>>(PNP_GSPAN_ARGS);
 #undef PNP_GSPAN_ARGS
     }
     PNP_CHECK_LAUNCH();
@@ -1706,29 +1714,24 @@ int csmri_fused_launch(int batch, const void* twtab, const void* a, const void* 
                        double alpha, const void* alpha_vec, double beta, const void* c1, double gamma, const void* c2, void* out,
                        int mode, double sigma_modifier, double fallback_sigma, const void* xrec, double* sse_out, void* sigma_out,
                        void* stream, void* w_out, void* mu_out, const double* alpha_pp, const double* gamma_pp, const double* sm_pp) {
-    const float scale = (float)(alpha / ((double)FN * (double)FN));
     const bool pp = alpha_pp != nullptr || gamma_pp != nullptr || sm_pp != nullptr;
     // (a lone c2 moves to the first operand slot below and its coefficient becomes beta, which has no per-problem form)
     PNP_CHECK_ARG(!(gamma_pp != nullptr && c1 == nullptr && c2 != nullptr), "per-problem gamma needs c1 beside c2 in the one-kernel form");
-    hipStream_t s = (hipStream_t)stream;
-    int num_cu = 0, st_groups = 0, st_units = 0;
-    { const int rc = stagger_config(&num_cu, &st_groups, &st_units); if (rc != PNP_OK) return rc; }
-    const int stagger_units = batch > num_cu ? st_units : 0;
-    { const int rc = fused_lds_optin(); if (rc != PNP_OK) return rc; }
+    PNP_FUSED_PROLOGUE(g, batch, alpha, stream);
     // epilogue operands as the kernel takes them: (c1, beta) first, then (c2, gamma); a lone c2 moves to the first slot
     int nops = (c1 != nullptr ? 1 : 0) + (c2 != nullptr ? 1 : 0);
     if (c1 == nullptr && c2 != nullptr) { c1 = c2; beta = gamma; c2 = nullptr; }
     const bool outer = w_out != nullptr;
-#define PNP_FUSED_ARGS (const float*)a, (const float*)b, bitsT, (const cx<float>*)yh, (const cx<float>*)twtab, scale,                \
+#define PNP_FUSED_ARGS (const float*)a, (const float*)b, bitsT, (const cx<float>*)yh, (const cx<float>*)twtab, g.scale,              \
                        (const float*)alpha_vec, (float)beta, (const float*)c1, (float)gamma, (const float*)c2, (float*)out,         \
                        (float)sigma_modifier, (float)fallback_sigma, (const float*)xrec, sse_out, (float*)sigma_out, (float*)w_out, \
-                       (float*)mu_out, num_cu, st_groups, stagger_units
+                       (float*)mu_out, g.num_cu, g.st_groups, g.stagger_units
 #define PNP_FUSED_LAUNCH(...)                                                                                             \
-    do { if (pp) k_svrg_iter_pp<__VA_ARGS__><<<batch, FT, F_LDS_BYTES, s>>>(PNP_FUSED_ARGS, alpha_pp, gamma_pp, sm_pp);     \
-         else k_svrg_iter<__VA_ARGS__><<<batch, FT, F_LDS_BYTES, s>>>(PNP_FUSED_ARGS); } while (0)
+    do { if (pp) k_svrg_iter_pp<__VA_ARGS__><<<batch, FT, F_LDS_BYTES, g.s>>>(PNP_FUSED_ARGS, alpha_pp, gamma_pp, sm_pp);   \
+         else k_svrg_iter<__VA_ARGS__><<<batch, FT, F_LDS_BYTES, g.s>>>(PNP_FUSED_ARGS); } while (0)
     // the 2-D prox: ONE kernel serves the plain and the _pp entry point (as k_grad_step) -- with the three arrays NULL k_svrg_iter_pp
     // keeps the scalars the host converted, which is the plain call
-#define PNP_FUSED_LAUNCH_W2D(...) k_svrg_iter_pp<3, __VA_ARGS__><<<batch, FT, F_LDS_BYTES, s>>>(PNP_FUSED_ARGS, alpha_pp, gamma_pp, sm_pp)
+#define PNP_FUSED_LAUNCH_W2D(...) k_svrg_iter_pp<3, __VA_ARGS__><<<batch, FT, F_LDS_BYTES, g.s>>>(PNP_FUSED_ARGS, alpha_pp, gamma_pp, sm_pp)
 #define PNP_FUSED_BY_NOPS(MD)                                                     \
     do { if (nops == 0) PNP_FUSED_LAUNCH(MD, false, 0); else if (nops == 1) PNP_FUSED_LAUNCH(MD, false, 1); else PNP_FUSED_LAUNCH(MD, false, 2); } while (0)
     if (outer) {                                                // the outer refresh folded into the first inner iteration
@@ -1749,39 +1752,22 @@ int csmri_fused_launch(int batch, const void* twtab, const void* a, const void* 
     return PNP_OK;
 }
 
-// the SARAH form (pnp_csmri_sarah_step[_pp]); mode: FUSED_FULL / FUSED_NO_DENOISE / FUSED_FULL_W2D; out2 may be NULL; scale and casts as csmri_fused_launch
+// the SARAH form (pnp_csmri_sarah_step[_pp]); mode: FUSED_FULL / FUSED_NO_DENOISE / FUSED_FULL_W2D; out2 may be NULL; casts as csmri_fused_launch
 int csmri_sarah_launch(int batch, const void* twtab, const void* a, const void* b, const uint32_t* bitsT, double alpha,
                        const void* alpha_vec, double beta, const void* c1, double gamma, const void* c2, void* v_out, void* out,
                        void* out2, int mode, double sigma_modifier, double fallback_sigma, const void* xrec, double* sse_out,
                        void* sigma_out, void* stream, const double* alpha_pp, const double* gamma_pp, const double* sm_pp) {
-    const float scale = (float)(alpha / ((double)FN * (double)FN));
     const bool pp = alpha_pp != nullptr || gamma_pp != nullptr || sm_pp != nullptr;
-    hipStream_t s = (hipStream_t)stream;
-    int num_cu = 0, st_groups = 0, st_units = 0;
-    { const int rc = stagger_config(&num_cu, &st_groups, &st_units); if (rc != PNP_OK) return rc; }
-    const int stagger_units = batch > num_cu ? st_units : 0;
-    {   // > 64 KiB of dynamic LDS needs the opt-in, once per device (as fused_lds_optin)
-        static unsigned long long attr_done = 0;
-        int dev = 0;
-        PNP_CHECK_HIP(hipGetDevice(&dev));
-        if (!((attr_done >> (dev & 63)) & 1ull)) {
-#define PNP_SARAH_ATTR(K, ...) PNP_CHECK_HIP(hipFuncSetAttribute((const void*)K<__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F_LDS_BYTES))
-            PNP_SARAH_ATTR(k_sarah_iter, 0, false); PNP_SARAH_ATTR(k_sarah_iter, 0, true); PNP_SARAH_ATTR(k_sarah_iter, 1, false);
-            PNP_SARAH_ATTR(k_sarah_iter_pp, 0, false); PNP_SARAH_ATTR(k_sarah_iter_pp, 0, true); PNP_SARAH_ATTR(k_sarah_iter_pp, 1, false);
-            PNP_SARAH_ATTR(k_sarah_iter_pp, 3, false); PNP_SARAH_ATTR(k_sarah_iter_pp, 3, true);
-#undef PNP_SARAH_ATTR
-            attr_done |= 1ull << (dev & 63);
-        }
-    }
-#define PNP_SARAH_ARGS (const float*)a, (const float*)b, bitsT, (const cx<float>*)twtab, scale, (const float*)alpha_vec, (float)beta,   \
+    PNP_FUSED_PROLOGUE(g, batch, alpha, stream);
+#define PNP_SARAH_ARGS (const float*)a, (const float*)b, bitsT, (const cx<float>*)twtab, g.scale, (const float*)alpha_vec, (float)beta, \
                        (const float*)c1, (float)gamma, (const float*)c2, (float*)v_out, (float*)out, (float*)out2, (float)sigma_modifier, \
-                       (float)fallback_sigma, (const float*)xrec, sse_out, (float*)sigma_out, num_cu, st_groups, stagger_units
+                       (float)fallback_sigma, (const float*)xrec, sse_out, (float*)sigma_out, g.num_cu, g.st_groups, g.stagger_units
 #define PNP_SARAH_LAUNCH(...)                                                                                             \
-    do { if (pp) k_sarah_iter_pp<__VA_ARGS__><<<batch, FT, F_LDS_BYTES, s>>>(PNP_SARAH_ARGS, alpha_pp, gamma_pp, sm_pp);    \
-         else k_sarah_iter<__VA_ARGS__><<<batch, FT, F_LDS_BYTES, s>>>(PNP_SARAH_ARGS); } while (0)
+    do { if (pp) k_sarah_iter_pp<__VA_ARGS__><<<batch, FT, F_LDS_BYTES, g.s>>>(PNP_SARAH_ARGS, alpha_pp, gamma_pp, sm_pp);  \
+         else k_sarah_iter<__VA_ARGS__><<<batch, FT, F_LDS_BYTES, g.s>>>(PNP_SARAH_ARGS); } while (0)
     if (mode == FUSED_FULL_W2D) {                               // the 2-D prox: ONE kernel serves the plain and the _pp entry point
-        if (out2 != nullptr) k_sarah_iter_pp<3, true><<<batch, FT, F_LDS_BYTES, s>>>(PNP_SARAH_ARGS, alpha_pp, gamma_pp, sm_pp);
-        else k_sarah_iter_pp<3, false><<<batch, FT, F_LDS_BYTES, s>>>(PNP_SARAH_ARGS, alpha_pp, gamma_pp, sm_pp);
+        if (out2 != nullptr) k_sarah_iter_pp<3, true><<<batch, FT, F_LDS_BYTES, g.s>>>(PNP_SARAH_ARGS, alpha_pp, gamma_pp, sm_pp);
+        else k_sarah_iter_pp<3, false><<<batch, FT, F_LDS_BYTES, g.s>>>(PNP_SARAH_ARGS, alpha_pp, gamma_pp, sm_pp);
     }
     else if (mode != FUSED_FULL) PNP_SARAH_LAUNCH(1, false);
     else if (out2 != nullptr) PNP_SARAH_LAUNCH(0, true);
@@ -1792,87 +1778,57 @@ int csmri_sarah_launch(int batch, const void* twtab, const void* a, const void* 
     return PNP_OK;
 }
 
-// the minibatch forms (pnp_csmri_grad_step[_pp] with YT, pnp_csmri_saga_step[_pp]); mode: FUSED_FULL / FUSED_NO_DENOISE / FUSED_FULL_W2D; scale and
-// casts as csmri_fused_launch.  saga: table != NULL selects k_saga_iter (c1 and beta are then not used)
+// the minibatch forms (pnp_csmri_grad_step[_pp] with YT, pnp_csmri_saga_step[_pp]); mode: FUSED_FULL / FUSED_NO_DENOISE / FUSED_FULL_W2D; casts
+// as csmri_fused_launch.  saga: table != NULL selects k_saga_iter (c1 and beta are then not used)
 int csmri_minibatch_launch(int batch, const void* twtab, const void* a, const uint32_t* bitsT, const void* YT, double alpha,
                            const void* alpha_vec, double beta, const void* c1, void* table, const int32_t* row, const int32_t* prev_row,
                            void* sum, double lr, double inv_hist, void* out, int mode, double sigma_modifier, double fallback_sigma,
                            const void* xrec, double* sse_out, void* sigma_out, void* stream, const double* alpha_pp, const double* lr_pp,
                            const double* sm_pp) {
-    const float scale = (float)(alpha / ((double)FN * (double)FN));
-    hipStream_t s = (hipStream_t)stream;
-    int num_cu = 0, st_groups = 0, st_units = 0;
-    { const int rc = stagger_config(&num_cu, &st_groups, &st_units); if (rc != PNP_OK) return rc; }
-    const int stagger_units = batch > num_cu ? st_units : 0;
-    {   // > 64 KiB of dynamic LDS needs the opt-in, once per device (as fused_lds_optin)
-        static unsigned long long attr_done = 0;
-        int dev = 0;
-        PNP_CHECK_HIP(hipGetDevice(&dev));
-        if (!((attr_done >> (dev & 63)) & 1ull)) {
-#define PNP_MB_ATTR(K, M) PNP_CHECK_HIP(hipFuncSetAttribute((const void*)K<M>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F_LDS_BYTES))
-            PNP_MB_ATTR(k_grad_step, 0); PNP_MB_ATTR(k_grad_step, 1); PNP_MB_ATTR(k_saga_iter, 0); PNP_MB_ATTR(k_saga_iter, 1);
-            PNP_MB_ATTR(k_grad_step, 3); PNP_MB_ATTR(k_saga_iter, 3);
-#undef PNP_MB_ATTR
-            attr_done |= 1ull << (dev & 63);
-        }
-    }
+    PNP_FUSED_PROLOGUE(g, batch, alpha, stream);
     if (table != nullptr) {
-#define PNP_SAGA_ARGS (const float*)a, bitsT, (const cx<float>*)YT, (const cx<float>*)twtab, scale, (const float*)alpha_vec, (float*)table, \
-                      row, prev_row, (float*)sum, (float)lr, (float)inv_hist, (float*)out, (float)sigma_modifier, (float)fallback_sigma,     \
-                      (const float*)xrec, sse_out, (float*)sigma_out, num_cu, st_groups, stagger_units, alpha_pp, lr_pp, sm_pp
-        if (mode == FUSED_FULL) k_saga_iter<0><<<batch, FT, F_LDS_BYTES, s>>>(PNP_SAGA_ARGS);
-        else if (mode == FUSED_FULL_W2D) k_saga_iter<3><<<batch, FT, F_LDS_BYTES, s>>>(PNP_SAGA_ARGS);
-        else k_saga_iter<1><<<batch, FT, F_LDS_BYTES, s>>>(PNP_SAGA_ARGS);
+#define PNP_SAGA_ARGS (const float*)a, bitsT, (const cx<float>*)YT, (const cx<float>*)twtab, g.scale, (const float*)alpha_vec, (float*)table, \
+                      row, prev_row, (float*)sum, (float)lr, (float)inv_hist, (float*)out, (float)sigma_modifier, (float)fallback_sigma,       \
+                      (const float*)xrec, sse_out, (float*)sigma_out, g.num_cu, g.st_groups, g.stagger_units, alpha_pp, lr_pp, sm_pp
+        if (mode == FUSED_FULL) k_saga_iter<0><<<batch, FT, F_LDS_BYTES, g.s>>>(PNP_SAGA_ARGS);
+        else if (mode == FUSED_FULL_W2D) k_saga_iter<3><<<batch, FT, F_LDS_BYTES, g.s>>>(PNP_SAGA_ARGS);
+        else k_saga_iter<1><<<batch, FT, F_LDS_BYTES, g.s>>>(PNP_SAGA_ARGS);
 #undef PNP_SAGA_ARGS
     } else {
-#define PNP_GS_ARGS (const float*)a, bitsT, (const cx<float>*)YT, (const cx<float>*)twtab, scale, (const float*)alpha_vec, (float)beta, \
-                    (const float*)c1, (float*)out, (float)sigma_modifier, (float)fallback_sigma, (const float*)xrec, sse_out,            \
-                    (float*)sigma_out, num_cu, st_groups, stagger_units, alpha_pp, sm_pp
-        if (mode == FUSED_FULL) k_grad_step<0><<<batch, FT, F_LDS_BYTES, s>>>(PNP_GS_ARGS);
-        else if (mode == FUSED_FULL_W2D) k_grad_step<3><<<batch, FT, F_LDS_BYTES, s>>>(PNP_GS_ARGS);
-        else k_grad_step<1><<<batch, FT, F_LDS_BYTES, s>>>(PNP_GS_ARGS);
+#define PNP_GS_ARGS (const float*)a, bitsT, (const cx<float>*)YT, (const cx<float>*)twtab, g.scale, (const float*)alpha_vec, (float)beta, \
+                    (const float*)c1, (float*)out, (float)sigma_modifier, (float)fallback_sigma, (const float*)xrec, sse_out,              \
+                    (float*)sigma_out, g.num_cu, g.st_groups, g.stagger_units, alpha_pp, sm_pp
+        if (mode == FUSED_FULL) k_grad_step<0><<<batch, FT, F_LDS_BYTES, g.s>>>(PNP_GS_ARGS);
+        else if (mode == FUSED_FULL_W2D) k_grad_step<3><<<batch, FT, F_LDS_BYTES, g.s>>>(PNP_GS_ARGS);
+        else k_grad_step<1><<<batch, FT, F_LDS_BYTES, g.s>>>(PNP_GS_ARGS);
 #undef PNP_GS_ARGS
     }
     PNP_CHECK_LAUNCH();
     return PNP_OK;
 }
 
-// the SAGA forms with a per-problem divisor (pnp_csmri_saga_step_hist_pp, pnp_csmri_saga_span_hist): k_saga_iter_hist with the stagger,
-// scale and casts of csmri_minibatch_launch; n_steps > 0 selects k_saga_span_hist (row = rows [n_steps][batch], prev_row = prev_row0,
+// the SAGA forms with a per-problem divisor (pnp_csmri_saga_step_hist_pp, pnp_csmri_saga_span_hist): k_saga_iter_hist with the stagger
+// and casts of csmri_minibatch_launch; n_steps > 0 selects k_saga_span_hist (row = rows [n_steps][batch], prev_row = prev_row0,
 // sse_out = the log ring, a = z in place and `out`, `mode` not used) as csmri_step_span_launch launches k_saga_span
 int csmri_saga_hist_launch(int batch, const void* twtab, const void* a, const uint32_t* bitsT, const void* YT, double alpha,
                            const void* alpha_vec, void* table, const int32_t* row, const int32_t* prev_row, void* sum, double lr,
                            double inv_hist, void* out, int mode, double sigma_modifier, double fallback_sigma, const void* xrec,
                            double* sse_out, void* sigma_out, void* stream, const double* alpha_pp, const double* lr_pp, const double* sm_pp,
                            const double* inv_hist_pp, int n_steps, int log_row0, int n_log) {
-    const float scale = (float)(alpha / ((double)FN * (double)FN));
-    hipStream_t s = (hipStream_t)stream;
-    int num_cu = 0, st_groups = 0, st_units = 0;
-    { const int rc = stagger_config(&num_cu, &st_groups, &st_units); if (rc != PNP_OK) return rc; }
-    const int stagger_units = batch > num_cu ? st_units : 0;
-    {   // > 64 KiB of dynamic LDS needs the opt-in, once per device (as fused_lds_optin)
-        static unsigned long long attr_done = 0;
-        int dev = 0;
-        PNP_CHECK_HIP(hipGetDevice(&dev));
-        if (!((attr_done >> (dev & 63)) & 1ull)) {
-            PNP_CHECK_HIP(hipFuncSetAttribute((const void*)k_saga_iter_hist<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F_LDS_BYTES));
-            PNP_CHECK_HIP(hipFuncSetAttribute((const void*)k_saga_iter_hist<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F_LDS_BYTES));
-            PNP_CHECK_HIP(hipFuncSetAttribute((const void*)k_saga_span_hist<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F_LDS_BYTES));
-            attr_done |= 1ull << (dev & 63);
-        }
-    }
+    PNP_FUSED_PROLOGUE(g, batch, alpha, stream);
     if (n_steps > 0) {
-        k_saga_span_hist<3><<<batch, FT, F_LDS_BYTES, s>>>((float*)const_cast<void*>(a), bitsT, (const cx<float>*)YT, (const cx<float>*)twtab, scale,
-                                                       (const float*)alpha_vec, (float*)table, row, prev_row, (float*)sum, (float)lr,
-                                                       (float)inv_hist, n_steps, (float)sigma_modifier, (float)fallback_sigma,
-                                                       (const float*)xrec, sse_out, log_row0, n_log, (float*)sigma_out, alpha_pp, lr_pp, sm_pp,
-                                                       inv_hist_pp);
+        k_saga_span_hist<3><<<batch, FT, F_LDS_BYTES, g.s>>>((float*)const_cast<void*>(a), bitsT, (const cx<float>*)YT, (const cx<float>*)twtab,
+                                                            g.scale, (const float*)alpha_vec, (float*)table, row, prev_row, (float*)sum,
+                                                            (float)lr, (float)inv_hist, n_steps, (float)sigma_modifier, (float)fallback_sigma,
+                                                            (const float*)xrec, sse_out, log_row0, n_log, (float*)sigma_out, alpha_pp, lr_pp,
+                                                            sm_pp, inv_hist_pp);
     } else {
-#define PNP_SAGA_ARGS (const float*)a, bitsT, (const cx<float>*)YT, (const cx<float>*)twtab, scale, (const float*)alpha_vec, (float*)table, \
-                      row, prev_row, (float*)sum, (float)lr, (float)inv_hist, (float*)out, (float)sigma_modifier, (float)fallback_sigma,     \
-                      (const float*)xrec, sse_out, (float*)sigma_out, num_cu, st_groups, stagger_units, alpha_pp, lr_pp, sm_pp, inv_hist_pp
-        if (mode == FUSED_FULL) k_saga_iter_hist<0><<<batch, FT, F_LDS_BYTES, s>>>(PNP_SAGA_ARGS);
-        else k_saga_iter_hist<1><<<batch, FT, F_LDS_BYTES, s>>>(PNP_SAGA_ARGS);
+#define PNP_SAGA_ARGS (const float*)a, bitsT, (const cx<float>*)YT, (const cx<float>*)twtab, g.scale, (const float*)alpha_vec, (float*)table, \
+                      row, prev_row, (float*)sum, (float)lr, (float)inv_hist, (float*)out, (float)sigma_modifier, (float)fallback_sigma,       \
+                      (const float*)xrec, sse_out, (float*)sigma_out, g.num_cu, g.st_groups, g.stagger_units, alpha_pp, lr_pp, sm_pp,         \
+                      inv_hist_pp
+        if (mode == FUSED_FULL) k_saga_iter_hist<0><<<batch, FT, F_LDS_BYTES, g.s>>>(PNP_SAGA_ARGS);
+        else k_saga_iter_hist<1><<<batch, FT, F_LDS_BYTES, g.s>>>(PNP_SAGA_ARGS);
 #undef PNP_SAGA_ARGS
     }
     PNP_CHECK_LAUNCH();
@@ -1885,21 +1841,12 @@ int csmri_sarah_span_launch(int batch, const void* twtab, void* z, void* w_prev,
                             const int32_t* t2_vec, double eta, const double* eta_pp, double lr, const double* lr_pp, int mini_batch_size,
                             const int32_t* mb_vec, double sigma_modifier, const double* sm_pp, double fallback_sigma, const void* xrec,
                             double* sse_log, double* outer_log, int log_row0, int n_log, void* sigma_out, void* stream) {
-    {   // > 64 KiB of dynamic LDS needs the opt-in, once per device (as fused_lds_optin; here: the kernel's first use in the file)
-        static unsigned long long attr_done = 0;
-        int dev = 0;
-        PNP_CHECK_HIP(hipGetDevice(&dev));
-        if (!((attr_done >> (dev & 63)) & 1ull)) {
-            PNP_CHECK_HIP(hipFuncSetAttribute((const void*)k_sarah_span_pp<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F_LDS_BYTES));
-            attr_done |= 1ull << (dev & 63);
-        }
-    }
-    k_sarah_span_pp<0><<<batch, FT, F_LDS_BYTES, (hipStream_t)stream>>>((float*)z, (float*)w_prev, (float*)w_next, (float*)v_prev, mask_bits,
-                                                                       (const cx<float>*)yh, (const float*)alpha_vec, selbits, step0, n_steps,
-                                                                       T2, t2_vec, eta, eta_pp, lr, lr_pp, mini_batch_size, mb_vec,
-                                                                       (const cx<float>*)twtab, (float)sigma_modifier, sm_pp,
-                                                                       (float)fallback_sigma, (const float*)xrec, sse_log, outer_log, log_row0,
-                                                                       n_log, (float*)sigma_out);
+    PNP_FUSED_PROLOGUE(g, batch, 0.0, stream);
+    k_sarah_span_pp<0><<<batch, FT, F_LDS_BYTES, g.s>>>((float*)z, (float*)w_prev, (float*)w_next, (float*)v_prev, mask_bits,
+                                                       (const cx<float>*)yh, (const float*)alpha_vec, selbits, step0, n_steps, T2, t2_vec, eta,
+                                                       eta_pp, lr, lr_pp, mini_batch_size, mb_vec, (const cx<float>*)twtab,
+                                                       (float)sigma_modifier, sm_pp, (float)fallback_sigma, (const float*)xrec, sse_log,
+                                                       outer_log, log_row0, n_log, (float*)sigma_out);
     PNP_CHECK_LAUNCH();
     return PNP_OK;
 }
