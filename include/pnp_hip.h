@@ -458,6 +458,24 @@ int pnp_deblur_grad_pp(pnp_deblur_plan* plan, const void* z, const void* Y, cons
                        const double* scale_pp, void* out, void* stream);
 int pnp_deblur_grad_mb_pp(pnp_deblur_plan* plan, const void* z, const void* Y, const void* mbd, double scale,
                           const double* scale_pp, void* out, void* stream);
+/* The variance-reduced correction and the step in one gradient pass (pnp_svrg.py:53,57 / pnp_sarah.py:72-75):
+ *   out = beta*c1 + gamma_b*c2 + scale_b * B^T S^T ( sel o ( S B (a - b) - Y ) )
+ * b    == NULL : a alone.
+ * Y    == NULL : no data term (the y terms of a minibatch difference cancel).
+ * sel  : uint8 [batch][M]; mbd: one step's threshold descriptors.  Either, neither, never both.
+ * scale_b = scale_pp ? scale_pp[b] : scale, the output factor formed as the _pp gradients form it: (dtype)(scale_b / sqrt((double)(H*W)))
+ * gamma_b = gamma_pp ? gamma_pp[b] : gamma, cast once to dtype; beta likewise.
+ * c1 / c2 == NULL : that addend is absent.
+ * The difference a - b is formed where the first FFT pass loads it; the three terms of the result are rounded one by one in the
+ * stated order (o = factor*Re; o += beta*c1; o += gamma_b*c2) where the last pass stores it, the addends read at the index that is
+ * written: out may alias a, b, c1 or c2.  Problem b of a call with scale_pp / gamma_pp equals, bit for bit, problem b of the scalar
+ * call with its values, whatever the batch size and its place in the batch.  Not bit-compatible with two pnp_deblur_grad calls and
+ * a combination (one rounding of a - b instead of those of two gradients).  Uniform plans only (a mixed-scale plan: PNP_ERR_ARG).
+ * PNP_ERR_ARG before any device work: NULL plan, a or out; sel and mbd together; beta != 0 without c1; gamma != 0 or a gamma_pp
+ * without c2.  No allocation, no synchronisation: capturable.                                                              */
+int pnp_deblur_grad_step(pnp_deblur_plan* plan, const void* a, const void* b, const void* Y, const uint8_t* sel, const void* mbd,
+                         double scale, const double* scale_pp, double beta, const void* c1, double gamma, const double* gamma_pp,
+                         const void* c2, void* out, void* stream);
 /* Mixed-scale plans (a sampling-ratio sweep as one batch; csrc/deblur_mixed.hip): every problem has a down-sampler and
  * a measurement count M_b of its own.  The plan owns n_sets distinct down-samplers -- the five arrays of pnp_deblur_plan_create
  * concatenated over the sets, all HOST pointers: M_set [n_sets]; the tap rows of set s are rows [g_off[s], g_off[s+1]) of

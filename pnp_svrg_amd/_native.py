@@ -139,6 +139,8 @@ SIGNATURES = {
     'pnp_deblur_objective_mixed': (_i, [_vp, _vp, _vp, _d, _vp, _vp]),
     'pnp_draw_thresholds_mpp': (_i, [_vp, _i, _vp, _vp, ctypes.c_uint64, _vp, ctypes.c_uint32, _i, _vp, _vp, _vp]),
     'pnp_indicator_from_thresholds_m': (_i, [_vp, _i, _i, _vp, _vp, _vp]),
+    # the SVRG / SARAH correction and the step of Deblur in one gradient pass: scalar and per-problem in one call
+    'pnp_deblur_grad_step': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _d, _vp, _d, _vp, _d, _vp, _vp, _vp, _vp]),
     'pnp_legacy_choice':(_i, [_vp, ctypes.POINTER(ctypes.c_int), _vp, _i, _i, _vp, _vp]),
 }
 

@@ -505,8 +505,14 @@ class DeblurBatch(_BatchBase):
         g = self.plan.grad(z, self.Y, scale=alpha, out=out if c1 is None else self._scratch(z), **self._sel(mbs, j))
         return self._combine(g, out, beta, c1)
 
-    def grad_stoch_diff(self, z, w, mbs, j, out, alpha=1.0, beta=0.0, c1=None, gamma=0.0, c2=None):
+    def grad_stoch_diff(self, z, w, mbs, j, out, alpha=1.0, beta=0.0, c1=None, gamma=0.0, c2=None, one_pass=False):
         # gs(z) - gs(w) = B^T S^T sel (S B (z - w)) + (terms in y cancel): two gradients, one combine
+        # one_pass=True (opt-in): exactly that, and the step's addends, as ONE pnp_deblur_grad_step -- nothing allocated;
+        # it rounds z - w once instead of two gradients, so it is not the default's bits
+        if one_pass:
+            if self.M_vec is not None:
+                raise ValueError('grad_stoch_diff(one_pass=True): a mixed-scale DeblurBatch has no one-pass step (uniform batches only)')
+            return self.plan.grad_step(z, b=w, scale=alpha, beta=beta, c1=c1, gamma=gamma, c2=c2, out=out, **self._sel(mbs, j))
         g1 = self.plan.grad(z, self.Y, scale=alpha, out=torch.empty_like(z), **self._sel(mbs, j))
         g2 = self.plan.grad(w, self.Y, scale=alpha, out=self._scratch(z), **self._sel(mbs, j))
         return self._combine(ops.axpbypcz(1.0, g1, -1.0, g2, out=g1), out, beta, c1, gamma, c2)

@@ -139,6 +139,122 @@ __global__ __launch_bounds__(256) void k_rowpass(const cx<T>* in, cx<T>* out, co
     }
 }
 
+// ---- the one-pass step (pnp_deblur_grad_step): siblings of k_colpass on its tile layout.  k_colpass itself and
+// its instantiations are left as they are: the entry points above keep their code and their bits.
+
+// The line transforms of the G columns held in the LDS tile, in place: column g from smem[g*(N+1) + .] through the registers
+// and back (k_colpass between its load and its store loop); with TWIDDLE output k1 of column b0 + g is multiplied by
+// W_N^(+-(b0+g)*k1).  Whole-block collective: begins and ends with a barrier.
+template <typename T, int RA, int LA, bool INV, bool TWIDDLE>
+__device__ __forceinline__ void colpass_lines(cx<T>* smem, const cx<T>* __restrict__ tw_line, const cx<T>* __restrict__ tw_big,
+                                              int b0, int g, int lane) {
+    using S = LineSmem<T, RA, LA>;
+    constexpr int N = S::N, LG = S::LG;
+    __syncthreads();
+    cx<T> v[LG], tw[LG];
+    load_twiddles_gen<T, LG>(tw, tw_line, lane, N);
+#pragma unroll
+    for (int r = 0; r < RA; ++r) v[r] = smem[g * (N + 1) + (lane < LA ? lane : 0) + LA * r];
+    fft_gen<T, RA, LA, INV>(v, tw, smem + g * LG * (LG + 1), lane);
+    __syncthreads();
+    if (lane < RA) {
+#pragma unroll
+        for (int r = 0; r < LA; ++r) {
+            const int k1 = lane + RA * r;
+            cx<T> o = v[r];
+            if (TWIDDLE) {
+                cx<T> w = tw_big[(size_t)(b0 + g) * k1];
+                if (INV) w = cconj(w);
+                o = cmul(o, w);
+            }
+            smem[g * (N + 1) + k1] = o;
+        }
+    }
+    __syncthreads();
+}
+
+// First pass of the step: the forward column DFT + twiddle of the real image a - b, the difference formed at the load
+// (b == nullptr: a alone).  One pass over a and b, no scratch image.
+template <typename T, int RA, int LA>
+__global__ __launch_bounds__(256) void k_colpass_diff(const T* a_, const T* b_, cx<T>* __restrict__ out,
+                                                      const cx<T>* __restrict__ tw_line, const cx<T>* __restrict__ tw_big) {
+    using S = LineSmem<T, RA, LA>;
+    constexpr int N = S::N, G = S::G, LG = S::LG;
+    __shared__ cx<T> smem[S::ELEMS];
+    const int t = threadIdx.x, g = t / LG, lane = t % LG;
+    const int prob = blockIdx.y, b0 = blockIdx.x * G;
+    const size_t base = (size_t)prob * N * N;
+    const int p = t % G;
+    for (int a = t / G; a < N; a += 256 / G) {
+        const size_t i = base + (size_t)a * N + b0 + p;
+        T val = a_[i];
+        if (b_ != nullptr) val -= b_[i];
+        smem[p * (N + 1) + a] = {val, (T)0};
+    }
+    colpass_lines<T, RA, LA, false, true>(smem, tw_line, tw_big, b0, g, lane);
+    for (int k1 = t / G; k1 < N; k1 += 256 / G) out[base + (size_t)k1 * N + b0 + p] = smem[p * (N + 1) + k1];
+}
+
+// Middle pass of the step on a plan without a down-sampler: the last pass of the first blur (inverse column DFT, real epilogue
+// alpha * Re(v) - Y, minibatch mask) and the first pass of the adjoint blur (forward column DFT + twiddle of that real image) on
+// the same block of G columns, in place in w: a block reads and writes its own columns only and every read precedes the
+// writes.  The residual lives in the LDS tile and never goes to HBM.  Y == nullptr: no data term.
+template <typename T, int RA, int LA>
+__global__ __launch_bounds__(256) void k_colpass_mid(cx<T>* w, const cx<T>* __restrict__ tw_line, const cx<T>* __restrict__ tw_big,
+                                                     T alpha, const T* __restrict__ Y, const uint8_t* __restrict__ sel,
+                                                     const MbDesc* __restrict__ mbd) {
+    using S = LineSmem<T, RA, LA>;
+    constexpr int N = S::N, G = S::G, LG = S::LG;
+    __shared__ cx<T> smem[S::ELEMS];
+    const int t = threadIdx.x, g = t / LG, lane = t % LG;
+    const int prob = blockIdx.y, b0 = blockIdx.x * G;
+    const size_t base = (size_t)prob * N * N;
+    const int p = t % G;
+    for (int k1 = t / G; k1 < N; k1 += 256 / G) smem[p * (N + 1) + k1] = w[base + (size_t)k1 * N + b0 + p];
+    colpass_lines<T, RA, LA, true, false>(smem, tw_line, tw_big, b0, g, lane);
+    for (int m1 = t / G; m1 < N; m1 += 256 / G) {               // k_colpass's OUT_REAL epilogue, on the tile
+        const size_t i = base + (size_t)m1 * N + b0 + p;
+        T o = alpha * smem[p * (N + 1) + m1].x;
+        if (Y != nullptr) o -= Y[i];
+        if (sel != nullptr && sel[i] == 0) o = (T)0;
+        if (mbd != nullptr && !mb_member(mbd[prob], (uint32_t)(m1 * N + b0 + p))) o = (T)0;
+        smem[p * (N + 1) + m1] = {o, (T)0};
+    }
+    colpass_lines<T, RA, LA, false, true>(smem, tw_line, tw_big, b0, g, lane);
+    for (int k1 = t / G; k1 < N; k1 += 256 / G) w[base + (size_t)k1 * N + b0 + p] = smem[p * (N + 1) + k1];
+}
+
+// Last pass of the step: the inverse column DFT with the two-addend epilogue
+//     o = alpha_b * Re(v);  o += beta * c1[i];  o += gamma_b * c2[i]
+// each product and sum rounded on its own (so a zero gradient term leaves exactly beta*c1 + gamma*c2).  alpha_b =
+// (T)(alpha_pp[b] / alpha_div) with alpha_pp, as the PP form of k_colpass; gamma_b = (T)gamma_pp[b] with gamma_pp.  The addends
+// are read at the index that is written and nowhere else: out may alias c1 or c2 (no __restrict__ on the three).
+template <typename T, int RA, int LA>
+__global__ __launch_bounds__(256) void k_colpass_step(const cx<T>* __restrict__ in, T* out, const cx<T>* __restrict__ tw_line,
+                                                      const cx<T>* __restrict__ tw_big, T alpha, const double* __restrict__ alpha_pp,
+                                                      double alpha_div, T beta, const T* c1, T gamma,
+                                                      const double* __restrict__ gamma_pp, const T* c2) {
+    using S = LineSmem<T, RA, LA>;
+    constexpr int N = S::N, G = S::G, LG = S::LG;
+    __shared__ cx<T> smem[S::ELEMS];
+    const int t = threadIdx.x, g = t / LG, lane = t % LG;
+    const int prob = blockIdx.y, b0 = blockIdx.x * G;
+    const size_t base = (size_t)prob * N * N;
+    const int p = t % G;
+    if (alpha_pp != nullptr) alpha = (T)(alpha_pp[prob] / alpha_div);
+    if (gamma_pp != nullptr) gamma = (T)gamma_pp[prob];
+    for (int k1 = t / G; k1 < N; k1 += 256 / G) smem[p * (N + 1) + k1] = in[base + (size_t)k1 * N + b0 + p];
+    colpass_lines<T, RA, LA, true, false>(smem, tw_line, tw_big, b0, g, lane);
+    for (int m1 = t / G; m1 < N; m1 += 256 / G) {
+#pragma clang fp contract(off)
+        const size_t i = base + (size_t)m1 * N + b0 + p;
+        T o = alpha * smem[p * (N + 1) + m1].x;
+        if (c1 != nullptr) o = o + beta * c1[i];
+        if (c2 != nullptr) o = o + gamma * c2[i];
+        out[i] = o;
+    }
+}
+
 // 4-tap sparse operator (pylops Bilinear forward / its CSR adjoint): out[m] = sum_t w[m][t] * x[idx[m][t]]
 template <typename T>
 __global__ void k_gather4(const T* __restrict__ x, const int32_t* __restrict__ idx, const T* __restrict__ w, int n_out,
@@ -233,6 +349,45 @@ int run_grad(pnp_deblur_plan* p, const T* z, const T* Y, const uint8_t* sel, dou
     }
     return blur<T, RA, LA>(p, res, true, (T)(scale / std::sqrt((double)N)), (T)0, nullptr, nullptr, out, s, nullptr, scale_pp,
                            std::sqrt((double)N));
+}
+
+// pnp_deblur_grad_step: out = beta*c1 + gamma_b*c2 + scale_b * B^T S^T (sel o (S B (a - b) - Y)).  Without a down-sampler 5 launches
+// (k_colpass_diff -> k_rowpass -> k_colpass_mid -> k_rowpass -> k_colpass_step), with one 8: the middle is today's
+// k_colpass -> k_gather4 -> k_csr -> k_colpass of run_grad.
+template <typename T, int RA, int LA>
+int run_grad_step(pnp_deblur_plan* p, const T* a, const T* b, const T* Y, const uint8_t* sel, const MbDesc* mbd, double scale,
+                  const double* scale_pp, T beta, const T* c1, T gamma, const double* gamma_pp, const T* c2, T* out, hipStream_t s) {
+    constexpr int G = LineSmem<T, RA, LA>::G;
+    const int N = p->N, B = p->batch;
+    const double sqrtN = std::sqrt((double)N);
+    const T inv_sqrtN = (T)(1.0 / sqrtN);
+    const dim3 grid(p->n / G, B);
+    cx<T>* w0 = (cx<T>*)p->w0;
+    const cx<T>*twl = (const cx<T>*)p->tw_line, *twb = (const cx<T>*)p->tw_big, *FB = (const cx<T>*)p->FB;
+    k_colpass_diff<T, RA, LA><<<grid, 256, 0, s>>>(a, b, w0, twl, twb);
+    PNP_CHECK_LAUNCH();
+    k_rowpass<T, RA, LA, false, false><<<grid, 256, 0, s>>>(w0, w0, twl, twb, FB);
+    PNP_CHECK_LAUNCH();
+    if (p->g_idx == nullptr) {
+        k_colpass_mid<T, RA, LA><<<grid, 256, 0, s>>>(w0, twl, twb, inv_sqrtN, Y, sel, mbd);
+        PNP_CHECK_LAUNCH();
+    } else {
+        T *blurred = (T*)p->r1, *down = (T*)p->down, *res = (T*)p->r0;
+        k_colpass<T, RA, LA, true, false, false, true><<<grid, 256, 0, s>>>(w0, blurred, twl, twb, inv_sqrtN, (T)0, nullptr, nullptr,
+                                                                      nullptr, nullptr, 0.0);
+        PNP_CHECK_LAUNCH();
+        k_gather4<T><<<dim3((p->M + 255) / 256, B), 256, 0, s>>>(blurred, p->g_idx, (const T*)p->g_w, p->M, N, (T)-1, Y, sel, mbd, down);
+        PNP_CHECK_LAUNCH();
+        k_csr<T><<<dim3((N + 255) / 256, B), 256, 0, s>>>(down, p->a_rowptr, p->a_col, (const T*)p->a_val, N, p->M, res);
+        PNP_CHECK_LAUNCH();
+        int rc = col_fwd<T, RA, LA>(p, res, B, s);
+        if (rc) return rc;
+    }
+    k_rowpass<T, RA, LA, true, false><<<grid, 256, 0, s>>>(w0, w0, twl, twb, FB);
+    PNP_CHECK_LAUNCH();
+    k_colpass_step<T, RA, LA><<<grid, 256, 0, s>>>(w0, out, twl, twb, (T)(scale / sqrtN), scale_pp, sqrtN, beta, c1, gamma, gamma_pp, c2);
+    PNP_CHECK_LAUNCH();
+    return PNP_OK;
 }
 
 template <typename T, int RA, int LA>
@@ -445,6 +600,26 @@ extern "C" int pnp_deblur_grad_mb(pnp_deblur_plan* p, const void* z, const void*
     double* oo = (double*)out;
     return p->NL == 16 ? run_grad<double, 16, 16>(p, zz, yy, nullptr, scale, oo, s, d)
          : p->NL == 12 ? run_grad<double, 8, 16>(p, zz, yy, nullptr, scale, oo, s, d) : run_grad<double, 8, 8>(p, zz, yy, nullptr, scale, oo, s, d);
+}
+
+// the variance-reduced correction and the step in one gradient pass:
+//     out = beta*c1 + gamma_b*c2 + scale_b * B^T S^T ( sel o (S B (a - b) - Y) ),   b, Y, c1, c2 nullable
+extern "C" int pnp_deblur_grad_step(pnp_deblur_plan* p, const void* a, const void* b, const void* Y, const uint8_t* sel,
+                                    const void* mbd, double scale, const double* scale_pp, double beta, const void* c1,
+                                    double gamma, const double* gamma_pp, const void* c2, void* out, void* stream) {
+    PNP_CHECK_ARG(p && a && out, "null argument");
+    PNP_CHECK_ARG(!(sel && mbd), "sel and mbd together: a minibatch is an indicator or this step's descriptors, never both");
+    PNP_CHECK_ARG(c1 || beta == 0.0, "beta != 0 needs c1");
+    PNP_CHECK_ARG(c2 || (gamma == 0.0 && !gamma_pp), "gamma != 0 or gamma_pp needs c2");
+    PNP_DB_UNIFORM(p);
+    hipStream_t s = (hipStream_t)stream;
+    const MbDesc* d = (const MbDesc*)mbd;
+#define PNP_DB_STEP(T, RA, LA)                                                                                             \
+    run_grad_step<T, RA, LA>(p, (const T*)a, (const T*)b, (const T*)Y, sel, d, scale, scale_pp, (T)beta, (const T*)c1, (T)gamma, \
+                             gamma_pp, (const T*)c2, (T*)out, s)
+    if (p->dtype == PNP_F32) return p->NL == 16 ? PNP_DB_STEP(float, 16, 16) : p->NL == 12 ? PNP_DB_STEP(float, 8, 16) : PNP_DB_STEP(float, 8, 8);
+    return p->NL == 16 ? PNP_DB_STEP(double, 16, 16) : p->NL == 12 ? PNP_DB_STEP(double, 8, 16) : PNP_DB_STEP(double, 8, 8);
+#undef PNP_DB_STEP
 }
 
 // forward model S B x (DeblurSR.py:110-112), for problem setup / f(w); out real [batch][M]

@@ -185,6 +185,16 @@ def _check_fused(name, batch, prox, log_objective):
         raise ValueError(f'{name}(fused=True) needs ' + ', '.join(missing))
 
 
+def _check_one_pass(name, batch, fused):
+    """`one_pass=True` of SvrgEngine and SarahEngine: the correction and the step of the streaming path as ONE
+    pnp_deblur_grad_step."""
+    if getattr(batch, 'kind', None) != 'deblur' or getattr(batch, 'M_vec', None) is not None:
+        raise ValueError(f'{name}(one_pass=True) needs a uniform DeblurBatch (got {type(batch).__name__}'
+                         f'{" of mixed scales" if getattr(batch, "M_vec", None) is not None else ""}): the one-pass step is a Deblur kernel')
+    if fused:
+        raise ValueError(f'{name}(one_pass=True) goes with the streaming path, not with fused=True (the one-kernel CSMRI iteration)')
+
+
 class _FusedStep:
     """The one-kernel inner iteration of GdEngine, SgdEngine and SagaEngine (fused=True) and their span kernels."""
 
@@ -426,11 +436,17 @@ class SvrgEngine(_T2PerProblem, _StochEngine):
     with s % T2[b] == 0 and walks, bit for bit, the trajectory a scalar engine with T2[b] walks.  The draw slots then hold a window
     of `span` steps (default: AHEAD) drawn with the absolute step ids, `step()` refreshes with a full gradient into a scratch and
     one pnp_refresh_pp launch (the unfolded refresh, also on the one-kernel path), `run_span(n)` runs n steps in launches of at
-    most `span` steps where `outer_kernel_ok()` holds, and there is no hipGraph form (`graph_ok()` is False, `run_outer` raises)."""
+    most `span` steps where `outer_kernel_ok()` holds, and there is no hipGraph form (`graph_ok()` is False, `run_outer` raises).
+    one_pass=True (opt-in): on a uniform DeblurBatch the streaming path's correction and step are ONE
+    pnp_deblur_grad_step (not the default's bits: z - w is rounded once); ValueError on any other batch and with fused=True."""
     FUSED_MIN_BATCH = 192
 
     def __init__(self, batch, prox, eta, T2, mini_batch_size, lr_decay=1.0, variant='svrg', n_log=4096, seed=0, fused=None,
-                 fold_outer=True, draw_id=None, span=None, log_objective=False):
+                 fold_outer=True, draw_id=None, span=None, log_objective=False, one_pass=False):
+        self.one_pass = bool(one_pass)
+        if self.one_pass:
+            _check_one_pass('SvrgEngine', batch, fused)
+        self._diff_kw = dict(one_pass=True) if self.one_pass else {}      # (off: grad_stoch_diff gets the arguments it always got)
         if np.ndim(T2) == 0 and span is not None:
             raise ValueError('span is the draw window of a per-problem T2; a scalar T2 draws an outer iteration at a time')
         pp = self._init_t2(batch, T2, span)
@@ -532,7 +548,7 @@ class SvrgEngine(_T2PerProblem, _StochEngine):
             return self.z
         if self.variant == 'svrg':
             self.b.grad_stoch_diff(self.z, self.w, self.mbs, j, out=self.z, alpha=self._c('-lr/mb', k, -lr / self.mb), beta=1.0,
-                                   c1=self.z, gamma=self._c('-lr', k, -lr), c2=self.mu)
+                                   c1=self.z, gamma=self._c('-lr', k, -lr), c2=self.mu, **self._diff_kw)
         else:
             self._step_along_mu(lr, k)
         return self.prox(self.z, self.b.xrec, sse_out)
@@ -650,10 +666,16 @@ class SarahEngine(_T2PerProblem, _StochEngine):
     (`outer_trace()`, `psnr_trace_of(b)`).  At a step where any problem refreshes `step()` makes the outer step for the WHOLE batch
     into scratch buffers and adopts it per problem with one pnp_refresh_pp and one pnp_select_pp launch; `run_span(n)` runs n steps in
     launches of pnp_csmri_sarah_span_pp where `outer_kernel_ok()` holds and lr_decay == 1.  `span` is the draw window as in
-    SvrgEngine.  There is no hipGraph form, no objective log, and no prox whose result depends on its call count."""
+    SvrgEngine.  There is no hipGraph form, no objective log, and no prox whose result depends on its call count.
+    one_pass=True (opt-in): on a uniform DeblurBatch v_next = v_prev + (gs(w_next) - gs(w_prev)) / mb is ONE
+    pnp_deblur_grad_step (not the default's bits); ValueError on any other batch and with fused=True."""
 
     def __init__(self, batch, prox, eta, T2, mini_batch_size, lr_decay=1.0, n_log=4096, seed=0, draw_id=None, log_objective=False,
-                 *, fused=False, split_log=False, span=None):
+                 *, fused=False, split_log=False, span=None, one_pass=False):
+        self.one_pass = bool(one_pass)
+        if self.one_pass:
+            _check_one_pass('SarahEngine', batch, fused)
+        self._diff_kw = dict(one_pass=True) if self.one_pass else {}      # (off: grad_stoch_diff gets the arguments it always got)
         if np.ndim(T2) != 0:
             if not split_log:
                 raise ValueError('SarahEngine takes a scalar T2 (its outer prox logs a row of its own: rows would stop lining up) '
@@ -737,7 +759,7 @@ class SarahEngine(_T2PerProblem, _StochEngine):
             self.n_prox += 1
         else:
             self.b.grad_stoch_diff(self.w_next, self.w_prev, self.mbs, j, out=self.v_next, alpha=self._c('1/mb', 0, 1.0 / self.mb),
-                                   beta=1.0, c1=self.v_prev)
+                                   beta=1.0, c1=self.v_prev, **self._diff_kw)
             ops.axpbypcz(1.0, self.z, self._c('-lr', k, -lr), self.v_next, out=self.z)
             self.z = self._prox(self.z)
             self.v_prev, self.v_next = self.v_next, self.v_prev

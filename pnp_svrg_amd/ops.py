@@ -806,6 +806,25 @@ class DeblurPlan:
             _route('pnp_deblur_grad', [self._h, _p(z), _p(Y), _p(sel), _pp(scale, self.B), _p(out), _stream()])
         return out
 
+    def grad_step(self, a, b=None, Y=None, sel=None, mbd=None, scale=1.0, beta=0.0, c1=None, gamma=0.0, c2=None, out=None):
+        """pnp_deblur_grad_step: beta * c1 + gamma * c2 + scale * B^T S^T (sel o (S B (a - b) - Y)) in one gradient pass (DESIGN
+        9.12).  b, Y, c1, c2: None = absent; sel / mbd as in `grad`; scale, gamma: a scalar or a float64 [B] device tensor (per
+        problem).  out may be a, b, c1 or c2.  Uniform plans only."""
+        assert a.dtype == self.dtype and a.numel() == self.B * self.N and (Y is None or Y.numel() == self.B * self.M)
+        assert sel is None or mbd is None
+        if self.M_vec is not None:
+            raise ValueError('grad_step: a mixed-scale plan has no one-pass step (uniform plans only)')
+        assert mbd is None or (mbd.dtype == torch.int64 and tuple(mbd.shape) == (self.B, 2))
+        for t in (b, c1, c2):
+            assert t is None or (t.dtype == self.dtype and t.numel() == a.numel())
+        assert (Y is None or Y.dtype == self.dtype) and (sel is None or (sel.dtype == torch.uint8 and sel.numel() == self.B * self.M))
+        out = out if out is not None else torch.empty_like(a)
+        assert out.dtype == self.dtype and out.numel() == a.numel()
+        sc, ga = _pp(scale, self.B), _pp(gamma, self.B)
+        N.call('pnp_deblur_grad_step', self._h, _p(a), _p(b), _p(Y), _p(sel), _p(mbd), sc[0], _p(sc[1]), float(beta), _p(c1),
+               ga[0], _p(ga[1]), _p(c2), _p(out), _stream())
+        return out
+
     def resized(self, batch):
         """A plan for `batch` problems on this plan's kernel spectrum and down-sampler (DeblurBatch.tile).  A mixed-scale plan
         repeats its problems' sets: batch = n * B, problem t * B + i on the set of problem i."""

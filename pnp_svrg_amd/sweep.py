@@ -154,7 +154,7 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
                 hist_size=50, H=256, W=256, dtype=torch.float32, max_batch=128, seeding='generator', variant='svrg', run_seed=1,
                 keep_trace=False, graph=True, kernel='Minimal', lr_decay=1.0, denoiser_kwargs=None, sigma_modifier=None,
                 shared_matrix=False, wide_trials=False, sarah_trials=False, t2_trials=False, objective=False, sarah_fused=False,
-                fused_steps=False, one_launch=False, hist_trials=False, mixed_scales=False, sarah_t2_trials=False):
+                fused_steps=False, one_launch=False, hist_trials=False, mixed_scales=False, sarah_t2_trials=False, one_pass_diff=False):
     """Runner for `run_sweep` / `grid_search` over any cell of the reference's sweep (script_diff_sampratio_set12.py:23-25,
     41-51, 64-131): problem in {'csmri', 'deblur', 'pr'} x algorithm in {'gd', 'sgd', 'svrg', 'saga', 'sarah'} x denoiser in
     {'tv', 'nlm', factory}; `n_inner` inner iterations (prox evaluations of the stepped iterate) per item, hyper-parameters
@@ -227,6 +227,11 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
     SarahEngine(T2=[B] ints, split_log=True) and advances by `run_span`; its rows ('psnr_trace' included: `psnr_trace_of`) are those of
     the per-trial runner.  Without it `check_trials` refuses the key, with or without t2_trials, in the words it always used.
     `run(items)` itself is unchanged by it.
+    one_pass_diff: opt in to the one-pass correction and step of Deblur (SvrgEngine / SarahEngine with one_pass=True):
+    problem='deblur', algorithm in {'svrg', 'sarah'}, without mixed_scales -- anything else is a ValueError that names the offender.
+    An inner iteration's two minibatch gradients and their combination become ONE pnp_deblur_grad_step; rows agree with the default's
+    to rounding, not bit for bit.  Rides through `run(items)` and through trial-batched grids.  False (default): engines, launches,
+    rows and messages are exactly what they were.
     Beside `run(items)` the runner offers the pieces of a trial-batched grid (`grid_search(batch_trials=True)`):
     `run.prepare_data(items)` builds a rank's batches WITHOUT engines, `run.run_trials(data, trials, max_batch_trials)` runs a list
     of trials ({'eta', 'mini_batch_size', 'sigma_modifier'} overrides) on them as tiled batches, `run.data_key` says which runners
@@ -287,6 +292,17 @@ def make_runner(images, problem='csmri', algorithm='svrg', denoiser='tv', *, eta
     if sarah_t2_trials and not (sarah_trials and algorithm == 'sarah'):
         raise ValueError(f"sarah_t2_trials=True needs sarah_trials=True and algorithm='sarah' (got sarah_trials={bool(sarah_trials)!r}, "
                          f'algorithm {algorithm!r}): it makes T2 a per-problem key of the trial-batched pnp_sarah grid')
+    if not isinstance(one_pass_diff, (bool, np.bool_)):
+        raise ValueError(f'one_pass_diff: True or False, got {one_pass_diff!r}')
+    if one_pass_diff:
+        if problem != 'deblur':
+            raise ValueError(f"one_pass_diff=True is for problem='deblur' (got {problem!r}): the one-pass step is a Deblur kernel")
+        if algorithm not in ('svrg', 'sarah'):
+            raise ValueError(f"one_pass_diff=True is for algorithm in ('svrg', 'sarah') (got {algorithm!r}): the others take no "
+                             'difference of minibatch gradients')
+        if mixed_scales:
+            raise ValueError('one_pass_diff=True needs mixed_scales=False (a mixed-scale batch has no one-pass step)')
+        eng_kw = dict(eng_kw, one_pass=True)                    # (rides with the other opt-in engine keywords)
     if shared_matrix and problem != 'pr':
         raise ValueError(f"shared_matrix=True is for problem='pr' (got {problem!r}): only its problems have a matrix to share")
     mb, dkw = mini_batch_size, dict(denoiser_kwargs or {})
